@@ -101,6 +101,10 @@ def parse():
                          "N > 1 code path - async gather to rank 0, fixed-order sum, overlapped steps, device-side "
                          "all_reduce of the settle loop.  Also switched on by BAS_BENCH_FORCE_PG=1")
     ap.add_argument("--no-self-check", action="store_true", help="skip the oracle comparison of the timed path's output")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy "
+                         "(scene: y [2, T_out] and peak; stream: the last block and the running peak), at most 64 MB "
+                         "in all; the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--no-traffic", action="store_true",
                     help="do not measure roofline.traffic (two short child runs under rocprofv3 --pmc, ~10 s each, before "
                          "anything else; N = 1 scene mode only) - the figure of profiles/fir_hbm_traffic.json is then replayed")
@@ -223,6 +227,31 @@ def measure_traffic(args):
     return out, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy (float32 stays float32, anything else becomes float64).  An array that
+    would take the total past 64 MB is replaced by a fixed, seeded sample of its elements (flattened, C order) and
+    the sample's positions go beside it as <name>_sample_index.npy (float64).  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float32 else v.astype(np.float64) for k, v in arrays.items()}
+    budget = (DUMP_LIMIT_BYTES - 4096) // max(1, len(arrays))              # (room for the .npy headers)
+    written = {}
+    for name, a in arrays.items():
+        if a.nbytes > budget:
+            m = budget // (a.itemsize + 8)
+            pos = np.sort(np.random.default_rng(0).choice(a.size, size=m, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), pos.astype(np.float64))
+            written[f"{name}_sample_index.npy"] = [m]
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[f"{name}.npy"] = list(a.shape)
+    return written
+
+
 class HipEvents:
     """Raw hipEvent_t pairs via libamdhip64 (the library records them on the launch stream)."""
 
@@ -322,6 +351,8 @@ def stream_mode(args):
     if collective:
         dist.barrier()
     el = time.perf_counter() - t0
+    # (copied before the event blocks below render into the same buffers)
+    dumped = {"y": y.cpu().numpy(), "peak": [st.peak]} if (args.dump_outputs and y is not None) else None
     if collective:
         t = torch.tensor([el], dtype=torch.float64, device="cpu" if gloo else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -365,7 +396,8 @@ def stream_mode(args):
                                                f"{n_ev} plain-launch blocks behind the timed region (the timed blocks are graph replays)"},
                           "valu": {"achieved": algo_flops / (fir_ms / 1e3) / 1e12, "peak": FP32_VALU_PEAK_TF, "unit": "TFLOP/s",
                                    "frac": algo_flops / (fir_ms / 1e3) / 1e12 / FP32_VALU_PEAK_TF},
-                          "out_block_shape": list(y.shape)}))
+                          "out_block_shape": list(y.shape),
+                          **({"dumped_outputs": dump_outputs(args.dump_outputs, dumped)} if dumped is not None else {})}))
     if collective:
         dist.destroy_process_group()
 
@@ -695,6 +727,9 @@ def run_scene(args, bas, dev, world, rank, backend, scaling, tbl, host_u, with_e
         step(None if use_graph else i)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and with_events and rank == 0:      # the last timed step's (y, peak), before anything below renders again
+        y_last, peak_last = (sc.y_final, sc.peak) if collective else (ys[0], sc.last_peak)
+        sc.dumped = {"y": y_last.cpu().numpy(), "peak": peak_last.reshape(-1)[:1].cpu().numpy()}
     if collective:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if backend != "nccl" else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -932,6 +967,8 @@ def main():
             out["rehearsal"] = f"{world} ranks on ONE device, gather staged through host memory ({backend}): " \
                                "a functional check of the multi-rank path, not a scaling measurement"
         out.update(info)
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, sc.dumped)
         if cpu_line is not None:
             out["cpu_baseline"] = cpu_line
         emit(json.dumps(out))
