@@ -327,6 +327,27 @@ int bas_render_stream_block_profiled_f32(float *x, long x_stride, const float *p
                                          float *running_peak, bas_stream_t stream,
                                          void *ev_begin, void *ev_end);
 
+/* ---- batches of independent renders (no reference counterpart as a batch; DESIGN.md "Batches") ----------
+ * B items, each rendered as if by make_signal_move_2d alone (apply_hrtf.py:356-466), in ONE render: item b occupies
+ * [off_b, off_b + T_in_b) of every source row (T_in_b = len_b rounded up to K, :405-406), followed by a zero gap of G
+ * samples (G >= L-1, a multiple of K) before off_{b+1}; its output is the window [off_b, off_b + T_in_b + L - 1) of the
+ * long render.  offsets [B] and lengths [B] are int64 DEVICE arrays; off_0 = 0, strictly increasing.
+ *
+ * bas_batch_pack_f32: sig [B][n_src][N] float32 (len_b <= N valid samples per item) -> x [n_src] rows of x_stride
+ *   floats (16-byte aligned, x_stride % 4 == 0; every float of a row written: the zero pad of :406 and the gaps);
+ *   elev/azim [B][n_src][n_q_max] float64 (the item's angles at t = 0, K, .., T_in_b: :429, :435) -> elev_out/azim_out
+ *   [n_src][T_in/K + 1]; the gap's inner boundaries repeat the item's last angle (their chunks' input is zero).  One launch.
+ * bas_batch_finish_f32: y [2] rows of y_stride floats (the long render); out_lengths [B] = T_in_b + L - 1 (:410).
+ *   peaks[b] = m_b = max|y| over both ears of item b's window (:462, device float [B], overwritten); with normalize != 0
+ *   the rule per item: if m_b > 1 the window is divided by m_b (:463-464).  out == NULL: in place; else out [B][2]
+ *   [out_len_max] is written whole (the window, then zeros).  A memset and two launches (maxima, then scale or compact);
+ *   bitwise deterministic (max is exact; atomicMax on the bits of non-negative floats); B <= 65535. */
+int bas_batch_pack_f32(const float *sig, int n_items, int n_src, long N, const long *lengths, const long *offsets,
+                       const double *elev, const double *azim, long n_q_max, int K, long T_in, float *x,
+                       long x_stride, double *elev_out, double *azim_out, bas_stream_t stream);
+int bas_batch_finish_f32(float *y, long y_stride, int n_items, const long *offsets, const long *out_lengths,
+                         long out_len_max, int normalize, float *out, float *peaks, bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's
