@@ -141,7 +141,9 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
     are ignored).  normalize: "each" (apply_hrtf.py:462-464 per item) or "none".  branch: the numeric branch of the
     angle step ("f64" or "pyfloat"; one per call).
     Returns device tensors (out [B, T_out_max, 2] float32, out_lengths [B] int64, peaks [B] float32): out[b, :out_len_b]
-    is item b's render, zeros beyond; peaks[b] = max|y_b| before the rule (the reference's m).  Equal-length batches
+    is item b's render, zeros beyond; peaks[b] = max|y_b| before the rule (the reference's m).  An empty item renders
+    as L-1 zero samples with m = 0 (apply_hrtf.py:405-464); at L = 1, where the reference's max of an empty output
+    raises, as no samples with m = 0.  Equal-length batches
     rendered in one piece come back as a zero-copy strided view of the render buffer, other batches (or contiguous=True)
     as a transposed view of a contiguous [B, 2, T_out_max] tensor.
     check=True: ask the library for device-side errors after every render (synchronises).  max_samples: the split limit
@@ -161,8 +163,9 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
     dev = tbl.device
     L = tbl.L
     groups = split_items(n, K, L, n_src, max_samples)
-    if events is not None and len(groups) != 1:
-        raise ValueError("events: the batch is split into several renders")
+    layouts = [plan_layout(n[b0:b1], K, S, L) for b0, b1 in groups]
+    if events is not None and (len(groups) != 1 or layouts[0].T_in == 0):
+        raise ValueError("events: the batch is split into several renders, or is one empty item (no launch)")
     with _hip.on_device(dev):
         sig = torch.as_tensor(signals).to(device=dev, dtype=torch.float32).reshape(B, n_src, N).contiguous()
         e_all = torch.as_tensor(elev).to(device=dev, dtype=torch.float64).reshape(B, n_src, -1).contiguous()
@@ -170,13 +173,16 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
         n_q_max = e_all.shape[-1]
         out_len = -(-n // K) * K + L - 1
         T_out_max = int(out_len.max())
-        in_place = len(groups) == 1 and not contiguous and bool((n == n[0]).all())
+        in_place = len(groups) == 1 and layouts[0].T_in > 0 and not contiguous and bool((n == n[0]).all())
         peaks = torch.empty((B,), dtype=torch.float32, device=dev)
         out = None if in_place else torch.empty((B, 2, T_out_max), dtype=torch.float32, device=dev)
         stream = _hip.current_stream(dev)
-        for b0, b1 in groups:
-            lay = plan_layout(n[b0:b1], K, S, L)
+        for (b0, b1), lay in zip(groups, layouts):
             nb = b1 - b0
+            if lay.T_in == 0:       # one empty item (split_items isolates it, or the batch is one): L-1 zeros, m = 0
+                out[b0:b1].zero_()
+                peaks[b0:b1].zero_()
+                continue
             meta = torch.from_numpy(np.stack([lay.lengths, lay.offsets, lay.out_lengths])).to(dev)   # one H2D copy
             stride = (lay.T_in + 3) // 4 * 4
             x = torch.empty((n_src, stride), dtype=torch.float32, device=dev)[:, :lay.T_in]

@@ -153,3 +153,20 @@ def test_batch_entry_points_are_declared():
     hdr = open(os.path.join(ROOT, "include", "bas.h")).read()
     for name in ("bas_batch_pack_f32", "bas_batch_finish_f32"):
         assert name in bas._hip.SIGNATURES and f"int {name}(" in hdr
+
+
+@pytest.mark.parametrize("K,L", [(512, 128), (128, 513), (64, 1)])
+def test_planner_empty_items(K, L):
+    """Empty items: a lone empty item is a render of T_in 0 (render_batch launches nothing for it and returns its L-1
+    zeros); several empty items still have their gaps, so the render is not empty; the split can isolate an empty item
+    at either end."""
+    G = batch.gap_samples(K, L)
+    lay = batch.plan_layout([0], K, K, L)
+    assert (lay.T_in, lay.n_q, list(lay.out_lengths), list(lay.fillers)) == (0, 1, [L - 1], [0])
+    lay = batch.plan_layout([0, 0, 0], K, K, L)
+    assert lay.T_in == 2 * G and list(lay.offsets) == [0, G, 2 * G] and list(lay.out_lengths) == [L - 1] * 3
+    assert (lay.offsets + lay.out_lengths <= lay.T_out).all()
+    groups = batch.split_items([3 * K, 0], K, L, max_samples=3 * K)
+    assert groups == [(0, 1), (1, 2)] and batch.plan_layout([0], K, K, L).T_in == 0
+    assert batch.split_items([0, 3 * K], K, L, max_samples=3 * K) == [(0, 1), (1, 2)]
+    assert batch.split_items([0, 5, 0], K, L, max_items=1) == [(0, 1), (1, 2), (2, 3)]
