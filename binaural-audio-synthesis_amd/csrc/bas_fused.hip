@@ -782,10 +782,14 @@ extern "C" const char *bas_render_fused_kernel_name(int n_src, long T_in, int K,
 
 #ifdef BAS_DIAG
 // diagnostic build only (tests, tools/stress_fused.py): which kernel a shape gets - waves per workgroup | h-only rows << 4 |
-// split roles << 5 | four waves per tile of 2048 << 6 (0: not served)
+// split roles << 5 | four waves per tile of 2048 << 6 | the FIR kernel writes y itself (direct output: no slab reduce) << 7 |
+// the slab reduce is the wide kernel (bas_launch_slab_reduce: more than 24 parts per tile) << 8 (0: not served)
 extern "C" int bas_debug_fused_plan(int n_src, long T_in, int K, int S, int L) {
     const FzPlan p = fz_plan(n_src, T_in, K, S, L);
-    return p.nw | (p.honly << 4) | (p.split << 5) | (p.quad << 6);
+    if (!p.nw) return 0;
+    const int direct = p.units_per_wg % n_src == 0;
+    const int wide = !direct && (n_src + p.units_per_wg - 1) / p.units_per_wg + 1 > 24;
+    return p.nw | (p.honly << 4) | (p.split << 5) | (p.quad << 6) | (direct << 7) | (wide << 8);
 }
 #endif
 
