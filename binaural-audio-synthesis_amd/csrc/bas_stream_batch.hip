@@ -1,0 +1,136 @@
+// Batched streams (include/bas.h "batched streams"): G independent streams of n_src sources advance by one
+// block of B samples in ONE render.  Session g's window [halo | block] starts at g·W of every source row, W = halo + B + K:
+// a zero chunk follows every window (its two boundaries are the end of session g and the start of session g+1, so the
+// crossfade of apply_hrtf.py:431-442 never mixes two sessions' angles into an emitted sample).  The angle rows hold nh + nb
+// boundaries per session, session g's from g·(nh + nb).  Two entry points around the unchanged render:
+//   bas_stream_batch_pack_f32     - scatter [G][n_src][B] blocks and [G][n_src][nb] angles into the windows' block columns
+//                                   and angle slots (never the halo columns, the halo angles or the gaps), one launch;
+//   bas_stream_batch_epilogue_f32 - per session, what bas_stream_epilogue_f32 does for one stream: the running peak over
+//                                   the emitted samples and the moves of the carried state, one launch.
+#include "bas_internal.h"
+
+#define SB_THREADS 256
+
+__device__ __forceinline__ bool sb_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// One row of workgroups per session (blockIdx.y = g).  Items of a session: n_src rows of ceil(B/4) quads, then n_src rows
+// of nb (elev, azim) pairs.  A quad moves as one 16-byte load and store when both rows are 16-byte aligned and B % 4 == 0
+// (every quad of the row then is), else as up to 4 scalars (still coalesced across a wave).
+__global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
+    const float *__restrict__ blocks, const double *__restrict__ elev, const double *__restrict__ azim, int n_src,
+    long B, long W, int halo, int nh, int nb, float *__restrict__ x, long x_stride, double *__restrict__ elev_out,
+    double *__restrict__ azim_out, long ang_stride) {
+    const int g = blockIdx.y;
+    const long nq = (B + 3) >> 2;
+    const long n_x = (long)n_src * nq, n_items = n_x + (long)n_src * nb;
+    const long gstride = (long)gridDim.x * SB_THREADS;
+    for (long i = blockIdx.x * (long)SB_THREADS + threadIdx.x; i < n_items; i += gstride) {
+        if (i < n_x) {
+            const int s = (int)(i / nq);
+            const long j0 = (i - (long)s * nq) << 2;
+            const float *src = blocks + ((long)g * n_src + s) * B;
+            float *dst = x + (long)s * x_stride + (long)g * W + halo;
+            if ((B & 3) == 0 && sb_aligned16(src) && sb_aligned16(dst)) {
+                *reinterpret_cast<f32x4 *>(dst + j0) = *reinterpret_cast<const f32x4 *>(src + j0);
+            } else {
+                for (int k = 0; k < 4 && j0 + k < B; ++k) dst[j0 + k] = src[j0 + k];
+            }
+        } else {
+            const long r = i - n_x;
+            const int s = (int)(r / nb);
+            const int c = (int)(r - (long)s * nb);
+            const long from = ((long)g * n_src + s) * nb + c;
+            const long to = (long)s * ang_stride + (long)g * (nh + nb) + nh + c;
+            elev_out[to] = elev[from];
+            azim_out[to] = azim[from];
+        }
+    }
+}
+
+// One row of workgroups per session.  peaks[g] = max(peaks[g], max|y[e][g·W + halo .. g·W + halo + B)|), e = 0, 1
+// (atomicMax on the bits of non-negative floats: exact and order-free), then bas_carry_moves on session g's offset pointers.
+__global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_epilogue_kernel(
+    float *__restrict__ x, long x_stride, int n_src, int halo, long B, long W, double *__restrict__ elev,
+    double *__restrict__ azim, long ang_stride, int nh, int nb, double *__restrict__ last, const float *__restrict__ y,
+    long y_stride, unsigned int *__restrict__ peak_bits) {
+    const int g = blockIdx.y;
+    const long tid = blockIdx.x * (long)SB_THREADS + threadIdx.x;
+    const long nthreads = (long)gridDim.x * SB_THREADS;
+    float lmax = 0.f;
+    for (int e = 0; e < 2; ++e) {
+        const float *w = y + e * y_stride + (long)g * W + halo;
+        const long head = sb_aligned16(w) ? 0 : min(B, (long)((16 - (reinterpret_cast<uintptr_t>(w) & 15)) >> 2));
+        if (blockIdx.x == 0 && threadIdx.x < head) lmax = fmaxf(lmax, fabsf(w[threadIdx.x]));
+        const float *wa = w + head;
+        const long nq = (B - head) >> 2;
+        for (long i = tid; i < nq; i += nthreads) {
+            const f32x4 q = *reinterpret_cast<const f32x4 *>(wa + 4 * i);
+            lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
+        }
+        const long tail0 = head + 4 * nq;
+        if (blockIdx.x == 0 && tail0 + threadIdx.x < B) lmax = fmaxf(lmax, fabsf(w[tail0 + threadIdx.x]));
+    }
+    bas_block_peak_max(lmax, peak_bits + g);
+    BasCarry C;
+    C.x = x + (long)g * W; C.x_stride = x_stride; C.n_src = n_src; C.halo = halo; C.B = B;
+    C.elev = elev + (long)g * (nh + nb); C.azim = azim + (long)g * (nh + nb); C.ang_stride = ang_stride;
+    C.nh = nh; C.nb = nb; C.last = last + 2L * n_src * g; C.running_peak = nullptr;
+    bas_carry_moves(C, tid, nthreads);
+}
+
+// workgroups per session: about 8 per CU over all sessions, at least one, at most one per 1024 items of a session's work
+static int sb_blocks_x(int n_sessions, long work) {
+    long want = (8L * bas_device_cus() + n_sessions - 1) / n_sessions;
+    const long cap = (work + 1023) / 1024;
+    if (want > cap) want = cap;
+    if (want < 1) want = 1;
+    if (want > 65535) want = 65535;
+    return (int)want;
+}
+
+// the checks both entry points share: sizes, then the strides against the layout's extent
+static int sb_check_layout(const char *what, int n_sessions, int n_src, long B, int K, int halo, long x_stride,
+                           long ang_stride) {
+    BAS_REQUIRE(n_sessions > 0 && n_sessions <= 65535 && n_src > 0 && K > 0 && B > 0 && halo >= 0, BAS_E_SHAPE,
+                "%s: need 0 < n_sessions <= 65535, n_src > 0, K > 0, B > 0, halo >= 0 (G=%d n_src=%d K=%d B=%ld halo=%d)",
+                what, n_sessions, n_src, K, B, halo);
+    BAS_REQUIRE(B % K == 0 && halo % K == 0, BAS_E_SHAPE, "%s: B (%ld) and halo (%d) must be multiples of K (%d)", what, B,
+                halo, K);
+    const long W = halo + B + K, nh = halo / K, nb = B / K + 1;
+    BAS_REQUIRE(x_stride >= n_sessions * W - K && ang_stride >= n_sessions * (nh + nb), BAS_E_SHAPE,
+                "%s: strides shorter than the layout (x_stride %ld < %ld or ang_stride %ld < %ld)", what, x_stride,
+                n_sessions * W - K, ang_stride, n_sessions * (nh + nb));
+    return 0;
+}
+
+extern "C" int bas_stream_batch_pack_f32(const float *blocks, const double *elev, const double *azim, int n_sessions,
+                                         int n_src, long B, int K, int halo, float *x, long x_stride, double *elev_out,
+                                         double *azim_out, long ang_stride, bas_stream_t stream) {
+    int rc = sb_check_layout("bas_stream_batch_pack_f32", n_sessions, n_src, B, K, halo, x_stride, ang_stride);
+    if (rc) return rc;
+    BAS_REQUIRE(blocks && elev && azim && x && elev_out && azim_out, BAS_E_NULL, "bas_stream_batch_pack_f32: null pointer");
+    const long W = halo + B + K;
+    const int nh = halo / K, nb = (int)(B / K + 1);
+    const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
+    hipLaunchKernelGGL(bas_stream_batch_pack_kernel, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev, azim,
+                       n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride);
+    return bas_check_launch("bas_stream_batch_pack_f32");
+}
+
+extern "C" int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
+                                             double *elev, double *azim, long ang_stride, double *last, const float *y,
+                                             long y_stride, float *peaks, bas_stream_t stream) {
+    int rc = sb_check_layout("bas_stream_batch_epilogue_f32", n_sessions, n_src, B, K, halo, x_stride, ang_stride);
+    if (rc) return rc;
+    const long W = halo + B + K;
+    BAS_REQUIRE(y_stride >= n_sessions * W - K, BAS_E_SHAPE, "bas_stream_batch_epilogue_f32: y_stride %ld < T_in %ld",
+                y_stride, n_sessions * W - K);
+    BAS_REQUIRE(x && elev && azim && last && y && peaks, BAS_E_NULL, "bas_stream_batch_epilogue_f32: null pointer");
+    const int nh = halo / K, nb = (int)(B / K + 1);
+    const long work = (2 * B) / 4 > (long)n_src * halo ? (2 * B) / 4 : (long)n_src * halo;
+    const dim3 grid(sb_blocks_x(n_sessions, work), n_sessions);
+    hipLaunchKernelGGL(bas_stream_batch_epilogue_kernel, grid, dim3(SB_THREADS), 0, bas_stream(stream), x, x_stride, n_src,
+                       halo, B, W, elev, azim, ang_stride, nh, nb, last, y, y_stride,
+                       reinterpret_cast<unsigned int *>(peaks));
+    return bas_check_launch("bas_stream_batch_epilogue_f32");
+}

@@ -1,0 +1,370 @@
+"""Many independent streams advanced together, block by block.
+
+The serving case: G live streams (sessions; one listener per game client, one scene per call), each with its own sources,
+its own carried state and its own running peak, all advancing by one block of B samples at a time.  Slot g behaves
+exactly like its own StreamRenderer(tbl, n_src, K, S) fed the same blocks (sessions with fewer sources pass zero rows),
+but one block of all G sessions is ONE render, laid out as render_batch lays out clips:
+
+  * session g's window [halo | block] (halo = L-1 rounded up to chunks, as in StreamRenderer) starts at g*W of every
+    source row, and one zero chunk follows it: W = halo + B + K, T_in = G*W - K;
+  * the gap is there for the ANGLES, not for the FIR: chunk i's inputs crossfade the IRs of boundaries i and i+1
+    (apply_hrtf.py:431-442), so a window's first boundary and the previous window's last one both reach emitted samples
+    and cannot be one boundary.  The gap chunk's two boundaries are the end of session g and the start of session g+1,
+    and its input is zero.  An emitted sample of window g (position >= halo >= L-1) reads only inputs of window g;
+  * the angle rows hold nh + nb boundaries per session (nh = halo/K, nb = B/K + 1): T_in/K + 1 = G*(nh + nb).
+
+One block: bas_stream_batch_pack_f32 (unless the producer wrote in place through input_view / trajectory_views), then the
+unchanged render (read plans + fused FIR, or the stored-IR path; no peak, no peak rule), then
+bas_stream_batch_epilogue_f32 (per-session running peaks over the emitted samples and the moves of every session's carried
+state).  With graph=True everything after the pack is replayed as one hipGraph, captured under the same rules as
+StreamRenderer's (`prepare(B)` before streaming; else the first block of a size runs plain and the second captures).
+
+The planner (`plan_stream_layout`) is plain numpy and needs no GPU.
+"""
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _hip
+from .batch import MAX_RENDER_SAMPLES, render_batch
+from .apply_hrtf import as_device_table, render_angles_device
+
+MAX_SESSIONS = 65535             # the epilogue and pack kernels have one row of workgroups per session (gridDim.y)
+
+
+def halo_samples(K, L):
+    """StreamRenderer.halo: L - 1 rounded up to whole chunks (0 at L = 1)."""
+    K, L = int(K), int(L)
+    return -(-(L - 1) // K) * K if L > 1 else 0
+
+
+@dataclass(frozen=True)
+class StreamLayout:
+    """One block of G sessions as one render."""
+    n_sessions: int
+    n_src: int
+    K: int
+    L: int
+    B: int
+
+    @property
+    def halo(self):
+        return halo_samples(self.K, self.L)
+
+    @property
+    def nh(self):
+        """Chunk boundaries carried with the halo."""
+        return self.halo // self.K
+
+    @property
+    def nb(self):
+        """Chunk boundaries of one block: t0, t0 + K, .., t0 + B."""
+        return self.B // self.K + 1
+
+    @property
+    def W(self):
+        """Session stride on the time axis: the window [halo | block] and one zero chunk."""
+        return self.halo + self.B + self.K
+
+    @property
+    def T_in(self):
+        return self.n_sessions * self.W - self.K
+
+    @property
+    def T_out(self):
+        return self.T_in + self.L - 1
+
+    @property
+    def n_q(self):
+        """Chunk boundaries per source row: T_in/K + 1 = G (nh + nb)."""
+        return self.n_sessions * (self.nh + self.nb)
+
+    @property
+    def offsets(self):
+        """Session g's window starts at offsets[g] of every source row."""
+        return np.arange(self.n_sessions, dtype=np.int64) * self.W
+
+    @property
+    def block_offsets(self):
+        """Session g's block (and its emitted outputs) start at block_offsets[g]."""
+        return self.offsets + self.halo
+
+    @property
+    def q_offsets(self):
+        """Index of session g's first boundary (the first halo boundary) in the angle rows."""
+        return np.arange(self.n_sessions, dtype=np.int64) * (self.nh + self.nb)
+
+
+def plan_stream_layout(n_sessions, n_src, K, L, B):
+    """The layout of one block of B samples for n_sessions sessions of n_src sources.  Raises ValueError for layouts the
+    batched render does not take (n_src * T_in above batch.MAX_RENDER_SAMPLES, more than MAX_SESSIONS sessions): they
+    are not split."""
+    G, n_src, K, L, B = int(n_sessions), int(n_src), int(K), int(L), int(B)
+    if K <= 0 or L <= 0:
+        raise ValueError("chunksize and the IR length must be positive")
+    if G <= 0 or n_src <= 0:
+        raise ValueError("need at least one session and one source")
+    if G > MAX_SESSIONS:
+        raise ValueError(f"{G} sessions: at most {MAX_SESSIONS} in one renderer")
+    if B <= 0 or B % K:
+        raise ValueError("block length must be a positive multiple of the chunk size")
+    lay = StreamLayout(G, n_src, K, L, B)
+    if n_src * lay.T_in > MAX_RENDER_SAMPLES:
+        raise ValueError(f"{G} sessions x {n_src} sources x blocks of {B}: n_src * T_in = {n_src * lay.T_in} exceeds "
+                         f"{MAX_RENDER_SAMPLES} samples of one render")
+    return lay
+
+
+def _session_runs(idx):
+    """[(g0, g1), ...]: maximal runs of consecutive session indices (one slice op per run: no index tensor, no copy)."""
+    runs = []
+    for g in idx:
+        if runs and runs[-1][1] == g:
+            runs[-1][1] = g + 1
+        else:
+            runs.append([g, g + 1])
+    return [tuple(r) for r in runs]
+
+
+class StreamBatchRenderer:
+    def __init__(self, tbl, n_sessions, n_src, chunksize, subchunksize, graph=True, copy_out=True):
+        """n_sessions independent streams of n_src sources each.  graph, copy_out: as for StreamRenderer."""
+        import torch
+        assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
+        self.G, self.n_src = int(n_sessions), int(n_src)
+        self.K, self.S = int(chunksize), int(subchunksize)
+        plan_stream_layout(self.G, self.n_src, self.K, 1, self.K)          # (session and source counts: ValueError)
+        self.tbl = as_device_table(tbl)
+        self.halo = halo_samples(self.K, self.tbl.L)
+        self.nh = self.halo // self.K
+        dev = self.tbl.device
+        self.graph_enabled, self.copy_out = bool(graph), bool(copy_out)
+        self._lay = None                                  # layout of the current block size
+        self._graph = None
+        self._blocks_in_layout = 0
+        # the angles at the END of every session's last block (finish()), in their own buffer: a change of block size
+        # re-lays the per-block buffers out and cannot lose them
+        self._last = torch.zeros((self.G, 2, self.n_src), dtype=torch.float64, device=dev)
+        self._peaks = torch.zeros((self.G,), dtype=torch.float32, device=dev)
+
+    # ---- buffers ---------------------------------------------------------------------------------------
+    def _x3(self, x=None, lay=None):
+        """[n_src, G, W] view of an input buffer: window g of source s is [s, g, :halo + B], its gap [s, g, halo + B:]."""
+        x, lay = (self._x, self._lay) if x is None else (x, lay)
+        return x[:, :lay.n_sessions * lay.W].view(lay.n_src, lay.n_sessions, lay.W)
+
+    def _a3(self, a, lay=None):
+        """[n_src, G, nh + nb] view of an angle buffer."""
+        lay = self._lay if lay is None else lay
+        return a.view(lay.n_src, lay.n_sessions, lay.nh + lay.nb)
+
+    def _layout(self, B):
+        """Per-block buffers for blocks of B samples (kept until another size arrives).  A change of size moves every
+        session's halo inputs and halo angles to their new offsets; the gaps of the new buffers are zero."""
+        import torch
+        if self._lay is not None and self._lay.B == B:
+            return
+        lay = plan_stream_layout(self.G, self.n_src, self.K, self.tbl.L, B)
+        dev, n, halo, nh = self.tbl.device, self.n_src, self.halo, self.nh
+        x = torch.zeros((n, (self.G * lay.W + 3) // 4 * 4), dtype=torch.float32, device=dev)
+        elev = torch.zeros((n, lay.n_q), dtype=torch.float64, device=dev)
+        azim = torch.zeros((n, lay.n_q), dtype=torch.float64, device=dev)
+        if self._lay is not None:                         # carry every session's halo into the new layout
+            self._x3(x, lay)[:, :, :halo] = self._x3()[:, :, :halo]
+            for new, old in ((elev, self._elev), (azim, self._azim)):
+                self._a3(new, lay)[:, :, :nh] = self._a3(old)[:, :, :nh]
+        self._lay, self._x, self._elev, self._azim = lay, x, elev, azim
+        self._graph, self._blocks_in_layout = None, 0
+        self._y = torch.empty((2, lay.T_out), dtype=torch.float32, device=dev)
+        self._blk = None                                  # staging buffers of the pack (allocated on first use)
+        self._ang_in = None
+        lib = _hip.lib()
+        with _hip.on_device(dev):
+            wb = max(lib.bas_render_workspace_bytes(n, lay.T_in, self.K, self.S, self.tbl.L),
+                     lib.bas_render_fused_workspace_bytes(n, lay.T_in, self.K, self.S, self.tbl.L))
+        self._ws = _hip.new_workspace(wb, dev)
+        self._ws_plans = torch.empty((lib.bas_interp2d_workspace_bytes(n * lay.n_q),), dtype=torch.uint8, device=dev)
+        self._idx = torch.empty((n * lay.n_q, 4), dtype=torch.int32, device=dev)
+        self._w = torch.empty((n * lay.n_q, 3), dtype=torch.float64, device=dev)
+
+    def layout(self, B):
+        """The StreamLayout of blocks of B samples (no device work)."""
+        return plan_stream_layout(self.G, self.n_src, self.K, self.tbl.L, B)
+
+    def input_view(self, B):
+        """Device view [G, n_src, B] (strided) of the renderer's own input buffer for blocks of B samples.  A producer that
+        writes the next block of every session here and passes this view to process() saves the pack launch (when it
+        also writes the angles through trajectory_views).  Valid until the block size changes."""
+        import torch
+        self._layout(B)
+        lay = self._lay
+        return torch.as_strided(self._x, (self.G, self.n_src, B), (lay.W, self._x.stride(0), 1), self.halo)
+
+    def trajectory_views(self, B):
+        """Device views (elev, azim), float64 [G, n_src, B/K + 1] (strided), of the renderer's own angle buffers for
+        blocks of B samples: the slots behind every session's carried halo boundaries."""
+        import torch
+        self._layout(B)
+        lay = self._lay
+        shape, strides = (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1)
+        return (torch.as_strided(self._elev, shape, strides, lay.nh), torch.as_strided(self._azim, shape, strides, lay.nh))
+
+    def _emitted(self):
+        """[G, B, 2] view of the render output: the samples this block completes for every session."""
+        import torch
+        lay = self._lay
+        return torch.as_strided(self._y, (self.G, lay.B, 2), (lay.W, 1, self._y.stride(0)), self.halo)
+
+    # ---- one block -------------------------------------------------------------------------------------
+    def _block_body(self):
+        """The stream-ordered work of one block after the pack (captured into the hipGraph)."""
+        lay, dev = self._lay, self.tbl.device
+        render_angles_device(self._x[:, :lay.T_in], self.K, self.S, self.tbl, self._elev, self._azim, normalize="none",
+                             out=self._y, ws=self._ws, ws_plans=self._ws_plans, params=(self._idx, self._w),
+                             want_peak=False)                 # (the epilogue takes each session's peak of the EMITTED samples)
+        with _hip.on_device(dev):
+            _hip.call("bas_stream_batch_epilogue_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src, self.halo,
+                      lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0),
+                      _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peaks),
+                      _hip.current_stream(dev))
+
+    def _capture(self):
+        import torch
+        g = torch.cuda.CUDAGraph()
+        # thread_local: allocations or copies of OTHER threads (a producer filling input_view()) do not invalidate
+        # the capture; the capture's own allocations come from the graph's private pool
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._block_body()
+        self._graph = g
+
+    def prepare(self, B):
+        """Lay out the buffers for blocks of B samples, run one block on silence as a warm-up and, with graph=True,
+        capture the block's hipGraph - before streaming starts, as StreamRenderer.prepare.  Every session's carried state
+        (input halo, halo angles, end angles, running peak) is left exactly as it was.  The warm-up overwrites the output
+        buffer: consume a view handed out with copy_out=False first."""
+        import torch
+        self._layout(B)
+        halo = self.halo
+        keep = (self._x.clone(), self._elev.clone(), self._azim.clone(), self._last.clone(), self._peaks.clone())
+        self._x3()[:, :, halo:halo + B].zero_()
+        self._block_body()                                # plain launches: warm-up
+        if self.graph_enabled and self._graph is None:
+            self._capture()                               # (records the launches, does not execute them)
+        torch.cuda.synchronize(self.tbl.device)
+        for buf, saved in zip((self._x, self._elev, self._azim, self._last, self._peaks), keep):
+            buf.copy_(saved)
+        self._blocks_in_layout = max(self._blocks_in_layout, 1)
+
+    def process(self, blocks, elev, azim):
+        """blocks: [G, n_src, B] (B a multiple of the chunk size); elev/azim: float64 [G, n_src, B/K + 1], every session's
+        trajectory at t0, t0 + K, .., t0 + B of this block (radians; numpy arrays or device tensors).  Returns the B stereo
+        samples this block completes for every session, a device tensor [G, B, 2], un-normalised."""
+        import torch
+        blk = torch.as_tensor(blocks)
+        if blk.dim() != 3 or tuple(blk.shape[:2]) != (self.G, self.n_src):
+            raise ValueError(f"blocks must be [{self.G}, {self.n_src}, B]")
+        B = int(blk.shape[2])
+        if B <= 0 or B % self.K:
+            raise ValueError("block length must be a positive multiple of the chunk size")
+        self._layout(B)
+        lay, dev = self._lay, self.tbl.device
+        x_view = self.input_view(B)
+        views = self.trajectory_views(B)
+        angs = [torch.as_tensor(a) for a in (elev, azim)]
+        for t in angs:
+            if tuple(t.shape) != (self.G, self.n_src, lay.nb):
+                raise ValueError(f"elev/azim must have shape ({self.G}, {self.n_src}, {lay.nb})")
+
+        def same(t, view, dtype):
+            return t.is_cuda and t.dtype == dtype and t.data_ptr() == view.data_ptr() and t.stride() == view.stride()
+        x_in_place = same(blk, x_view, torch.float32)
+        a_in_place = all(same(t, v, torch.float64) for t, v in zip(angs, views))
+        if x_in_place or a_in_place:                      # the producer wrote part of the block in place: copy the rest
+            if not x_in_place:
+                x_view.copy_(blk)
+            if not a_in_place:
+                for t, v in zip(angs, views):
+                    v.copy_(t)
+        else:                                             # one pack launch from dense device arrays
+            if not (blk.is_cuda and blk.dtype == torch.float32 and blk.is_contiguous() and blk.device == dev):
+                if self._blk is None:
+                    self._blk = torch.empty((self.G, self.n_src, B), dtype=torch.float32, device=dev)
+                self._blk.copy_(blk)                      # (H2D for host arrays)
+                blk = self._blk
+            for k, t in enumerate(angs):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev):
+                    if self._ang_in is None:
+                        self._ang_in = torch.empty((2, self.G, self.n_src, lay.nb), dtype=torch.float64, device=dev)
+                    self._ang_in[k].copy_(t)              # (float64 kept exactly)
+                    angs[k] = self._ang_in[k]
+            with _hip.on_device(dev):
+                _hip.call("bas_stream_batch_pack_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]), self.G,
+                          self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev),
+                          _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
+        if self._graph is not None:
+            self._graph.replay()
+        elif not self.graph_enabled or self._blocks_in_layout == 0:
+            self._block_body()                            # no prepare(): the first block of a size runs plain (warm-up)
+        else:
+            self._capture()                               # ... and the second one captures (a device synchronisation:
+            self._graph.replay()                          # real-time callers use prepare() instead)
+        self._blocks_in_layout += 1
+        out = self._emitted()
+        return out.clone() if self.copy_out else out
+
+    # ---- per-session state -----------------------------------------------------------------------------
+    @property
+    def peaks(self):
+        """float32 [G] (host): every session's max |sample| emitted since its start or last reset / finish."""
+        return self._peaks.cpu().numpy()
+
+    @property
+    def peaks_device(self):
+        """The running peaks as the renderer's own device tensor (no read-back; updated in place by every block)."""
+        return self._peaks
+
+    def _sessions(self, sessions):
+        idx = sorted({int(g) for g in np.asarray(sessions, dtype=np.int64).reshape(-1)})
+        if idx and not (0 <= idx[0] and idx[-1] < self.G):
+            raise ValueError(f"session index out of range [0, {self.G})")
+        if len(idx) != np.asarray(sessions).size:
+            raise ValueError("sessions must not repeat")
+        return idx
+
+    def reset(self, sessions):
+        """Drop the streams of these slots without a tail: their halo inputs, halo angles, end angles and peaks are
+        zeroed on the device (slice ops on the current stream, no synchronisation).  Their next block starts fresh."""
+        for g0, g1 in _session_runs(self._sessions(sessions)):
+            if self._lay is not None:
+                self._x3()[:, g0:g1, :self.halo].zero_()
+                self._a3(self._elev)[:, g0:g1, :self.nh].zero_()
+                self._a3(self._azim)[:, g0:g1, :self.nh].zero_()
+            self._last[g0:g1].zero_()
+            self._peaks[g0:g1].zero_()
+
+    def finish(self, sessions, return_peaks=False):
+        """Emit the last L-1 samples of these sessions' streams (the tail the reference appends, apply_hrtf.py:410), as
+        StreamRenderer.finish: each session's [halo | K zeros] window with its halo angles, then its end angle twice,
+        rendered for the listed sessions only, in one batched render (render_batch: the gap behind each window is at least
+        L-1 samples, so a tail reads no other session's inputs).  The tail's samples count into the sessions' peaks; then
+        the slots restart as fresh streams (reset).  Returns a device tensor [len(sessions), L-1, 2] in ascending session
+        order, and with return_peaks=True also float32 [len(sessions)] (host): the finished streams' final peaks."""
+        import torch
+        idx = self._sessions(sessions)
+        n, L, K, halo, nh = len(idx), self.tbl.L, self.K, self.halo, self.nh
+        dev = self.tbl.device
+        tails = torch.zeros((n, L - 1, 2), dtype=torch.float32, device=dev)
+        if n and L > 1 and self._lay is not None:         # (no block yet: the halo holds silence, the tail is zeros)
+            sel = torch.tensor(idx, dtype=torch.int64, device=dev)
+            sig = torch.zeros((n, self.n_src, halo + K), dtype=torch.float32, device=dev)
+            sig[:, :, :halo] = self._x3()[:, :, :halo].index_select(1, sel).transpose(0, 1)
+            ang = []
+            for k, a in enumerate((self._elev, self._azim)):
+                end = self._last.index_select(0, sel)[:, k, :, None]                     # [n, n_src, 1]
+                ang.append(torch.cat([self._a3(a)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2))
+            out, _, _ = render_batch(sig, K, self.S, ang[0], ang[1], self.tbl, normalize="none")
+            tails.copy_(out[:, halo:halo + L - 1])
+            self._peaks.index_copy_(0, sel, torch.maximum(self._peaks.index_select(0, sel), tails.abs().amax(dim=(1, 2))))
+        final = self._peaks[idx].cpu().numpy() if return_peaks else None
+        self.reset(idx)
+        return (tails, final) if return_peaks else tails

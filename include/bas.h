@@ -348,6 +348,31 @@ int bas_batch_pack_f32(const float *sig, int n_items, int n_src, long N, const l
 int bas_batch_finish_f32(float *y, long y_stride, int n_items, const long *offsets, const long *out_lengths,
                          long out_len_max, int normalize, float *out, float *peaks, bas_stream_t stream);
 
+/* ---- batched streams (no reference counterpart) ----------------------------------------------------
+ * G independent streams (sessions) of n_src sources advance by one block of B samples in ONE render.  Session g's window
+ * [halo | block] (halo = L-1 rounded up to chunks, as for bas_stream_epilogue_f32) starts at g W of every source row,
+ * W = halo + B + K: one zero chunk follows each window, T_in = G W - K.  The chunk crossfade (apply_hrtf.py:431-442)
+ * mixes the IRs of a chunk's two boundaries, so a window's first boundary cannot be the previous window's last one: the
+ * gap chunk's boundaries are both, and its input is zero.  The FIR needs no gap (an emitted sample, at >= halo >= L-1
+ * into its window, reads only inputs of that window: apply_hrtf.py:444-453).  Angle rows: nh + nb boundaries per session
+ * (nh = halo / K, nb = B / K + 1), session g's from g (nh + nb); T_in / K + 1 = G (nh + nb).  K divides B and halo;
+ * x_stride >= T_in, ang_stride >= G (nh + nb); G <= 65535 (one row of workgroups per session).
+ *
+ * bas_stream_batch_pack_f32: blocks [G][n_src][B] float32 -> x[s][g W + halo + j]; elev/azim [G][n_src][nb] float64 (the
+ *   block's boundaries t0, t0 + K, .., t0 + B: :429, :435) -> elev_out/azim_out[s][g (nh + nb) + nh + c].  The halo
+ *   columns, the halo angles and the gaps are not written.  One launch; 16-byte accesses where the rows are aligned.
+ * bas_stream_batch_epilogue_f32: after the window render into y [2] rows of y_stride >= T_in floats, per session g what
+ *   bas_stream_epilogue_f32 does for one stream, on session g's offset pointers: peaks[g] = max(peaks[g], max|y[e][g W +
+ *   halo .. g W + halo + B)|) over both ears (:462 over the emitted samples; atomicMax on the bits of non-negative floats:
+ *   exact, order-free); the input halo, the halo's boundaries and the angles at the block's end (last [G][2][n_src]) move
+ *   as for one stream.  One launch. */
+int bas_stream_batch_pack_f32(const float *blocks, const double *elev, const double *azim, int n_sessions, int n_src,
+                              long B, int K, int halo, float *x, long x_stride, double *elev_out, double *azim_out,
+                              long ang_stride, bas_stream_t stream);
+int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
+                                  double *elev, double *azim, long ang_stride, double *last, const float *y,
+                                  long y_stride, float *peaks, bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's
