@@ -70,6 +70,11 @@ SIGNATURES = {
                                       _c_void_p]),
     "bas_stream_batch_pack_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_long, _c_int, _c_int,
                                            _c_void_p, _c_long, _c_void_p, _c_void_p, _c_long, _c_void_p]),
+    "bas_stream_batch_pack_head_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_long,
+                                                _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p, _c_long,
+                                                _c_void_p]),
+    "bas_head_relative_f64": (_c_int, [_c_void_p, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_int, _c_int,
+                                       _c_int, _c_void_p, _c_void_p, _c_long, _c_long, _c_void_p]),
     "bas_stream_batch_epilogue_f32": (_c_int, [_c_void_p, _c_long, _c_int, _c_int, _c_int, _c_long, _c_int, _c_void_p,
                                                _c_void_p, _c_long, _c_void_p, _c_void_p, _c_long, _c_void_p, _c_void_p]),
     "bas_resample_up_f64": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),

@@ -5,9 +5,12 @@
 // boundaries per session, session g's from g·(nh + nb).  Two entry points around the unchanged render:
 //   bas_stream_batch_pack_f32     - scatter [G][n_src][B] blocks and [G][n_src][nb] angles into the windows' block columns
 //                                   and angle slots (never the halo columns, the halo angles or the gaps), one launch;
+//   bas_stream_batch_pack_head_f32 - the same scatter with world-frame angles and [G][nb][4] head orientations: the angle
+//                                   slots get the head-relative angles (bas_head.h), still one launch;
 //   bas_stream_batch_epilogue_f32 - per session, what bas_stream_epilogue_f32 does for one stream: the running peak over
 //                                   the emitted samples and the moves of the carried state, one launch.
 #include "bas_internal.h"
+#include "bas_head.h"
 
 #define SB_THREADS 256
 
@@ -15,11 +18,13 @@ __device__ __forceinline__ bool sb_aligned16(const void *p) { return (reinterpre
 
 // One row of workgroups per session (blockIdx.y = g).  Items of a session: n_src rows of ceil(B/4) quads, then n_src rows
 // of nb (elev, azim) pairs.  A quad moves as one 16-byte load and store when both rows are 16-byte aligned and B % 4 == 0
-// (every quad of the row then is), else as up to 4 scalars (still coalesced across a wave).
+// (every quad of the row then is), else as up to 4 scalars (still coalesced across a wave).  HEAD: the angles are world-frame
+// and head [G][nb][4] holds session g's orientation at each boundary; the slots get bas_head_relative's angles.
+template <bool HEAD>
 __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
     const float *__restrict__ blocks, const double *__restrict__ elev, const double *__restrict__ azim, int n_src,
     long B, long W, int halo, int nh, int nb, float *__restrict__ x, long x_stride, double *__restrict__ elev_out,
-    double *__restrict__ azim_out, long ang_stride) {
+    double *__restrict__ azim_out, long ang_stride, const double *__restrict__ head) {
     const int g = blockIdx.y;
     const long nq = (B + 3) >> 2;
     const long n_x = (long)n_src * nq, n_items = n_x + (long)n_src * nb;
@@ -41,8 +46,16 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
             const int c = (int)(r - (long)s * nb);
             const long from = ((long)g * n_src + s) * nb + c;
             const long to = (long)s * ang_stride + (long)g * (nh + nb) + nh + c;
-            elev_out[to] = elev[from];
-            azim_out[to] = azim[from];
+            if constexpr (HEAD) {
+                const double *q = head + ((long)g * nb + c) * 4;
+                double el_h, az_h;
+                bas_head_relative(q[0], q[1], q[2], q[3], elev[from], azim[from], el_h, az_h);
+                elev_out[to] = el_h;
+                azim_out[to] = az_h;
+            } else {
+                elev_out[to] = elev[from];
+                azim_out[to] = azim[from];
+            }
         }
     }
 }
@@ -112,9 +125,25 @@ extern "C" int bas_stream_batch_pack_f32(const float *blocks, const double *elev
     const long W = halo + B + K;
     const int nh = halo / K, nb = (int)(B / K + 1);
     const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
-    hipLaunchKernelGGL(bas_stream_batch_pack_kernel, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev, azim,
-                       n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride);
+    hipLaunchKernelGGL(bas_stream_batch_pack_kernel<false>, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev,
+                       azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, nullptr);
     return bas_check_launch("bas_stream_batch_pack_f32");
+}
+
+extern "C" int bas_stream_batch_pack_head_f32(const float *blocks, const double *elev, const double *azim,
+                                              const double *head, int n_sessions, int n_src, long B, int K, int halo,
+                                              float *x, long x_stride, double *elev_out, double *azim_out, long ang_stride,
+                                              bas_stream_t stream) {
+    int rc = sb_check_layout("bas_stream_batch_pack_head_f32", n_sessions, n_src, B, K, halo, x_stride, ang_stride);
+    if (rc) return rc;
+    BAS_REQUIRE(blocks && elev && azim && head && x && elev_out && azim_out, BAS_E_NULL,
+                "bas_stream_batch_pack_head_f32: null pointer");
+    const long W = halo + B + K;
+    const int nh = halo / K, nb = (int)(B / K + 1);
+    const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
+    hipLaunchKernelGGL(bas_stream_batch_pack_kernel<true>, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev,
+                       azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head);
+    return bas_check_launch("bas_stream_batch_pack_head_f32");
 }
 
 extern "C" int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,

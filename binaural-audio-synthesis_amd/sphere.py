@@ -287,3 +287,140 @@ def interpolation_params_device(elev, azim, out=None, branch="f64"):
         _hip.call("bas_traj_params_branch_f64", _hip.ptr(e), _hip.ptr(z), n, ring_elev, ring_start, ring_count,
                   _hip.ptr(nodes), _hip.ptr(idx), _hip.ptr(w), BRANCHES[branch], _hip.current_stream(dev))
     return idx.reshape(tuple(elev.shape) + (4,)), w.reshape(tuple(elev.shape) + (3,))
+
+
+# ---- head tracking --------------------------------------------------------------------------------
+def _head_shapes(ang_shape, head_shape):
+    """ValueError unless angles are (..., n_src, nb) and head (..., nb, 4) with the same leading axes."""
+    ang_shape, head_shape = tuple(ang_shape), tuple(head_shape)
+    if len(ang_shape) < 2:
+        raise ValueError(f"angles must have shape (..., n_src, nb), not {ang_shape}")
+    if head_shape != ang_shape[:-2] + (ang_shape[-1], 4):
+        raise ValueError(f"head must have shape {ang_shape[:-2] + (ang_shape[-1], 4)} for angles of shape {ang_shape}")
+
+
+def check_head(head):
+    """ValueError for non-finite head orientations and zero-norm quaternions (float64 numpy array [..., 4]); the norm is
+    taken as the kernels take it, so one that underflows to zero or overflows counts as zero or non-finite."""
+    q = np.asarray(head, dtype=np.float64)
+    if not np.isfinite(q).all():
+        raise ValueError("head orientations must be finite")
+    with np.errstate(over="ignore", under="ignore"):
+        w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+        n = np.sqrt(w * w + x * x + y * y + z * z)
+    if not (np.isfinite(n) & (n > 0)).all():
+        raise ValueError("head orientations must be quaternions of non-zero, finite norm")
+
+
+def head_relative_angles(elev, azim, head):
+    """The listener's view of world-frame directions (float64 numpy; the definition the device kernels are held to).
+
+    elev/azim: world-frame angles (..., n_src, nb) in radians; head: (..., nb, 4) quaternions (w, x, y, z) of the head
+    orientation at each of the nb boundaries, shared by the n_src sources (rotating head into world coordinates,
+    d_world = R(q) d_head; any non-zero norm).  Directions are d = (-sin az cos el, cos az cos el, sin el) (the reference's
+    sphere.py:51-56: +y front, +z up, +x right).  q is negated first when w < 0.  A pure yaw (x == y == 0 after that)
+    keeps the elevation bit for bit and gives az - 2 atan2(z, w) (az itself when z == 0); otherwise el_h = atan2(z_h,
+    hypot(x_h, y_h)), az_h = atan2(-x_h, y_h) for d_head = R(q)^T d_world, not wrapped.  Returns (el_h, az_h) float64
+    arrays of the angles' shape.  ValueError for non-finite angles or orientations and zero-norm quaternions."""
+    e = np.asarray(elev, dtype=np.float64)
+    a = np.asarray(azim, dtype=np.float64)
+    q = np.asarray(head, dtype=np.float64)
+    if a.shape != e.shape:
+        raise ValueError("elev and azim must have the same shape")
+    _head_shapes(e.shape, q.shape)
+    if not (np.isfinite(e).all() and np.isfinite(a).all()):
+        raise ValueError("angles must be finite")
+    check_head(q)
+    q = np.expand_dims(q, -3)                                   # (..., 1, nb, 4): one orientation for all sources
+    q = np.where(q[..., :1] < 0, -q, q)
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    yaw = (x == 0) & (y == 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        az_yaw = np.where(z == 0, a, a - 2.0 * np.arctan2(z, w))
+        n = np.sqrt(w * w + x * x + y * y + z * z)
+        w, x, y, z = w / n, x / n, y / n, z / n
+        se, ce, sa, ca = np.sin(e), np.cos(e), np.sin(a), np.cos(a)
+        dx, dy, dz = -sa * ce, ca * ce, se
+        xh = (1.0 - 2.0 * (y * y + z * z)) * dx + 2.0 * (x * y + w * z) * dy + 2.0 * (x * z - w * y) * dz
+        yh = 2.0 * (x * y - w * z) * dx + (1.0 - 2.0 * (x * x + z * z)) * dy + 2.0 * (y * z + w * x) * dz
+        zh = 2.0 * (x * z + w * y) * dx + 2.0 * (y * z - w * x) * dy + (1.0 - 2.0 * (x * x + y * y)) * dz
+        el_g = np.arctan2(zh, np.hypot(xh, yh))
+        az_g = np.arctan2(-xh, yh)
+    return np.where(yaw, e, el_g), np.where(yaw, az_yaw, az_g)
+
+
+def head_to_device(head, shape, dev, buf=None):
+    """A head argument of the renderers as a float64 tensor on `dev`: a device tensor on `dev` is checked for shape and
+    dtype only and used as it is; anything else (numpy arrays, host tensors, another device) is validated on the host
+    (check_head) and copied into `buf` (allocated when None).  Returns (tensor, buf)."""
+    import torch
+    if isinstance(head, torch.Tensor) and head.is_cuda:
+        if tuple(head.shape) != tuple(shape) or head.dtype != torch.float64:
+            raise ValueError(f"head must be a float64 tensor of shape {tuple(shape)}")
+        if head.device == dev:
+            return head, buf
+        src = head
+    else:
+        arr = head.numpy() if isinstance(head, torch.Tensor) else head
+        arr = np.asarray(arr, dtype=np.float64)
+        if arr.shape != tuple(shape):
+            raise ValueError(f"head must have shape {tuple(shape)}")
+        check_head(arr)
+        src = torch.from_numpy(np.ascontiguousarray(arr))
+    if buf is None or tuple(buf.shape) != tuple(shape):
+        buf = torch.empty(tuple(shape), dtype=torch.float64, device=dev)
+    buf.copy_(src)
+    return buf, buf
+
+
+def head_relative_angles_device(elev, azim, head, out=None):
+    """head_relative_angles on the GPU (bas_head_relative_f64, one launch): for offline callers that then render the
+    angles themselves (render_angles_device, render_batch).  elev/azim: world-frame angles [G, n_src, nb] or [n_src, nb];
+    head [G, nb, 4] or [nb, 4].  Device tensors must be float64 and are checked for shape and dtype only (a non-finite
+    orientation gives non-finite angles, a zero quaternion the identity); numpy arrays and host tensors are validated on
+    the host as head_relative_angles validates them, then uploaded.  out = (elev_out, azim_out): float64 device tensors of
+    the angles' shape and equal strides, unit stride on the last axis (strided views such as a renderer's
+    trajectory_views serve), or elev and azim themselves (in place).  Returns (elev_h, azim_h) device tensors."""
+    import torch
+    from . import _hip
+    tensors = [t for t in (elev, azim, head) + tuple(out or ()) if isinstance(t, torch.Tensor) and t.is_cuda]
+    dev = tensors[0].device if tensors else _hip.require_gpu()
+    ang = []
+    for t in (elev, azim):
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            if t.dtype != torch.float64:
+                raise ValueError("elev/azim device tensors must be float64")
+            ang.append(t if t.device == dev else t.to(dev))
+        else:
+            arr = np.asarray(t.numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
+            if not np.isfinite(arr).all():
+                raise ValueError("angles must be finite")
+            ang.append(torch.from_numpy(np.ascontiguousarray(arr)).to(dev))
+    e, a = ang
+    if tuple(a.shape) != tuple(e.shape) or e.dim() not in (2, 3):
+        raise ValueError("elev and azim must have the same shape, [G, n_src, nb] or [n_src, nb]")
+    shape = tuple(e.shape)
+    _head_shapes(shape, tuple(head.shape) if hasattr(head, "shape") else np.shape(head))
+    q, _ = head_to_device(head, shape[:-2] + (shape[-1], 4), dev)
+    if out is None:
+        out = (torch.empty(shape, dtype=torch.float64, device=dev), torch.empty(shape, dtype=torch.float64, device=dev))
+    eo, ao = out
+    for t in (eo, ao):
+        if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_cuda or t.device != dev:
+            raise ValueError(f"out must be two float64 tensors of shape {shape} on {dev}")
+    if eo.stride() != ao.stride() or eo.stride(-1) != 1:
+        raise ValueError("out tensors must have equal strides and unit stride on the last axis")
+    if e.stride() != a.stride() or e.stride(-1) != 1:
+        e, a = e.contiguous(), a.contiguous()
+    if q.stride(-1) != 1 or q.stride(-2) < 4:
+        q = q.contiguous()
+    if len(shape) == 2:
+        e3, a3, q3, eo3, ao3 = e[None], a[None], q[None], eo[None], ao[None]
+    else:
+        e3, a3, q3, eo3, ao3 = e, a, q, eo, ao
+    G, n_src, nb = e3.shape
+    with _hip.on_device(dev):
+        _hip.call("bas_head_relative_f64", _hip.ptr(e3), _hip.ptr(a3), e3.stride(0), e3.stride(1), _hip.ptr(q3),
+                  q3.stride(0), q3.stride(1), G, n_src, nb, _hip.ptr(eo3), _hip.ptr(ao3), eo3.stride(0), eo3.stride(1),
+                  _hip.current_stream(dev))
+    return eo, ao

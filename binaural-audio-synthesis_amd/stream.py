@@ -30,8 +30,25 @@ is its offset inside its chunk, apply_hrtf.py:442), and their work is quantised 
 tiles of 2048 samples anyway - a 512-sample block with a 512-sample halo is ONE tile per
 source, exactly as it would be with a 128-sample halo.
 """
-from . import _hip
+from . import _hip, sphere
 from .apply_hrtf import as_device_table, plan_angles_device, render_angles_device
+
+
+def rotate_into_views(elev, azim, head, views):
+    """World-frame angles of one block (host arrays or device tensors) and a head already on the device -> head-relative
+    angles in a renderer's trajectory views, one bas_head_relative_f64 launch.  float64 tensors on the views' device are
+    read where they are (in place when they are the views); anything else is first copied into the views, as the
+    headless path copies it."""
+    import torch
+    dev = views[0].device
+    src = []
+    for t, v in zip((elev, azim), views):
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.device == dev:
+            src.append(t)
+        else:
+            v.copy_(torch.as_tensor(t))                   # (H2D for host arrays; float64 kept exactly)
+            src.append(v)
+    sphere.head_relative_angles_device(src[0], src[1], head, out=views)
 
 
 def tile_filling_block(about, chunksize, ir_length, tile=8192):
@@ -78,6 +95,7 @@ class StreamRenderer:
         self.samples_in = 0
         self._finished = False
         self._events = None                               # (begin, end) raw hipEvent_t around the FIR kernel of plain-launch blocks (bench.py)
+        self._head_buf = None                             # device staging of host head orientations (process(head=...))
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _reserve(self, B):
@@ -206,9 +224,14 @@ class StreamRenderer:
         self._peak_dev.copy_(keep[4])
         self._blocks_in_layout = max(self._blocks_in_layout, 1)
 
-    def process(self, block, elev, azim):
+    def process(self, block, elev, azim, head=None):
         """block: [n_src, B] (B a multiple of the chunk size); elev/azim: float64 [n_src, B/K + 1],
         the trajectory at t = t0, t0+K, .., t0+B of this block (radians; numpy arrays or device tensors).
+        head: None (elev/azim are head-relative), or the listener's head orientation at the same boundaries, quaternions
+        (w, x, y, z) [B/K + 1, 4]: elev/azim are then world-frame, and one launch of
+        bas_head_relative_f64 writes the head-relative angles into trajectory_views(B) (in place when elev/azim are
+        those views).  A host head is validated (sphere.check_head: ValueError) and staged in a persistent device
+        buffer; a device tensor is checked for shape and dtype only.
         Returns the B stereo samples this block completes as a device tensor (B, 2), un-normalised."""
         import torch
         assert not self._finished, "stream already finished"
@@ -218,12 +241,20 @@ class StreamRenderer:
         assert B % self.K == 0 and B > 0, 'block length must be a positive multiple of the chunk size'
         self._layout(B)
         nb = self._nb
-        for src, dst in ((elev, self._elev_all[:, self.nh:]), (azim, self._azim_all[:, self.nh:])):
-            t = torch.as_tensor(src)
-            if tuple(t.shape) != (self.n_src, nb):
-                raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
-            if not (t.is_cuda and t.data_ptr() == dst.data_ptr() and t.dtype == torch.float64 and t.stride() == dst.stride()):
-                dst.copy_(t)                              # (H2D for host arrays; float64 kept exactly)
+        if head is None:
+            for src, dst in ((elev, self._elev_all[:, self.nh:]), (azim, self._azim_all[:, self.nh:])):
+                t = torch.as_tensor(src)
+                if tuple(t.shape) != (self.n_src, nb):
+                    raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
+                if not (t.is_cuda and t.data_ptr() == dst.data_ptr() and t.dtype == torch.float64 and t.stride() == dst.stride()):
+                    dst.copy_(t)                          # (H2D for host arrays; float64 kept exactly)
+        else:
+            views = (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:])
+            for t in (elev, azim):
+                if tuple(torch.as_tensor(t).shape) != (self.n_src, nb):
+                    raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
+            q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
+            rotate_into_views(elev, azim, q, views)
         x_dst = self._xbuf[:, self.halo:self.halo + B]
         in_place = blk.is_cuda and blk.dtype == torch.float32 and blk.stride() == x_dst.stride() and \
             blk.data_ptr() == x_dst.data_ptr()

@@ -25,9 +25,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _hip
+from . import _hip, sphere
 from .batch import MAX_RENDER_SAMPLES, render_batch
 from .apply_hrtf import as_device_table, render_angles_device
+from .stream import rotate_into_views
 
 MAX_SESSIONS = 65535             # the epilogue and pack kernels have one row of workgroups per session (gridDim.y)
 
@@ -178,6 +179,7 @@ class StreamBatchRenderer:
         self._y = torch.empty((2, lay.T_out), dtype=torch.float32, device=dev)
         self._blk = None                                  # staging buffers of the pack (allocated on first use)
         self._ang_in = None
+        self._head_in = None
         lib = _hip.lib()
         with _hip.on_device(dev):
             wb = max(lib.bas_render_workspace_bytes(n, lay.T_in, self.K, self.S, self.tbl.L),
@@ -255,10 +257,16 @@ class StreamBatchRenderer:
             buf.copy_(saved)
         self._blocks_in_layout = max(self._blocks_in_layout, 1)
 
-    def process(self, blocks, elev, azim):
+    def process(self, blocks, elev, azim, head=None):
         """blocks: [G, n_src, B] (B a multiple of the chunk size); elev/azim: float64 [G, n_src, B/K + 1], every session's
-        trajectory at t0, t0 + K, .., t0 + B of this block (radians; numpy arrays or device tensors).  Returns the B stereo
-        samples this block completes for every session, a device tensor [G, B, 2], un-normalised."""
+        trajectory at t0, t0 + K, .., t0 + B of this block (radians; numpy arrays or device tensors).  head: None
+        (elev/azim are head-relative), or every session's listener orientation at the same boundaries, quaternions
+        (w, x, y, z) [G, B/K + 1, 4]: elev/azim are then world-frame.  Dense inputs take the rotation in
+        the pack launch (bas_stream_batch_pack_head_f32: no launch more); when the producer wrote in place through
+        input_view / trajectory_views, one bas_head_relative_f64 launch rotates the angle views in place.  A host head is
+        validated (sphere.check_head: ValueError) and staged in a persistent device buffer; a device tensor is checked for
+        shape and dtype only.  Returns the B stereo samples this block completes for every session, a device tensor
+        [G, B, 2], un-normalised."""
         import torch
         blk = torch.as_tensor(blocks)
         if blk.dim() != 3 or tuple(blk.shape[:2]) != (self.G, self.n_src):
@@ -279,10 +287,16 @@ class StreamBatchRenderer:
             return t.is_cuda and t.dtype == dtype and t.data_ptr() == view.data_ptr() and t.stride() == view.stride()
         x_in_place = same(blk, x_view, torch.float32)
         a_in_place = all(same(t, v, torch.float64) for t, v in zip(angs, views))
+        if head is not None:                              # (the renderer's own head buffer is dense: the fused pack reads it)
+            q, self._head_in = sphere.head_to_device(head, (self.G, lay.nb, 4), dev, self._head_in)
+            if not (x_in_place or a_in_place):
+                q = q.contiguous()
         if x_in_place or a_in_place:                      # the producer wrote part of the block in place: copy the rest
             if not x_in_place:
                 x_view.copy_(blk)
-            if not a_in_place:
+            if head is not None:                          # world-frame angles -> head-relative ones in the views
+                rotate_into_views(angs[0], angs[1], q, views)
+            elif not a_in_place:
                 for t, v in zip(angs, views):
                     v.copy_(t)
         else:                                             # one pack launch from dense device arrays
@@ -298,9 +312,14 @@ class StreamBatchRenderer:
                     self._ang_in[k].copy_(t)              # (float64 kept exactly)
                     angs[k] = self._ang_in[k]
             with _hip.on_device(dev):
-                _hip.call("bas_stream_batch_pack_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]), self.G,
-                          self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev),
-                          _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
+                if head is None:
+                    _hip.call("bas_stream_batch_pack_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]), self.G,
+                              self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev),
+                              _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
+                else:
+                    _hip.call("bas_stream_batch_pack_head_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
+                              _hip.ptr(q), self.G, self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0),
+                              _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
         if self._graph is not None:
             self._graph.replay()
         elif not self.graph_enabled or self._blocks_in_layout == 0:

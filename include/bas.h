@@ -365,13 +365,37 @@ int bas_batch_finish_f32(float *y, long y_stride, int n_items, const long *offse
  *   bas_stream_epilogue_f32 does for one stream, on session g's offset pointers: peaks[g] = max(peaks[g], max|y[e][g W +
  *   halo .. g W + halo + B)|) over both ears (:462 over the emitted samples; atomicMax on the bits of non-negative floats:
  *   exact, order-free); the input halo, the halo's boundaries and the angles at the block's end (last [G][2][n_src]) move
- *   as for one stream.  One launch. */
+ *   as for one stream.  One launch.
+ * bas_stream_batch_pack_head_f32: bas_stream_batch_pack_f32 with world-frame elev/azim and head [G][nb][4] (dense; session
+ *   g's orientation (w, x, y, z) at each of the block's boundaries, see "head tracking" below): the angle slots receive
+ *   the head-relative angles bas_head_relative_f64 computes, bit for bit.  Same checks, same launch count (one). */
 int bas_stream_batch_pack_f32(const float *blocks, const double *elev, const double *azim, int n_sessions, int n_src,
                               long B, int K, int halo, float *x, long x_stride, double *elev_out, double *azim_out,
                               long ang_stride, bas_stream_t stream);
+int bas_stream_batch_pack_head_f32(const float *blocks, const double *elev, const double *azim, const double *head,
+                                   int n_sessions, int n_src, long B, int K, int halo, float *x, long x_stride,
+                                   double *elev_out, double *azim_out, long ang_stride, bas_stream_t stream);
 int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
                                   double *elev, double *azim, long ang_stride, double *last, const float *y,
                                   long y_stride, float *peaks, bas_stream_t stream);
+
+/* ---- head tracking (no reference counterpart) -------------------------------------------------------
+ * Sources given in the world frame, the listener's head orientation per chunk boundary.  Directions follow the
+ * reference's convention (sphere.py:51-56): d = (-sin az cos el, cos az cos el, sin el), +y front, +z up, +x right.
+ * head = unit quaternion (w, x, y, z), float64 (any non-zero norm: it is normalised), rotating head coordinates into
+ * world ones: d_world = R(q) d_head, so d_head = R(q)^T d_world.  q is negated first when w < 0.  A pure yaw (x == y == 0
+ * after that) keeps the elevation bit for bit and gives az - 2 atan2(z, w) (az itself when z == 0: the identity changes
+ * neither angle); otherwise el_h = atan2(z_h, hypot(x_h, y_h)), az_h = atan2(-x_h, y_h), not wrapped.  Nothing is
+ * validated on the device: a non-finite head gives non-finite angles, a zero quaternion the identity.
+ *
+ * bas_head_relative_f64: elev/azim [G][n_src][nb] at elev[g in_stride_g + s in_stride_s + c] (world frame), head [G][nb][4]
+ *   at head[g head_stride_g + c head_stride_c + k] -> elev_out/azim_out[g out_stride_g + s out_stride_s + c] (head
+ *   relative).  The output strides must address every element once (BAS_E_SHAPE otherwise), head_stride_c >= 4, all
+ *   strides >= 0, all pointers 8-byte aligned (BAS_E_ALIGN).  In place: elev_out == elev and azim_out == azim with the
+ *   input strides on the output.  One launch. */
+int bas_head_relative_f64(const double *elev, const double *azim, long in_stride_g, long in_stride_s, const double *head,
+                          long head_stride_g, long head_stride_c, int n_groups, int n_src, int nb, double *elev_out,
+                          double *azim_out, long out_stride_g, long out_stride_s, bas_stream_t stream);
 
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All

@@ -7,8 +7,10 @@ both sides pay the same staging copies.  Per case it reports, as medians over th
     span includes the gaps the host leaves between the renderers' launches);
   * host_us: host time of the process() calls of one block (no synchronisation inside);
   * wall_us: host time of one block up to a stream synchronisation, and rtf = G B / fs / wall (real-time factor).
+With --head both sides are head-tracked: world-frame angles and a device tensor of head orientations
+per block (the batch rotates inside its pack launch, each lone renderer with one bas_head_relative_f64 launch).
 Prints one JSON line; --out also writes it to a file.
-    python3 tools/bench_stream_batch.py [--steps 50] [--warmup 5] [--out profiles/stream_batch_bench.json]"""
+    python3 tools/bench_stream_batch.py [--steps 50] [--warmup 5] [--case 256x512] [--head] [--out profiles/stream_batch_bench.json]"""
 import argparse
 import json
 import os
@@ -50,6 +52,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--case", action="append", default=None, metavar="GxB",
+                    help="only these cases (e.g. 256x512; repeatable); default: all of CASES")
+    ap.add_argument("--head", action="store_true", help="head-tracked: world angles + per-boundary head orientations")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -58,27 +63,32 @@ def main():
     tbl = bas.irs_and_delaydiffs(host.upsampling, host.diffs_left, host.diffs_right, host.irs_left, host.irs_right)
     rng = np.random.default_rng(0)
     result = {"workload": f"G sessions x {N_SRC} sources, K={K} S={S} L={L}, fs={FS}; one block per step",
-              "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "cases": []}
-    for G, B in CASES:
+              "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "head": args.head,
+              "cases": []}
+    cases = CASES if args.case is None else [tuple(int(v) for v in c.lower().split("x")) for c in args.case]
+    for G, B in cases:
         nb = B // K + 1
         x = torch.from_numpy((rng.standard_normal((G, N_SRC, B)) * 0.1).astype(np.float32)).cuda()
         e = torch.from_numpy(rng.uniform(-0.7, 1.2, (G, N_SRC, nb))).cuda()
         a = torch.from_numpy(rng.uniform(-7, 7, (G, N_SRC, nb))).cuda()
+        q = rng.standard_normal((G, nb, 4))
+        hd = torch.from_numpy(q / np.linalg.norm(q, axis=-1, keepdims=True)).cuda() if args.head else None
+        hg = (lambda g: None) if hd is None else (lambda g: hd[g])
         sb = bas.StreamBatchRenderer(tbl, G, N_SRC, K, S, graph=True, copy_out=False)
         sb.prepare(B)
-        batch = _time(lambda: sb.process(x, e, a), args.steps, args.warmup)
+        batch = _time(lambda: sb.process(x, e, a, head=hd), args.steps, args.warmup)
         loop_r = [bas.StreamRenderer(tbl, N_SRC, K, S, graph=True, copy_out=False) for _ in range(G)]
         for r in loop_r:
             r.prepare(B)
 
         def loop_step():
             for g, r in enumerate(loop_r):
-                r.process(x[g], e[g], a[g])
+                r.process(x[g], e[g], a[g], head=hg(g))
         loop = _time(loop_step, args.steps, args.warmup)
         # the same block through both: the batch's sessions against the lone renderers (carried state differs only by
         # the number of blocks each has seen, equal here)
-        y = sb.process(x, e, a).clone()
-        diff = max(float((y[g] - r.process(x[g], e[g], a[g])).abs().max()) for g, r in enumerate(loop_r))
+        y = sb.process(x, e, a, head=hd).clone()
+        diff = max(float((y[g] - r.process(x[g], e[g], a[g], head=hg(g))).abs().max()) for g, r in enumerate(loop_r))
         lay = sb.layout(B)
         audio_s = G * B / FS
         row = {"G": G, "n_src": N_SRC, "B": B, "T_in": lay.T_in,
