@@ -223,6 +223,12 @@ def render_mix(signals, chunksize, subchunksize, irs_per_source, normalize=True)
     """Multi-source semantics of this build (not in the reference):
     mix = sum over sources of the un-normalised float64 renders, cast to float32,
     then the reference's peak rule applied once to the mix."""
+    res = render_mix_f64(signals, chunksize, subchunksize, irs_per_source).astype(np.float32).T
+    return peak_normalize(res) if normalize else res
+
+
+def render_mix_f64(signals, chunksize, subchunksize, irs_per_source):
+    """render_mix's float64 (2, out_length) sum of the sources, before the float32 cast."""
     acc = None
     for x, irs in zip(signals, irs_per_source):
         x = np.asarray(x)
@@ -239,8 +245,7 @@ def render_mix(signals, chunksize, subchunksize, irs_per_source, normalize=True)
                 out[0, lo: lo + subchunksize + l - 1] += np.convolve(seg, h[0])
                 out[1, lo: lo + subchunksize + l - 1] += np.convolve(seg, h[1])
         acc = out if acc is None else acc + out
-    res = acc.astype(np.float32).T
-    return peak_normalize(res) if normalize else res
+    return acc
 
 
 # --------------------------------------------------------------------------
@@ -302,4 +307,100 @@ def render_window(x_win, m_first, chunksize, subchunksize, ir_of, l, n0, n1):
         lo, hi = max(n0, m), min(n1, m + l)                 # outputs this input sample reaches
         if hi > lo:
             out[:, lo - n0:hi - n0] += x_win[m - m_first] * g[:, lo - m:hi - m]
+    return out
+
+
+# --------------------------------------------------------------------------
+# batched a3 + a6 for whole-output checks (tests/test_whole_output_cpu.py holds it to interp2d bit for bit)
+# --------------------------------------------------------------------------
+_RING_START = np.cumsum((0,) + _RING_COUNTS[:-1])
+_TABLE_ELEV64 = _TABLE[:, 1].astype(np.float64)
+
+
+def _frac_shift_rows(x, s, step=1):
+    """frac_shift of every row of x (Q, M) by its own s (Q,), elementwise in frac_shift's order."""
+    q, m = x.shape
+    lo = np.floor(s).astype(np.int64)
+    hi = np.ceil(s).astype(np.int64)
+    f = (s - lo.astype(np.float64))[:, None]               # s - int(floor s), as the scalar form
+    # x[(n - lo) % m] for n = 0, step, .. is row window m - lo % m of [x | x]: whole-row copies, no per-sample index
+    win = np.lib.stride_tricks.sliding_window_view(np.concatenate([x, x], axis=1), m, axis=1)[:, :, ::step]
+    rows = np.arange(q)
+    return (1 - f) * win[rows, m - lo % m] + f * win[rows, m - hi % m]
+
+
+def _azim_params_many(elev, azim):
+    """azim_params for float64 arrays of ring elevations (the np.float64 branch): (before, a, after)."""
+    azim = azim % TWO_PI
+    elev = np.clip(elev, -np.pi / 4, np.pi / 2)
+    pole = np.abs(elev - np.pi / 2) < 1e-5
+    q = elev.size
+    before = np.full(q, POLE_INDEX, dtype=np.int64)
+    after = np.full(q, POLE_INDEX, dtype=np.int64)
+    a = np.zeros(q)
+    matched = np.zeros(q, dtype=bool)
+    for r, count in enumerate(_RING_COUNTS):
+        first = _RING_START[r]
+        on = ~pole & ~matched & (np.abs(_TABLE_ELEV64[first] - elev) < 1e-5)
+        matched |= on
+        if not on.any():
+            continue
+        ring_az = _TABLE[first:first + count, 2]           # float32, compared in float64 as the scalar form
+        az = azim[on]
+        le = ring_az[None, :] <= az[:, None]
+        if not le.any(axis=1).all():
+            raise ValueError("no ring node at or below the azimuth")
+        b = first + (count - 1 - np.argmax(le[:, ::-1], axis=1))          # largest index with az_node <= azim
+        gt = ~le
+        af = np.where(gt.any(axis=1), first + np.argmax(gt, axis=1), first)   # smallest index with az_node > azim
+        az_b = _TABLE[b, 2]
+        az_a = _TABLE[af, 2]
+        az_a = np.where(az_a < az_b, np.float32(TWO_PI), az_a)          # TWO_PI - float32 is float32 arithmetic
+        a[on] = (az - az_b) / (az_a - az_b)
+        before[on], after[on] = b, af
+    if not (pole | matched).all():
+        raise ValueError("elev is not one of the database elevations")
+    return before, a, after
+
+
+def _ring_interp_many(tbl, before, after, alpha):
+    """ring_interp(.., return_upsampled=True) per query: (delay_left, delay_right, (Q, 2, L*U))."""
+    u = tbl.upsampling
+    out, delays = [], []
+    for irs, diffs in ((tbl.irs_left, tbl.diffs_left), (tbl.irs_right, tbl.diffs_right)):
+        d = u * diffs[before, after]
+        q_nodelay = _frac_shift_rows(irs[after, :], -d)
+        blend = (1 - alpha)[:, None] * irs[before, :] + alpha[:, None] * q_nodelay
+        d_i = alpha * d
+        out.append(_frac_shift_rows(blend, d_i))
+        delays.append(d_i / u)
+    return delays[0], delays[1], np.stack(out, axis=1)
+
+
+def interp2d_many(tbl, elev, azim, batch=64):
+    """interp2d for float64 arrays of angles (the reference's np.float64 branch): (Q, 2, L) float64 chunk IRs,
+    bit-identical to calling interp2d once per query (every step is elementwise, in the same order).  The scalar
+    interp2d stays the definition; this is held to it.  Queries are taken `batch` at a time to bound memory."""
+    elev = np.asarray(elev, dtype=np.float64).reshape(-1)
+    azim = np.asarray(azim, dtype=np.float64).reshape(-1)
+    assert elev.shape == azim.shape
+    u = tbl.upsampling
+    out = np.empty((elev.size, 2, ir_length(tbl)))
+    for q0 in range(0, elev.size, batch):
+        e, z = elev[q0:q0 + batch], azim[q0:q0 + batch]
+        hi_i = np.searchsorted(_ELEVS, e, side="left")     # elev_bracket: min of _ELEVS >= elev, max of _ELEVS <= elev
+        lo_i = np.searchsorted(_ELEVS, e, side="right") - 1
+        higher = np.where(hi_i < _ELEVS.size, _ELEVS[np.minimum(hi_i, _ELEVS.size - 1)], 1.5707963267948966)
+        lower = np.where(lo_i >= 0, _ELEVS[np.maximum(lo_i, 0)], -0.78539816339744828)
+        pt, at, qt = _azim_params_many(higher, z)
+        pb, ab, qb = _azim_params_many(lower, z)
+        span = higher > lower
+        a = np.where(span, (e - lower) / np.where(span, higher - lower, 1.0), 0.0)
+        dlt, drt, top = _ring_interp_many(tbl, pt, qt, at)
+        dlb, drb, bot = _ring_interp_many(tbl, pb, qb, ab)
+        for ear, (diffs, dt, db) in enumerate(((tbl.diffs_left, dlt, dlb), (tbl.diffs_right, drt, drb))):
+            dv = u * (-dt + diffs[pt, pb] + db)
+            bot_nodelay = _frac_shift_rows(bot[:, ear, :], -dv)
+            blend = (1 - a)[:, None] * bot_nodelay + a[:, None] * top[:, ear, :]
+            out[q0:q0 + e.size, ear, :] = _frac_shift_rows(blend, (1 - a) * dv, u)
     return out

@@ -344,7 +344,7 @@ def test_long_ir_segments(tables):
 
 
 def test_linearity_and_determinism_at_full_size(dev_tables):
-    """BASELINE-size properties (oracle too slow here): render(a+b) = render(a)+render(b) with
+    """BASELINE-size properties (every sample against the oracle: test_gpu_whole_output.py): render(a+b) = render(a)+render(b) with
     normalisation off, bitwise run-to-run determinism, and chunk-aligned time invariance."""
     import torch
     h, d = dev_tables[("consistent", 128)]
