@@ -22,7 +22,7 @@ int bas_grid_for(long items, int cap);
 int bas_device_cus();                                  // CU count of the current device, cached
 hipError_t bas_allow_full_lds(const void *fn);         // dynamic-LDS limit of a kernel raised once per device
 struct BasTail;                                        // bas_tail.h
-// Carried state of a stream block (bas_stream.hip; bas.h "streaming"): what bas_stream_epilogue_f32 moves after a window's
+// Carried state of a stream block (bas_stream_batch.hip, bas.h): what bas_stream_epilogue_f32 moves after a window's
 // render.  The slab reduce kernels take one and do that work behind their own (x == null: nothing) - a launch less per block.
 struct BasCarry {
     float *x;                   // [n_src] rows [halo | block]: the last halo samples move to the front

@@ -1,14 +1,18 @@
-// Batched streams (include/bas.h "batched streams"): G independent streams of n_src sources advance by one
-// block of B samples in ONE render.  Session g's window [halo | block] starts at g·W of every source row, W = halo + B + K:
-// a zero chunk follows every window (its two boundaries are the end of session g and the start of session g+1, so the
-// crossfade of apply_hrtf.py:431-442 never mixes two sessions' angles into an emitted sample).  The angle rows hold nh + nb
-// boundaries per session, session g's from g·(nh + nb).  Two entry points around the unchanged render:
-//   bas_stream_batch_pack_f32     - scatter [G][n_src][B] blocks and [G][n_src][nb] angles into the windows' block columns
-//                                   and angle slots (never the halo columns, the halo angles or the gaps), one launch;
+// Carried state of block-wise rendering (bas.h "streaming", "batched streams").  A stream
+// is rendered as [halo | block] windows (the reference's chunk loop is causal, apply_hrtf.py:431-453).  Batched streams: G
+// independent streams of n_src sources advance by one block of B samples in ONE render.  Session g's window starts at g·W
+// of every source row, W = halo + B + K: a zero chunk follows every window (its two boundaries are the end of session g and
+// the start of session g+1, so the crossfade of apply_hrtf.py:431-442 never mixes two sessions' angles into an emitted
+// sample).  The angle rows hold nh + nb boundaries per session, session g's from g·(nh + nb).  Entry points:
+//   bas_stream_batch_pack_f32      - scatter [G][n_src][B] blocks and [G][n_src][nb] angles into the windows' block columns
+//                                    and angle slots (never the halo columns, the halo angles or the gaps), one launch;
 //   bas_stream_batch_pack_head_f32 - the same scatter with world-frame angles and [G][nb][4] head orientations: the angle
-//                                   slots get the head-relative angles (bas_head.h), still one launch;
-//   bas_stream_batch_epilogue_f32 - per session, what bas_stream_epilogue_f32 does for one stream: the running peak over
-//                                   the emitted samples and the moves of the carried state, one launch.
+//                                    slots get the head-relative angles (bas_head.h), still one launch;
+//   bas_stream_batch_epilogue_f32  - behind the render, per session: the running peak over the samples the block emits (the
+//                                    window's first `halo` outputs were emitted before, its last L-1 are incomplete) and
+//                                    the moves of the carried state (bas_carry_moves), one launch;
+//   bas_stream_epilogue_f32        - the same kernel on ONE stream (one session row), behind renders that do not move the
+//                                    carried state themselves (stream.py's two-call blocks, direct-output fused blocks).
 #include "bas_internal.h"
 #include "bas_head.h"
 
@@ -62,7 +66,9 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
 
 // One row of workgroups per session.  peaks[g] = max(peaks[g], max|y[e][g·W + halo .. g·W + halo + B)|), e = 0, 1
 // (atomicMax on the bits of non-negative floats: exact and order-free), then bas_carry_moves on session g's offset pointers.
-__global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_epilogue_kernel(
+// peak_bits may be null (bas_stream_epilogue_f32): the test is on a kernel argument, the same for the whole workgroup, as
+// bas_block_peak_max's barrier needs.
+__global__ __launch_bounds__(SB_THREADS) void bas_stream_block_epilogue_kernel(
     float *__restrict__ x, long x_stride, int n_src, int halo, long B, long W, double *__restrict__ elev,
     double *__restrict__ azim, long ang_stride, int nh, int nb, double *__restrict__ last, const float *__restrict__ y,
     long y_stride, unsigned int *__restrict__ peak_bits) {
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_epilogue_kernel(
         const long tail0 = head + 4 * nq;
         if (blockIdx.x == 0 && tail0 + threadIdx.x < B) lmax = fmaxf(lmax, fabsf(w[tail0 + threadIdx.x]));
     }
-    bas_block_peak_max(lmax, peak_bits + g);
+    if (peak_bits) bas_block_peak_max(lmax, peak_bits + g);
     BasCarry C;
     C.x = x + (long)g * W; C.x_stride = x_stride; C.n_src = n_src; C.halo = halo; C.B = B;
     C.elev = elev + (long)g * (nh + nb); C.azim = azim + (long)g * (nh + nb); C.ang_stride = ang_stride;
@@ -116,34 +122,36 @@ static int sb_check_layout(const char *what, int n_sessions, int n_src, long B, 
     return 0;
 }
 
-extern "C" int bas_stream_batch_pack_f32(const float *blocks, const double *elev, const double *azim, int n_sessions,
-                                         int n_src, long B, int K, int halo, float *x, long x_stride, double *elev_out,
-                                         double *azim_out, long ang_stride, bas_stream_t stream) {
-    int rc = sb_check_layout("bas_stream_batch_pack_f32", n_sessions, n_src, B, K, halo, x_stride, ang_stride);
+// both pack entry points: the layout checks, the pointers (head only with HEAD), one launch
+template <bool HEAD>
+static int sb_pack(const char *what, const float *blocks, const double *elev, const double *azim, const double *head,
+                   int n_sessions, int n_src, long B, int K, int halo, float *x, long x_stride, double *elev_out,
+                   double *azim_out, long ang_stride, bas_stream_t stream) {
+    int rc = sb_check_layout(what, n_sessions, n_src, B, K, halo, x_stride, ang_stride);
     if (rc) return rc;
-    BAS_REQUIRE(blocks && elev && azim && x && elev_out && azim_out, BAS_E_NULL, "bas_stream_batch_pack_f32: null pointer");
+    BAS_REQUIRE(blocks && elev && azim && (!HEAD || head) && x && elev_out && azim_out, BAS_E_NULL, "%s: null pointer",
+                what);
     const long W = halo + B + K;
     const int nh = halo / K, nb = (int)(B / K + 1);
     const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
-    hipLaunchKernelGGL(bas_stream_batch_pack_kernel<false>, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev,
-                       azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, nullptr);
-    return bas_check_launch("bas_stream_batch_pack_f32");
+    hipLaunchKernelGGL(bas_stream_batch_pack_kernel<HEAD>, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev,
+                       azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head);
+    return bas_check_launch(what);
+}
+
+extern "C" int bas_stream_batch_pack_f32(const float *blocks, const double *elev, const double *azim, int n_sessions,
+                                         int n_src, long B, int K, int halo, float *x, long x_stride, double *elev_out,
+                                         double *azim_out, long ang_stride, bas_stream_t stream) {
+    return sb_pack<false>("bas_stream_batch_pack_f32", blocks, elev, azim, nullptr, n_sessions, n_src, B, K, halo, x,
+                          x_stride, elev_out, azim_out, ang_stride, stream);
 }
 
 extern "C" int bas_stream_batch_pack_head_f32(const float *blocks, const double *elev, const double *azim,
                                               const double *head, int n_sessions, int n_src, long B, int K, int halo,
                                               float *x, long x_stride, double *elev_out, double *azim_out, long ang_stride,
                                               bas_stream_t stream) {
-    int rc = sb_check_layout("bas_stream_batch_pack_head_f32", n_sessions, n_src, B, K, halo, x_stride, ang_stride);
-    if (rc) return rc;
-    BAS_REQUIRE(blocks && elev && azim && head && x && elev_out && azim_out, BAS_E_NULL,
-                "bas_stream_batch_pack_head_f32: null pointer");
-    const long W = halo + B + K;
-    const int nh = halo / K, nb = (int)(B / K + 1);
-    const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
-    hipLaunchKernelGGL(bas_stream_batch_pack_kernel<true>, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev,
-                       azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head);
-    return bas_check_launch("bas_stream_batch_pack_head_f32");
+    return sb_pack<true>("bas_stream_batch_pack_head_f32", blocks, elev, azim, head, n_sessions, n_src, B, K, halo, x,
+                         x_stride, elev_out, azim_out, ang_stride, stream);
 }
 
 extern "C" int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
@@ -158,8 +166,24 @@ extern "C" int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sess
     const int nh = halo / K, nb = (int)(B / K + 1);
     const long work = (2 * B) / 4 > (long)n_src * halo ? (2 * B) / 4 : (long)n_src * halo;
     const dim3 grid(sb_blocks_x(n_sessions, work), n_sessions);
-    hipLaunchKernelGGL(bas_stream_batch_epilogue_kernel, grid, dim3(SB_THREADS), 0, bas_stream(stream), x, x_stride, n_src,
+    hipLaunchKernelGGL(bas_stream_block_epilogue_kernel, grid, dim3(SB_THREADS), 0, bas_stream(stream), x, x_stride, n_src,
                        halo, B, W, elev, azim, ang_stride, nh, nb, last, y, y_stride,
                        reinterpret_cast<unsigned int *>(peaks));
     return bas_check_launch("bas_stream_batch_epilogue_f32");
+}
+
+extern "C" int bas_stream_epilogue_f32(float *x, long x_stride, int n_src, int halo, long B, double *elev, double *azim,
+                                       long ang_stride, int nh, int nb, double *last, const float *y, long y_stride,
+                                       float *running_peak, bas_stream_t stream) {
+    BAS_REQUIRE(n_src >= 0 && halo >= 0 && B > 0 && nh >= 0 && nb >= 2, BAS_E_SHAPE,
+                "bas_stream_epilogue_f32: need n_src>=0, halo>=0, B>0, nh>=0, nb>=2 (n_src=%d halo=%d B=%ld nh=%d nb=%d)",
+                n_src, halo, B, nh, nb);
+    BAS_REQUIRE(x_stride >= halo + B && ang_stride >= nh + nb && y_stride >= halo + B, BAS_E_SHAPE,
+                "bas_stream_epilogue_f32: strides shorter than the window");
+    BAS_REQUIRE(y && (n_src == 0 || (x && elev && azim && last)), BAS_E_NULL, "bas_stream_epilogue_f32: null pointer");
+    long work = 2 * B > (long)n_src * halo ? 2 * B : (long)n_src * halo;
+    hipLaunchKernelGGL(bas_stream_block_epilogue_kernel, dim3(bas_grid_for(work, 1024)), dim3(SB_THREADS), 0,
+                       bas_stream(stream), x, x_stride, n_src, halo, B, 0L, elev, azim, ang_stride, nh, nb, last, y,
+                       y_stride, reinterpret_cast<unsigned int *>(running_peak));      // (one session: W unused)
+    return bas_check_launch("bas_stream_epilogue_f32");
 }

@@ -146,6 +146,7 @@ def render_time_sharded(signals, chunksize, subchunksize, elev, azim, tbl, ir_le
     Returns (T_out, 2) on rank dst, None elsewhere."""
     import torch
     import torch.distributed as dist
+    from .stream import halo_samples
     if render_fn is None:
         from .apply_hrtf import render_sources
         render_fn = lambda s, k, ss, e, a, t: render_sources(s, k, ss, e, a, t, normalize="none")   # noqa: E731
@@ -156,7 +157,7 @@ def render_time_sharded(signals, chunksize, subchunksize, elev, azim, tbl, ir_le
     sig = torch.as_tensor(signals)
     n_src, n = sig.shape
     n_chunks = -(-n // K)
-    halo_c = -(-(L - 1) // K) if L > 1 else 0
+    halo_c = halo_samples(K, L) // K
     c0, c1 = shard_time(n_chunks, world, rank)
     h0 = max(c0 - halo_c, 0)                                  # first chunk read
     x = sig[:, h0 * K:min(c1 * K, n)]

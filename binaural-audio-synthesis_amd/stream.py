@@ -22,7 +22,8 @@ writes y itself, and shapes the fused kernels do not serve, end in bas_stream_ep
 instead).  With graph=True those are replayed as ONE hipGraph launch.  `prepare(B)` lays the buffers out and
 captures the graph BEFORE streaming starts (capture synchronises the device and must not
 race with allocations of other threads: keep it out of the real-time phase); without it the
-first block of a size runs as plain launches and the second one captures.
+first block of a size runs as plain launches and the second one captures.  That life cycle, the render of a window
+and the workspaces it needs live in _BlockStream, which StreamRenderer and stream_batch.StreamBatchRenderer share.
 
 Why the halo is a whole number of CHUNKS (K) rather than L-1 rounded to 32: the kernels
 take windows whose first sample lies on a chunk boundary (the crossfade position of an input
@@ -51,6 +52,17 @@ def rotate_into_views(elev, azim, head, views):
     sphere.head_relative_angles_device(src[0], src[1], head, out=views)
 
 
+def halo_samples(K, L):
+    """The carried halo of a stream: L - 1 rounded up to whole chunks (0 at L = 1)."""
+    K, L = int(K), int(L)
+    return -(-(L - 1) // K) * K if L > 1 else 0
+
+
+def _is_buffer(t, view, dtype):
+    """t already is `view` of a renderer's own buffer (a producer wrote there in place): nothing to copy."""
+    return t.is_cuda and t.dtype == dtype and t.data_ptr() == view.data_ptr() and t.stride() == view.stride()
+
+
 def tile_filling_block(about, chunksize, ir_length, tile=8192):
     """The largest block length <= `about` (a multiple of the chunk size) whose window - [halo | block] inputs, L - 1 more
     outputs - ends on a tile boundary of the big scenes' FIR kernel (8192 outputs per (tile, source) unit) or just before it.
@@ -58,14 +70,93 @@ def tile_filling_block(about, chunksize, ir_length, tile=8192):
     are 32.08 tiles, rendered as 33 (+ 3 %: 3 661 against 3 788 x real time for BASELINE config 5); 261 120 are 31.95.
     Returns `about` rounded down to chunks where no whole tile fits."""
     K, L = int(chunksize), int(ir_length)
-    halo = -(-(L - 1) // K) * K if L > 1 else 0
+    halo = halo_samples(K, L)
     about = int(about) // K * K
     tiles = (halo + about + L - 1) // tile
     best = (tiles * tile - (L - 1) - halo) // K * K
     return best if tiles >= 1 and best >= K else max(about, K)
 
 
-class StreamRenderer:
+class _BlockStream:
+    """What a block-wise renderer does the same way whatever its layout: the table, K, S and the halo; the block's hipGraph
+    (the first block of a size runs plain, the second captures; prepare() captures before streaming starts); the render of
+    one window and its workspaces; process()'s fresh tensor or view.  A subclass lays out its buffers (_layout, which sets
+    _blocks_in_layout to 0 and drops _graph), stages the inputs, and provides _block_body (the stream-ordered work of one
+    block), input_view, _carried (the tensors prepare() must leave as they were) and _emitted (the samples a block emits)."""
+
+    def __init__(self, tbl, chunksize, subchunksize, graph, copy_out):
+        assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
+        self.tbl = as_device_table(tbl)
+        self.K, self.S = int(chunksize), int(subchunksize)
+        self.halo = halo_samples(self.K, self.tbl.L)
+        self.nh = self.halo // self.K                     # chunk boundaries carried with the halo
+        self.graph_enabled, self.copy_out = bool(graph), bool(copy_out)
+        self._graph = None
+        self._blocks_in_layout = 0
+        self._events = None                               # (begin, end) raw hipEvent_t around the FIR kernel of plain-launch blocks (bench.py)
+
+    def _window_workspaces(self, n_src, T_in, n_q):
+        """The render workspace of a window of n_src x T_in inputs (the larger of the stored-IR and the fused path's) and
+        the read plans' workspace of its n_q chunk boundaries."""
+        import torch
+        lib, dev, K, S, L = _hip.lib(), self.tbl.device, self.K, self.S, self.tbl.L
+        with _hip.on_device(dev):
+            wb = max(lib.bas_render_workspace_bytes(n_src, T_in, K, S, L),
+                     lib.bas_render_fused_workspace_bytes(n_src, T_in, K, S, L))
+        self._ws = _hip.new_workspace(wb, dev)
+        self._ws_plans = torch.empty((lib.bas_interp2d_workspace_bytes(n_q),), dtype=torch.uint8, device=dev)
+
+    def _render_window(self, x, elev, azim):
+        """a3, read plans, chunk IRs + FIR + mix (or the stored-IR path) of one window into self._y: no peak, no peak rule
+        (the epilogue takes the peak of the EMITTED samples)."""
+        render_angles_device(x, self.K, self.S, self.tbl, elev, azim, normalize="none", out=self._y, ws=self._ws,
+                             ws_plans=self._ws_plans, events=self._events, want_peak=False)
+
+    def _capture(self):
+        import torch
+        assert self._events is None, "HIP events of a profiling caller cannot be captured into the block's graph"
+        g = torch.cuda.CUDAGraph()
+        # thread_local: allocations or copies of OTHER threads (a producer filling input_view()) do not invalidate
+        # the capture; the capture's own allocations come from the graph's private pool
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._block_body()
+        self._graph = g
+
+    def _run_block(self):
+        """Render the staged block; returns what it emits (a fresh tensor, or with copy_out=False the view)."""
+        if self._graph is not None:
+            self._graph.replay()
+        elif not self.graph_enabled or self._blocks_in_layout == 0:
+            self._block_body()                            # no prepare(): the first block of a size runs plain (warm-up)
+        else:
+            self._capture()                               # ... and the second one captures (a device synchronisation:
+            self._graph.replay()                          # real-time callers use prepare() instead)
+        self._blocks_in_layout += 1
+        out = self._emitted()
+        return out.clone() if self.copy_out else out
+
+    def prepare(self, B):
+        """Lay out the buffers for blocks of B samples, run one block on silence as a warm-up (first-use costs of the
+        kernels) and, with graph=True, capture the block's hipGraph - all BEFORE streaming starts, so that no
+        process() call ever pays for a capture (which synchronises the device for milliseconds).  The carried
+        state (input halo, halo angles, end angles, running peaks) is left exactly as it was.
+        Call again after a change of block size or after input_view() had to grow.  The warm-up block is rendered
+        into the renderer's own output buffer: a block view handed out by process() with copy_out=False is overwritten
+        by it - consume such a view before calling prepare() mid-stream."""
+        import torch
+        self._layout(B)
+        keep = [t.clone() for t in self._carried()]
+        self.input_view(B).zero_()
+        self._block_body()                                # plain launches: warm-up
+        if self.graph_enabled and self._graph is None:
+            self._capture()                               # (records the launches, does not execute them)
+        torch.cuda.synchronize(self.tbl.device)
+        for t, saved in zip(self._carried(), keep):
+            t.copy_(saved)
+        self._blocks_in_layout = max(self._blocks_in_layout, 1)
+
+
+class StreamRenderer(_BlockStream):
     one_call = True      # bas_render_stream_block_f32 where the fused kernels serve the block (False: render + epilogue launch; A/B, tests)
 
     def __init__(self, tbl, n_src, chunksize, subchunksize, graph=True, copy_out=True):
@@ -73,19 +164,13 @@ class StreamRenderer:
         size).  copy_out: process() returns a fresh tensor (True) or a view of the renderer's output buffer that
         the next process() call overwrites (False: no copy kernel; for callers that consume each block at once)."""
         import torch
-        assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
-        self.tbl = as_device_table(tbl)
-        self.n_src, self.K, self.S = int(n_src), int(chunksize), int(subchunksize)
-        L = self.tbl.L
-        self.halo = -(-(L - 1) // self.K) * self.K if L > 1 else 0
-        self.nh = self.halo // self.K                     # chunk boundaries carried with the halo
+        super().__init__(tbl, chunksize, subchunksize, graph, copy_out)
+        self.n_src = int(n_src)
         dev = self.tbl.device
-        self.graph_enabled, self.copy_out = bool(graph), bool(copy_out)
         # input staging buffer [n_src, halo + capacity]: columns [0, halo) carry the previous inputs, a block
         # is rendered in place behind them (input_view() lets a producer write there directly: no copy)
         self._xbuf = torch.zeros((self.n_src, self.halo), dtype=torch.float32, device=dev)
         self._B = None                                    # block size the per-block buffers are laid out for
-        self._graph = None
         self._halo_params = None                          # (elev, azim) [n_src, nh] of the halo's boundaries across a re-layout
         self._started = False                             # a block has been rendered
         # the angles at the END of the last block, for finish(): their own buffer, so that a change of block size
@@ -94,7 +179,6 @@ class StreamRenderer:
         self._peak_dev = torch.zeros((1,), dtype=torch.float32, device=dev)
         self.samples_in = 0
         self._finished = False
-        self._events = None                               # (begin, end) raw hipEvent_t around the FIR kernel of plain-launch blocks (bench.py)
         self._head_buf = None                             # device staging of host head orientations (process(head=...))
 
     # ---- buffers ---------------------------------------------------------------------------------------
@@ -125,16 +209,8 @@ class StreamRenderer:
         if self._halo_params is not None:
             self._elev_all[:, :nh], self._azim_all[:, :nh] = self._halo_params
             self._halo_params = None
-        self._idx = torch.empty((n * (nh + nb), 4), dtype=torch.int32, device=dev)
-        self._w = torch.empty((n * (nh + nb), 3), dtype=torch.float64, device=dev)
         self._y = torch.empty((2, self.halo + B + self.tbl.L - 1), dtype=torch.float32, device=dev)
-        lib = _hip.lib()
-        t_in = self.halo + B
-        with _hip.on_device(dev):
-            wb = max(lib.bas_render_workspace_bytes(n, t_in, self.K, self.S, self.tbl.L),
-                     lib.bas_render_fused_workspace_bytes(n, t_in, self.K, self.S, self.tbl.L))
-        self._ws = _hip.new_workspace(wb, dev)
-        self._ws_plans = torch.empty((lib.bas_interp2d_workspace_bytes(n * (nh + nb)),), dtype=torch.uint8, device=dev)
+        self._window_workspaces(n, self.halo + B, n * (nh + nb))
 
     def input_view(self, B):
         """Device view [n_src, B] of the renderer's own input buffer.  A producer (decoder, H2D copy,
@@ -177,52 +253,24 @@ class StreamRenderer:
                 else:
                     _hip.call("bas_render_stream_block_profiled_f32", *args, self._events[0], self._events[1])
             return
-        # other shapes: a3, read plans, chunk IRs + FIR + mix (or the stored-IR path), then the epilogue launch
-        render_angles_device(x, self.K, self.S, self.tbl, self._elev_all, self._azim_all, normalize="none",
-                             out=self._y, ws=self._ws, ws_plans=self._ws_plans, params=(self._idx, self._w),
-                             events=self._events, want_peak=False)   # (the epilogue tracks the peak of the EMITTED samples)
+        # other shapes: the render of the window, then the epilogue launch
+        self._render_window(x, self._elev_all, self._azim_all)
         with _hip.on_device(dev):
             _hip.call("bas_stream_epilogue_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), self.n_src, halo, B,
                       _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0), nh, nb,
                       _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peak_dev),
                       _hip.current_stream(dev))
 
-    def _capture(self):
-        import torch
-        assert self._events is None, "HIP events of a profiling caller cannot be captured into the block's graph"
-        g = torch.cuda.CUDAGraph()
-        # thread_local: allocations or copies of OTHER threads (a decoder filling input_view()) do not invalidate
-        # the capture; the capture's own allocations come from the graph's private pool
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._block_body()
-        self._graph = g
+    def _carried(self):
+        return self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev
+
+    def _emitted(self):
+        return self._y[:, self.halo:self.halo + self._B].t()
 
     def prepare(self, B):
-        """Lay out the buffers for blocks of B samples, run one block on silence as a warm-up (first-use costs of the
-        kernels) and, with graph=True, capture the block's hipGraph - all BEFORE streaming starts, so that no
-        process() call ever pays for a capture (which synchronises the device for milliseconds).  The carried
-        state (input halo, halo angles, end angles, running peak, sample count) is left exactly as it was.
-        Call again after a change of block size or after input_view() had to grow.  The warm-up block is rendered
-        into the renderer's own output buffer: a block view handed out by process() with copy_out=False is overwritten
-        by it - consume such a view before calling prepare() mid-stream."""
-        import torch
         assert not self._finished, "stream already finished"
         assert B % self.K == 0 and B > 0, 'block length must be a positive multiple of the chunk size'
-        self._layout(B)
-        halo, nh = self.halo, self.nh
-        keep = (self._xbuf[:, :halo + B].clone(), self._elev_all.clone(), self._azim_all.clone(), self._last.clone(),
-                self._peak_dev.clone())
-        self._xbuf[:, halo:halo + B].zero_()
-        self._block_body()                                # plain launches: warm-up
-        if self.graph_enabled and self._graph is None:
-            self._capture()                               # (records the launches, does not execute them)
-        torch.cuda.synchronize(self.tbl.device)
-        self._xbuf[:, :halo + B].copy_(keep[0])
-        self._elev_all.copy_(keep[1])
-        self._azim_all.copy_(keep[2])
-        self._last.copy_(keep[3])
-        self._peak_dev.copy_(keep[4])
-        self._blocks_in_layout = max(self._blocks_in_layout, 1)
+        super().prepare(B)
 
     def process(self, block, elev, azim, head=None):
         """block: [n_src, B] (B a multiple of the chunk size); elev/azim: float64 [n_src, B/K + 1],
@@ -246,7 +294,7 @@ class StreamRenderer:
                 t = torch.as_tensor(src)
                 if tuple(t.shape) != (self.n_src, nb):
                     raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
-                if not (t.is_cuda and t.data_ptr() == dst.data_ptr() and t.dtype == torch.float64 and t.stride() == dst.stride()):
+                if not _is_buffer(t, dst, torch.float64):
                     dst.copy_(t)                          # (H2D for host arrays; float64 kept exactly)
         else:
             views = (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:])
@@ -256,22 +304,12 @@ class StreamRenderer:
             q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
             rotate_into_views(elev, azim, q, views)
         x_dst = self._xbuf[:, self.halo:self.halo + B]
-        in_place = blk.is_cuda and blk.dtype == torch.float32 and blk.stride() == x_dst.stride() and \
-            blk.data_ptr() == x_dst.data_ptr()
-        if not in_place:
+        if not _is_buffer(blk, x_dst, torch.float32):
             x_dst.copy_(blk)
-        if self._graph is not None:
-            self._graph.replay()
-        elif not self.graph_enabled or self._blocks_in_layout == 0:
-            self._block_body()                            # no prepare(): the first block of a size runs plain (warm-up)
-        else:
-            self._capture()                               # ... and the second one captures (a device synchronisation:
-            self._graph.replay()                          # real-time callers use prepare() instead)
+        out = self._run_block()
         self._started = True
-        self._blocks_in_layout += 1
         self.samples_in += B
-        out = self._y[:, self.halo:self.halo + B].t()
-        return out.clone() if self.copy_out else out
+        return out
 
     @property
     def peak(self):

@@ -16,8 +16,8 @@ but one block of all G sessions is ONE render, laid out as render_batch lays out
 One block: bas_stream_batch_pack_f32 (unless the producer wrote in place through input_view / trajectory_views), then the
 unchanged render (read plans + fused FIR, or the stored-IR path; no peak, no peak rule), then
 bas_stream_batch_epilogue_f32 (per-session running peaks over the emitted samples and the moves of every session's carried
-state).  With graph=True everything after the pack is replayed as one hipGraph, captured under the same rules as
-StreamRenderer's (`prepare(B)` before streaming; else the first block of a size runs plain and the second captures).
+state).  With graph=True everything after the pack is replayed as one hipGraph, captured by StreamRenderer's code
+(stream._BlockStream: `prepare(B)` before streaming; else the first block of a size runs plain and the second captures).
 
 The planner (`plan_stream_layout`) is plain numpy and needs no GPU.
 """
@@ -27,16 +27,9 @@ import numpy as np
 
 from . import _hip, sphere
 from .batch import MAX_RENDER_SAMPLES, render_batch
-from .apply_hrtf import as_device_table, render_angles_device
-from .stream import rotate_into_views
+from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views
 
 MAX_SESSIONS = 65535             # the epilogue and pack kernels have one row of workgroups per session (gridDim.y)
-
-
-def halo_samples(K, L):
-    """StreamRenderer.halo: L - 1 rounded up to whole chunks (0 at L = 1)."""
-    K, L = int(K), int(L)
-    return -(-(L - 1) // K) * K if L > 1 else 0
 
 
 @dataclass(frozen=True)
@@ -127,22 +120,15 @@ def _session_runs(idx):
     return [tuple(r) for r in runs]
 
 
-class StreamBatchRenderer:
+class StreamBatchRenderer(_BlockStream):
     def __init__(self, tbl, n_sessions, n_src, chunksize, subchunksize, graph=True, copy_out=True):
         """n_sessions independent streams of n_src sources each.  graph, copy_out: as for StreamRenderer."""
         import torch
-        assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
         self.G, self.n_src = int(n_sessions), int(n_src)
-        self.K, self.S = int(chunksize), int(subchunksize)
-        plan_stream_layout(self.G, self.n_src, self.K, 1, self.K)          # (session and source counts: ValueError)
-        self.tbl = as_device_table(tbl)
-        self.halo = halo_samples(self.K, self.tbl.L)
-        self.nh = self.halo // self.K
+        plan_stream_layout(self.G, self.n_src, int(chunksize), 1, int(chunksize))   # (session and source counts: ValueError)
+        super().__init__(tbl, chunksize, subchunksize, graph, copy_out)
         dev = self.tbl.device
-        self.graph_enabled, self.copy_out = bool(graph), bool(copy_out)
         self._lay = None                                  # layout of the current block size
-        self._graph = None
-        self._blocks_in_layout = 0
         # the angles at the END of every session's last block (finish()), in their own buffer: a change of block size
         # re-lays the per-block buffers out and cannot lose them
         self._last = torch.zeros((self.G, 2, self.n_src), dtype=torch.float64, device=dev)
@@ -180,14 +166,7 @@ class StreamBatchRenderer:
         self._blk = None                                  # staging buffers of the pack (allocated on first use)
         self._ang_in = None
         self._head_in = None
-        lib = _hip.lib()
-        with _hip.on_device(dev):
-            wb = max(lib.bas_render_workspace_bytes(n, lay.T_in, self.K, self.S, self.tbl.L),
-                     lib.bas_render_fused_workspace_bytes(n, lay.T_in, self.K, self.S, self.tbl.L))
-        self._ws = _hip.new_workspace(wb, dev)
-        self._ws_plans = torch.empty((lib.bas_interp2d_workspace_bytes(n * lay.n_q),), dtype=torch.uint8, device=dev)
-        self._idx = torch.empty((n * lay.n_q, 4), dtype=torch.int32, device=dev)
-        self._w = torch.empty((n * lay.n_q, 3), dtype=torch.float64, device=dev)
+        self._window_workspaces(n, lay.T_in, n * lay.n_q)
 
     def layout(self, B):
         """The StreamLayout of blocks of B samples (no device work)."""
@@ -221,41 +200,15 @@ class StreamBatchRenderer:
     def _block_body(self):
         """The stream-ordered work of one block after the pack (captured into the hipGraph)."""
         lay, dev = self._lay, self.tbl.device
-        render_angles_device(self._x[:, :lay.T_in], self.K, self.S, self.tbl, self._elev, self._azim, normalize="none",
-                             out=self._y, ws=self._ws, ws_plans=self._ws_plans, params=(self._idx, self._w),
-                             want_peak=False)                 # (the epilogue takes each session's peak of the EMITTED samples)
+        self._render_window(self._x[:, :lay.T_in], self._elev, self._azim)
         with _hip.on_device(dev):
             _hip.call("bas_stream_batch_epilogue_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src, self.halo,
                       lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0),
                       _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peaks),
                       _hip.current_stream(dev))
 
-    def _capture(self):
-        import torch
-        g = torch.cuda.CUDAGraph()
-        # thread_local: allocations or copies of OTHER threads (a producer filling input_view()) do not invalidate
-        # the capture; the capture's own allocations come from the graph's private pool
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._block_body()
-        self._graph = g
-
-    def prepare(self, B):
-        """Lay out the buffers for blocks of B samples, run one block on silence as a warm-up and, with graph=True,
-        capture the block's hipGraph - before streaming starts, as StreamRenderer.prepare.  Every session's carried state
-        (input halo, halo angles, end angles, running peak) is left exactly as it was.  The warm-up overwrites the output
-        buffer: consume a view handed out with copy_out=False first."""
-        import torch
-        self._layout(B)
-        halo = self.halo
-        keep = (self._x.clone(), self._elev.clone(), self._azim.clone(), self._last.clone(), self._peaks.clone())
-        self._x3()[:, :, halo:halo + B].zero_()
-        self._block_body()                                # plain launches: warm-up
-        if self.graph_enabled and self._graph is None:
-            self._capture()                               # (records the launches, does not execute them)
-        torch.cuda.synchronize(self.tbl.device)
-        for buf, saved in zip((self._x, self._elev, self._azim, self._last, self._peaks), keep):
-            buf.copy_(saved)
-        self._blocks_in_layout = max(self._blocks_in_layout, 1)
+    def _carried(self):
+        return self._x, self._elev, self._azim, self._last, self._peaks
 
     def process(self, blocks, elev, azim, head=None):
         """blocks: [G, n_src, B] (B a multiple of the chunk size); elev/azim: float64 [G, n_src, B/K + 1], every session's
@@ -282,11 +235,8 @@ class StreamBatchRenderer:
         for t in angs:
             if tuple(t.shape) != (self.G, self.n_src, lay.nb):
                 raise ValueError(f"elev/azim must have shape ({self.G}, {self.n_src}, {lay.nb})")
-
-        def same(t, view, dtype):
-            return t.is_cuda and t.dtype == dtype and t.data_ptr() == view.data_ptr() and t.stride() == view.stride()
-        x_in_place = same(blk, x_view, torch.float32)
-        a_in_place = all(same(t, v, torch.float64) for t, v in zip(angs, views))
+        x_in_place = _is_buffer(blk, x_view, torch.float32)
+        a_in_place = all(_is_buffer(t, v, torch.float64) for t, v in zip(angs, views))
         if head is not None:                              # (the renderer's own head buffer is dense: the fused pack reads it)
             q, self._head_in = sphere.head_to_device(head, (self.G, lay.nb, 4), dev, self._head_in)
             if not (x_in_place or a_in_place):
@@ -320,16 +270,7 @@ class StreamBatchRenderer:
                     _hip.call("bas_stream_batch_pack_head_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
                               _hip.ptr(q), self.G, self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0),
                               _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
-        if self._graph is not None:
-            self._graph.replay()
-        elif not self.graph_enabled or self._blocks_in_layout == 0:
-            self._block_body()                            # no prepare(): the first block of a size runs plain (warm-up)
-        else:
-            self._capture()                               # ... and the second one captures (a device synchronisation:
-            self._graph.replay()                          # real-time callers use prepare() instead)
-        self._blocks_in_layout += 1
-        out = self._emitted()
-        return out.clone() if self.copy_out else out
+        return self._run_block()
 
     # ---- per-session state -----------------------------------------------------------------------------
     @property
