@@ -86,10 +86,34 @@ SIGNATURES = {
                                                       _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
                                                       _c_int, _c_void_p, _c_void_p, _c_long, _c_int, _c_int, _c_void_p,
                                                       _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    # per-source gain at chunk boundaries
+    "bas_interp2d_plan_gain_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int,
+                                            _c_void_p, _c_size_t, _c_void_p]),
+    "bas_interp2d_plan_angles_gain_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p,
+                                                   _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int,
+                                                   _c_void_p, _c_size_t, _c_void_p]),
+    "bas_interp2d_gain_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int,
+                                       _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "bas_render_stream_block_gain_f32": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_void_p, _c_int, _c_long, _c_int,
+                                                  _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_int,
+                                                  _c_void_p, _c_void_p, _c_void_p, _c_long, _c_int, _c_int, _c_void_p,
+                                                  _c_void_p, _c_void_p, _c_void_p]),
+    "bas_stream_epilogue_gain_f32": (_c_int, [_c_void_p, _c_long, _c_int, _c_int, _c_long, _c_void_p, _c_void_p,
+                                              _c_void_p, _c_long, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_long,
+                                              _c_void_p, _c_void_p]),
+    "bas_stream_batch_pack_gain_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int,
+                                                _c_long, _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p,
+                                                _c_void_p, _c_long, _c_void_p]),
+    "bas_stream_batch_epilogue_gain_f32": (_c_int, [_c_void_p, _c_long, _c_int, _c_int, _c_int, _c_long, _c_int,
+                                                    _c_void_p, _c_void_p, _c_void_p, _c_long, _c_void_p, _c_void_p,
+                                                    _c_void_p, _c_long, _c_void_p, _c_void_p]),
+    "bas_batch_pack_gain_f32": (_c_int, [_c_void_p, _c_int, _c_int, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_long, _c_int, _c_long, _c_void_p, _c_long, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_void_p]),
 }
 
 _lib = None
-ABI_VERSION = 5                                                      # BAS_ABI_VERSION of include/bas.h
+ABI_VERSION = 6                                                      # BAS_ABI_VERSION of include/bas.h
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libbas_hip_diag.so")   # -DBAS_DIAG build: reads BAS_FORCE_KERNEL (tests only)
 
 

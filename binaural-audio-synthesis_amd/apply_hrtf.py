@@ -164,17 +164,79 @@ def delay_compensated_interpolation_easy(irs_and_delaydiffs, continuous_index: f
 # --------------------------------------------------------------------------
 # a6
 # --------------------------------------------------------------------------
-def interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None):
+def interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=None):
     """Batched table arithmetic of interpolate_2d (apply_hrtf.py:219-279) for
     precomputed parameters: idx int32 [n,4], w float64 [n,3] (numpy or device
     tensors).  Returns a device tensor [n, 2, L] float32 (`out` if given).
-    validate=False skips the index range check (a host<->device sync)."""
+    validate=False skips the index range check (a host<->device sync).
+    gain: None, or one float64 value per query ([n]): H[q] = gain[q] interpolate_2d(q)."""
     tbl = as_device_table(tbl)
     with _hip.on_device(tbl.device):
-        return _interpolate_2d_params(tbl, idx, w, out, validate, ws)
+        return _interpolate_2d_params(tbl, idx, w, out, validate, ws, gain)
 
 
-def _interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None):
+# ---- per-source gain at chunk boundaries (DESIGN.md §3.10) -----------------------------------------------------------
+def check_gain(gain, shape):
+    """A host gain argument as a float64 numpy array of `shape`: ValueError for another shape or non-finite values."""
+    arr = np.asarray(gain.numpy() if hasattr(gain, "numpy") else gain, dtype=np.float64)
+    if arr.shape != tuple(shape):
+        raise ValueError(f"gain must have shape {tuple(shape)}, got {arr.shape}")
+    if not np.isfinite(arr).all():
+        raise ValueError("gains must be finite")
+    return arr
+
+
+def _is_device_gain(gain, shape):
+    """gain is a device tensor: checked for shape and dtype only (as device angles and heads are).  False for host data."""
+    import torch
+    if not (isinstance(gain, torch.Tensor) and gain.is_cuda):
+        return False
+    if tuple(gain.shape) != tuple(shape) or gain.dtype != torch.float64:
+        raise ValueError(f"gain must be a float64 tensor of shape {tuple(shape)}")
+    return True
+
+
+def gain_to_device(gain, shape, dev, buf=None):
+    """A gain argument as a contiguous float64 tensor of `shape` on `dev`: a contiguous device tensor on `dev` is used as
+    it is (shape and dtype checked); anything else is validated (check_gain for host data) and copied into `buf`
+    (allocated when None or of another shape).  Returns (tensor, buf)."""
+    import torch
+    shape = tuple(shape)
+    if _is_device_gain(gain, shape):
+        if gain.device == dev and gain.is_contiguous():
+            return gain, buf
+        src = gain
+    else:
+        src = torch.from_numpy(np.ascontiguousarray(check_gain(gain, shape)))
+    if buf is None or tuple(buf.shape) != shape:
+        buf = torch.empty(shape, dtype=torch.float64, device=dev)
+    buf.copy_(src)
+    return buf, buf
+
+
+def stage_gain(gain, view):
+    """Copy a gain argument into a renderer's gain view (a device tensor that is the view itself: nothing to do)."""
+    import torch
+    if _is_device_gain(gain, view.shape):
+        if gain.data_ptr() == view.data_ptr() and gain.stride() == view.stride():
+            return
+        view.copy_(gain)
+    else:
+        view.copy_(torch.from_numpy(check_gain(gain, view.shape)))
+
+
+def _flat_device_gain(gain, n_q):
+    """The gain of a device-side call: None, or a contiguous float64 device tensor of n_q values (flat view)."""
+    import torch
+    if gain is None:
+        return None
+    if not (isinstance(gain, torch.Tensor) and gain.is_cuda and gain.dtype == torch.float64 and gain.is_contiguous()
+            and gain.numel() == n_q):
+        raise ValueError(f"gain must be a contiguous float64 device tensor of {n_q} values (one per chunk boundary)")
+    return gain.reshape(-1)
+
+
+def _interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=None):
     import torch
     tbl = as_device_table(tbl)
     dev = tbl.device
@@ -189,8 +251,14 @@ def _interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None):
     ws_bytes = _hip.lib().bas_interp2d_workspace_bytes(n)
     if ws is None or ws.numel() < ws_bytes:
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    _hip.call("bas_interp2d_f32", _hip.ptr(tbl.packed), _hip.ptr(tbl.diffs), _hip.ptr(idx_t), _hip.ptr(w_t), n,
-              tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(H), _hip.ptr(ws), ws.numel(), _hip.current_stream(dev))
+    if gain is None:
+        _hip.call("bas_interp2d_f32", _hip.ptr(tbl.packed), _hip.ptr(tbl.diffs), _hip.ptr(idx_t), _hip.ptr(w_t), n,
+                  tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(H), _hip.ptr(ws), ws.numel(), _hip.current_stream(dev))
+        return H
+    g, _ = gain_to_device(gain.reshape(-1) if hasattr(gain, "reshape") else np.reshape(gain, -1), (n,), dev)
+    _hip.call("bas_interp2d_gain_f32", _hip.ptr(tbl.packed), _hip.ptr(tbl.diffs), _hip.ptr(idx_t), _hip.ptr(w_t),
+              _hip.ptr(g), n, tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(H), _hip.ptr(ws), ws.numel(),
+              _hip.current_stream(dev))
     return H
 
 
@@ -263,7 +331,7 @@ def render_device(x, chunksize, subchunksize, H, tbl_L, normalize="mix", out=Non
 @_hip.on_device_of("x")
 def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix", out=None, events=None,
                          ws=None, ws_plans=None, fused=None, angles=None, n_queries=None, want_peak=True, check=False,
-                         plans_ready=False):
+                         plans_ready=False, gain=None):
     """interpolate_2d + render for precomputed parameters: x [n_src, T_in] device float32,
     idx int32 [n_src*(n_chunks+1), 4], w float64 [.., 3] on the device.  Uses the fused kernel
     (chunk IRs evaluated inside the FIR kernel, never stored) when the sizes allow it, else
@@ -273,7 +341,9 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     their own running peak).  ws: a workspace from _hip.new_workspace (zeroed control block).  check=True: ask the
     library for device-side errors afterwards (synchronises the stream: for callers that copy the result to the host anyway).
     plans_ready=True: ws_plans already holds this scene's read plans (plan_angles_device on another stream, ordered before
-    this call by the caller): only the fused FIR is launched; needs n_queries and a shape the fused kernels serve."""
+    this call by the caller): only the fused FIR is launched; needs n_queries and a shape the fused kernels serve.
+    gain: None, or one float64 gain per query (a contiguous device tensor of n_queries values): the chunk
+    IRs become gain[q] interpolate_2d(q) (in the read plans, or in the stored IRs of the other path)."""
     import torch
     tbl = as_device_table(tbl)
     dev = x.device
@@ -287,11 +357,14 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     n_q = idx.shape[0] if idx is not None else n_queries
     if plans_ready and not fused:
         raise ValueError("plans_ready: this shape is not served by the fused kernels (they are the ones that read plans)")
+    if plans_ready and gain is not None:
+        raise ValueError("plans_ready: the gains ride in the plans (plan_angles_device(..., gain=...))")
+    gain = _flat_device_gain(gain, n_q)
     if not fused:
         if idx is None:                                       # (angles given, shape not served by the fused kernel)
             idx, w = sphere.interpolation_params_device(angles[0], angles[1], branch=angles[2])
             idx, w = idx.reshape(-1, 4), w.reshape(-1, 3)
-        H = interpolate_2d_params(tbl, idx, w, validate=False, ws=ws_plans)
+        H = interpolate_2d_params(tbl, idx, w, validate=False, ws=ws_plans, gain=gain)
         return render_device(x, chunksize, subchunksize, H.view(n_src, n_q // max(n_src, 1), 2, tbl.L), tbl.L,
                              normalize, out=out, events=events, ws=ws)
     t_out = t_in + tbl.L - 1
@@ -307,15 +380,15 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     if plans_ready:
         if ws_plans.numel() < pb:
             raise ValueError("plans_ready: ws_plans is smaller than bas_interp2d_workspace_bytes(n_queries)")
-    elif angles is None:
+    elif angles is None and gain is None:
         _hip.call("bas_interp2d_plan_f32", _hip.ptr(tbl.diffs), _hip.ptr(idx), _hip.ptr(w), n_q, tbl.ndir, tbl.L,
                   tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
+    elif angles is None:
+        _hip.call("bas_interp2d_plan_gain_f32", _hip.ptr(tbl.diffs), _hip.ptr(idx), _hip.ptr(w), _hip.ptr(gain), n_q,
+                  tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
     else:                                                     # small batch: a3 + plans in one launch
         e, z, branch = angles
-        ring_elev, ring_start, ring_count = sphere._ring_args()
-        _hip.call("bas_interp2d_plan_angles_f32", _hip.ptr(tbl.diffs), _hip.ptr(e), _hip.ptr(z), n_q, ring_elev,
-                  ring_start, ring_count, _hip.ptr(sphere.device_nodes(dev)), sphere.BRANCHES[branch], tbl.ndir, tbl.L,
-                  tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
+        _plan_angles_call(tbl, e, z, gain, n_q, branch, ws_plans, dev, stream)
     args = (_hip.ptr(x), x.stride(0), _hip.ptr(tbl.packed), _hip.ptr(ws_plans), n_src, t_in, chunksize, subchunksize, tbl.L,
             tbl.upsampling, tbl.ndir, _hip.ptr(y), 0, _hip.ptr(peak), int(normalize == "mix"), _hip.ptr(ws), ws.numel(), stream)
     if events is None:
@@ -327,12 +400,25 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     return y, peak
 
 
-def plan_angles_device(tbl, elev, azim, ws_plans, branch="f64"):
+def _plan_angles_call(tbl, elev, azim, gain, n_q, branch, ws_plans, dev, stream):
+    """a3 + read plans in one launch; with a gain (flat float64 device tensor) the gained instantiation."""
+    ring_elev, ring_start, ring_count = sphere._ring_args()
+    common = (ring_elev, ring_start, ring_count, _hip.ptr(sphere.device_nodes(dev)), sphere.BRANCHES[branch], tbl.ndir,
+              tbl.L, tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
+    if gain is None:
+        _hip.call("bas_interp2d_plan_angles_f32", _hip.ptr(tbl.diffs), _hip.ptr(elev), _hip.ptr(azim), n_q, *common)
+    else:
+        _hip.call("bas_interp2d_plan_angles_gain_f32", _hip.ptr(tbl.diffs), _hip.ptr(elev), _hip.ptr(azim),
+                  _hip.ptr(gain), n_q, *common)
+
+
+def plan_angles_device(tbl, elev, azim, ws_plans, branch="f64", gain=None):
     """The first launch of render_angles_device alone, on the current stream: trajectory angles (float64 device tensors,
     one per source and chunk boundary) -> a3 -> the fused kernels' read plans in ws_plans (uint8 device tensor of at least
     bas_interp2d_workspace_bytes(elev.numel()) bytes).  For callers that render a SEQUENCE of scenes and let the plans of
     the next one be computed beside the FIR of the current one (bench.py --overlap-plans; a rank's share of a multi-GPU
-    scene leaves CUs free): render_params_device(..., plans_ready=True) is the other half."""
+    scene leaves CUs free): render_params_device(..., plans_ready=True) is the other half.  gain: None, or a contiguous
+    float64 device tensor of one gain per angle, folded into the plans' weights."""
     import torch
     tbl = as_device_table(tbl)
     if not (elev.is_cuda and azim.is_cuda and elev.dtype == torch.float64 and azim.dtype == torch.float64
@@ -341,12 +427,10 @@ def plan_angles_device(tbl, elev, azim, ws_plans, branch="f64"):
     if branch not in sphere.BRANCHES:
         raise ValueError("branch must be 'f64' or 'pyfloat'")
     n_q, dev = elev.numel(), elev.device
+    gain = _flat_device_gain(gain, n_q)
     if ws_plans.numel() < _hip.lib().bas_interp2d_workspace_bytes(n_q):
         raise ValueError("ws_plans is smaller than bas_interp2d_workspace_bytes(n_queries)")
-    ring_elev, ring_start, ring_count = sphere._ring_args()
-    _hip.call("bas_interp2d_plan_angles_f32", _hip.ptr(tbl.diffs), _hip.ptr(elev), _hip.ptr(azim), n_q, ring_elev,
-              ring_start, ring_count, _hip.ptr(sphere.device_nodes(dev)), sphere.BRANCHES[branch], tbl.ndir, tbl.L,
-              tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), _hip.current_stream(dev))
+    _plan_angles_call(tbl, elev, azim, gain, n_q, branch, ws_plans, dev, _hip.current_stream(dev))
     return ws_plans
 
 
@@ -356,7 +440,7 @@ MERGED_A3_MAX_QUERIES = 1 << 30     # a3 rides inside the plan kernel (one launc
 
 def render_angles_device(x, chunksize, subchunksize, tbl, elev, azim, normalize="mix", out=None, events=None,
                          ws=None, ws_plans=None, fused=None, params=None, branch="f64", want_peak=True, check=False,
-                         plans_ready=False):
+                         plans_ready=False, gain=None):
     """The whole device side of make_signal_move_2d for trajectories that live on the GPU: x [n_src, T_in] device
     float32 (T_in % K == 0), elev / azim float64 device tensors [n_src, T_in/K + 1] (radians at t = 0, K, .., T_in).
     bas_traj_params_f64 (a3 + the elevation bracket), then render_params_device (read plans + fused FIR where the
@@ -365,7 +449,8 @@ def render_angles_device(x, chunksize, subchunksize, tbl, elev, azim, normalize=
     a3 runs inside the plan kernel (bas_interp2d_plan_angles_f32: one launch less, no (idx, w) round trip; round 3's form,
     in which both ears' threads redid the angle arithmetic, lost above 65 536 queries - 53 us against 9 + 15 us for 221 k;
     round 4's does it once per query: equal there, 3 us ahead for a 32-source share: tools/ab_a3_merge.py).  `params` is
-    only written by the two-launch form (MERGED_A3_MAX_QUERIES = 0)."""
+    only written by the two-launch form (MERGED_A3_MAX_QUERIES = 0).
+    gain: None, or a contiguous float64 device tensor of one gain per angle."""
     tbl = as_device_table(tbl)
     n_src, t_in = x.shape
     if elev.numel() != n_src * (t_in // chunksize + 1) or azim.numel() != elev.numel():
@@ -373,17 +458,19 @@ def render_angles_device(x, chunksize, subchunksize, tbl, elev, azim, normalize=
     import torch
     if not (elev.is_cuda and azim.is_cuda and elev.dtype == torch.float64 and azim.dtype == torch.float64):
         raise ValueError("elev/azim must be float64 device tensors")
+    gain = _flat_device_gain(gain, elev.numel())
     if elev.numel() <= MERGED_A3_MAX_QUERIES and elev.is_contiguous() and azim.is_contiguous():
         if branch not in sphere.BRANCHES:
             raise ValueError("branch must be 'f64' or 'pyfloat'")
         return render_params_device(x, chunksize, subchunksize, tbl, None, None, normalize, out=out, events=events, ws=ws,
                                     ws_plans=ws_plans, fused=fused, angles=(elev, azim, branch), n_queries=elev.numel(),
-                                    want_peak=want_peak, check=check, plans_ready=plans_ready)
+                                    want_peak=want_peak, check=check, plans_ready=plans_ready, gain=gain)
     if plans_ready:
         raise ValueError("plans_ready needs contiguous angle tensors (the merged a3 + plan launch)")
     idx, w = sphere.interpolation_params_device(elev, azim, out=params, branch=branch)
     return render_params_device(x, chunksize, subchunksize, tbl, idx.reshape(-1, 4), w.reshape(-1, 3), normalize,
-                                out=out, events=events, ws=ws, ws_plans=ws_plans, fused=fused, want_peak=want_peak, check=check)
+                                out=out, events=events, ws=ws, ws_plans=ws_plans, fused=fused, want_peak=want_peak, check=check,
+                                gain=gain)
 
 
 def _params_to_device(tbl, idx, w):
@@ -395,7 +482,7 @@ def _params_to_device(tbl, idx, w):
     return idx_t, w_t
 
 
-def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize="mix", fused=None):
+def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize="mix", fused=None, gain=None):
     """Render and mix many independently moving sources.
 
     signals: [n_src, N] (numpy or tensor); elev/azim: float64 [n_src, n_chunks+1]
@@ -404,6 +491,9 @@ def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize=
     renders, then the reference's peak rule once on the mix ("mix") or not at all
     ("none").  Returns a device tensor of shape (out_length, 2) - a transposed view of
     [2, out_length], the same memory order the reference returns (:459).
+    gain: None, or float64 [n_src, n_chunks+1], source s's gain at each chunk boundary: the chunk IR
+    there becomes gain * interpolate_2d, crossfaded per subchunk as the IRs are.  Host gains must be finite (ValueError);
+    device tensors are checked for shape and dtype only.
     """
     import torch
     tbl = as_device_table(tbl)
@@ -419,8 +509,9 @@ def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize=
     idx, w = sphere.interpolation_params_batch(elev, azim)
     if idx.shape[:-1] != (n_src, n_q):
         raise ValueError(f"elev/azim must have shape ({n_src}, {n_q})")
+    g = None if gain is None else gain_to_device(gain, (n_src, n_q), dev)[0]
     idx_t, w_t = _params_to_device(tbl, idx, w)
-    y, _ = render_params_device(x, chunksize, subchunksize, tbl, idx_t, w_t, normalize, fused=fused)
+    y, _ = render_params_device(x, chunksize, subchunksize, tbl, idx_t, w_t, normalize, fused=fused, gain=g)
     return y.t()
 
 

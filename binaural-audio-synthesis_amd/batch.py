@@ -132,7 +132,7 @@ def _all_finite(a):
 
 
 def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None, normalize="each", branch="f64",
-                 contiguous=False, check=False, max_samples=None, events=None):
+                 contiguous=False, check=False, max_samples=None, events=None, gain=None):
     """Render B independent clips in one device render, each as make_signal_move_2d renders it alone.
 
     signals: [B, N] (one source per item) or [B, n_src, N] (small scenes, mixed per item as render_sources mixes), numpy
@@ -148,16 +148,22 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
     as a transposed view of a contiguous [B, 2, T_out_max] tensor.
     check=True: ask the library for device-side errors after every render (synchronises).  max_samples: the split limit
     (default MAX_RENDER_SAMPLES).  events: four torch.cuda.Event recorded before the pack and after the pack, the render
-    and the finish (one-render batches: tools/bench_batch.py)."""
+    and the finish (one-render batches: tools/bench_batch.py).
+    gain: None, or float64 of elev's shape [B, (n_src,) n_q_max]: each source's gain at each of its item's chunk boundaries
+    (DESIGN.md §3.10); the peak rule and peaks see the gained output.  Host gains must be finite (ValueError); device
+    tensors are checked for shape and dtype only."""
     import torch
     from . import _hip, sphere
-    from .apply_hrtf import as_device_table, render_angles_device
+    from .apply_hrtf import as_device_table, render_angles_device, gain_to_device
     B, n_src, N, n = _check_args(tuple(signals.shape), lengths, tuple(np.shape(elev)), tuple(np.shape(azim)),
                                  chunksize, subchunksize, normalize)
     if branch not in sphere.BRANCHES:
         raise ValueError("branch must be 'f64' or 'pyfloat'")
     if not (_all_finite(elev) and _all_finite(azim)):
         raise ValueError("trajectory contains non-finite angles")
+    g_all = None
+    if gain is not None:                                  # (validated before any device work)
+        g_all = gain_to_device(gain, tuple(np.shape(elev)), as_device_table(tbl).device)[0].reshape(B, n_src, -1)
     K, S = int(chunksize), int(subchunksize)
     tbl = as_device_table(tbl)
     dev = tbl.device
@@ -186,16 +192,21 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
             meta = torch.from_numpy(np.stack([lay.lengths, lay.offsets, lay.out_lengths])).to(dev)   # one H2D copy
             stride = (lay.T_in + 3) // 4 * 4
             x = torch.empty((n_src, stride), dtype=torch.float32, device=dev)[:, :lay.T_in]
-            ang = torch.empty((2, n_src, lay.n_q), dtype=torch.float64, device=dev)
+            ang = torch.empty((2 if g_all is None else 3, n_src, lay.n_q), dtype=torch.float64, device=dev)
             if events is not None:
                 events[0].record()
-            _hip.call("bas_batch_pack_f32", _hip.ptr(sig[b0]), nb, n_src, N, _hip.ptr(meta[0]), _hip.ptr(meta[1]),
-                      _hip.ptr(e_all[b0]), _hip.ptr(a_all[b0]), n_q_max, K, lay.T_in, _hip.ptr(x), stride,
-                      _hip.ptr(ang[0]), _hip.ptr(ang[1]), stream)
+            if g_all is None:
+                _hip.call("bas_batch_pack_f32", _hip.ptr(sig[b0]), nb, n_src, N, _hip.ptr(meta[0]), _hip.ptr(meta[1]),
+                          _hip.ptr(e_all[b0]), _hip.ptr(a_all[b0]), n_q_max, K, lay.T_in, _hip.ptr(x), stride,
+                          _hip.ptr(ang[0]), _hip.ptr(ang[1]), stream)
+            else:
+                _hip.call("bas_batch_pack_gain_f32", _hip.ptr(sig[b0]), nb, n_src, N, _hip.ptr(meta[0]), _hip.ptr(meta[1]),
+                          _hip.ptr(e_all[b0]), _hip.ptr(a_all[b0]), _hip.ptr(g_all[b0]), n_q_max, K, lay.T_in, _hip.ptr(x),
+                          stride, _hip.ptr(ang[0]), _hip.ptr(ang[1]), _hip.ptr(ang[2]), stream)
             if events is not None:
                 events[1].record()
             y, _ = render_angles_device(x, K, S, tbl, ang[0], ang[1], normalize="none", branch=branch, want_peak=False,
-                                        check=check)
+                                        check=check, gain=None if g_all is None else ang[2])
             if events is not None:
                 events[2].record()
             _hip.call("bas_batch_finish_f32", _hip.ptr(y), y.stride(0), nb, _hip.ptr(meta[1]), _hip.ptr(meta[2]),

@@ -15,11 +15,14 @@
 // One row of workgroups per item (blockIdx.y = b): item b's segment [off_b, off_{b+1}) of every source row (the last one to
 // x_stride), 4 samples per thread (16-byte store; rows 16-byte aligned, stride a multiple of 4 floats), then the segment's
 // chunk boundaries [off_b/K, off_{b+1}/K) (the last one to n_q), one (elev, azim) pair per thread.  Every float of
-// x[s][0 .. x_stride) is written: the pad and the gaps are 0.  No search: the item is the row's.
+// x[s][0 .. x_stride) is written: the pad and the gaps are 0.  No search: the item is the row's.  GAIN: gain [B][n_src]
+// [n_q_max] is packed into gain_out like the angles.
+template <bool GAIN>
 __global__ __launch_bounds__(BB_THREADS) void bas_batch_pack_kernel(
     const float *__restrict__ sig, int n_items, int n_src, long N, const long *__restrict__ len, const long *__restrict__ off,
     const double *__restrict__ elev, const double *__restrict__ azim, long n_q_max, int K, long n_q,
-    float *__restrict__ x, long x_stride, double *__restrict__ elev_out, double *__restrict__ azim_out) {
+    float *__restrict__ x, long x_stride, double *__restrict__ elev_out, double *__restrict__ azim_out,
+    const double *__restrict__ gain, double *__restrict__ gain_out) {
     const int b0 = blockIdx.y;
     const bool last = b0 + 1 == n_items;
     const long start = off[b0], end = last ? x_stride : off[b0 + 1];
@@ -65,6 +68,7 @@ __global__ __launch_bounds__(BB_THREADS) void bas_batch_pack_kernel(
             const long src = ((long)b0 * n_src + s) * n_q_max + c;
             elev_out[(long)s * n_q + q] = elev[src];
             azim_out[(long)s * n_q + q] = azim[src];
+            if constexpr (GAIN) gain_out[(long)s * n_q + q] = gain[src];        // (filler: the item's last gain)
         }
     }
 }
@@ -167,25 +171,46 @@ static int batch_blocks_x(int n_items, long max_len) {
     return (int)want;
 }
 
+static int batch_pack(const char *who, const float *sig, int n_items, int n_src, long N, const long *lengths,
+                      const long *offsets, const double *elev, const double *azim, const double *gain, bool need_gain,
+                      long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
+                      double *gain_out, bas_stream_t stream) {
+    BAS_REQUIRE(n_items > 0 && n_src > 0 && N >= 0 && K > 0 && T_in > 0 && n_q_max > 0, BAS_E_SHAPE,
+                "%s: need n_items, n_src, K, T_in, n_q_max > 0 and N >= 0", who);
+    BAS_REQUIRE(T_in % K == 0, BAS_E_SHAPE, "%s: T_in (%ld) must be a multiple of K (%d)", who, T_in, K);
+    BAS_REQUIRE(x_stride >= T_in && x_stride % 4 == 0, BAS_E_SHAPE, "%s: x_stride must be >= T_in and a multiple of 4", who);
+    BAS_REQUIRE(lengths && offsets && elev && azim && x && elev_out && azim_out && (sig || N == 0) &&
+                    (!need_gain || (gain && gain_out)),
+                BAS_E_NULL, "%s: null pointer", who);
+    BAS_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0, BAS_E_ALIGN, "%s: x must be 16-byte aligned", who);
+    BAS_REQUIRE(n_items <= 65535, BAS_E_SHAPE, "%s: more than 65535 items in one call", who);
+    const long n_q = T_in / K + 1;
+    const dim3 grid(batch_blocks_x(n_items, n_src * ((x_stride + n_items - 1) / n_items)), n_items);
+    if (need_gain)
+        hipLaunchKernelGGL(bas_batch_pack_kernel<true>, grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items, n_src, N,
+                           lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, gain, gain_out);
+    else
+        hipLaunchKernelGGL(bas_batch_pack_kernel<false>, grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items, n_src, N,
+                           lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, nullptr, nullptr);
+    return bas_check_launch(who);
+}
+
 extern "C" int bas_batch_pack_f32(const float *sig, int n_items, int n_src, long N, const long *lengths,
                                   const long *offsets, const double *elev, const double *azim, long n_q_max, int K,
                                   long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
                                   bas_stream_t stream) {
-    BAS_REQUIRE(n_items > 0 && n_src > 0 && N >= 0 && K > 0 && T_in > 0 && n_q_max > 0, BAS_E_SHAPE,
-                "bas_batch_pack_f32: need n_items, n_src, K, T_in, n_q_max > 0 and N >= 0");
-    BAS_REQUIRE(T_in % K == 0, BAS_E_SHAPE, "bas_batch_pack_f32: T_in (%ld) must be a multiple of K (%d)", T_in, K);
-    BAS_REQUIRE(x_stride >= T_in && x_stride % 4 == 0, BAS_E_SHAPE,
-                "bas_batch_pack_f32: x_stride must be >= T_in and a multiple of 4");
-    BAS_REQUIRE(lengths && offsets && elev && azim && x && elev_out && azim_out && (sig || N == 0), BAS_E_NULL,
-                "bas_batch_pack_f32: null pointer");
-    BAS_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0, BAS_E_ALIGN, "bas_batch_pack_f32: x must be 16-byte aligned");
-    BAS_REQUIRE(n_items <= 65535, BAS_E_SHAPE, "bas_batch_pack_f32: more than 65535 items in one call");
-    const long n_q = T_in / K + 1;
-    const dim3 grid(batch_blocks_x(n_items, n_src * ((x_stride + n_items - 1) / n_items)), n_items);
-    hipLaunchKernelGGL(bas_batch_pack_kernel, grid, dim3(BB_THREADS), 0,
-                       bas_stream(stream), sig, n_items, n_src, N, lengths, offsets, elev, azim, n_q_max, K, n_q, x,
-                       x_stride, elev_out, azim_out);
-    return bas_check_launch("bas_batch_pack_f32");
+    return batch_pack("bas_batch_pack_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, nullptr, false, n_q_max, K,
+                      T_in, x, x_stride, elev_out, azim_out, nullptr, stream);
+}
+
+// apply_hrtf.py:429-447 per item with per-boundary gains: gain [B][n_src][n_q_max] -> gain_out
+// [n_src][T_in/K + 1], packed as the angles (the gap's inner boundaries repeat the item's last gain)
+extern "C" int bas_batch_pack_gain_f32(const float *sig, int n_items, int n_src, long N, const long *lengths,
+                                       const long *offsets, const double *elev, const double *azim, const double *gain,
+                                       long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out,
+                                       double *azim_out, double *gain_out, bas_stream_t stream) {
+    return batch_pack("bas_batch_pack_gain_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, gain, true, n_q_max,
+                      K, T_in, x, x_stride, elev_out, azim_out, gain_out, stream);
 }
 
 extern "C" int bas_batch_finish_f32(float *y, long y_stride, int n_items, const long *offsets, const long *out_lengths,

@@ -916,6 +916,11 @@ static int fused_impl(const char *who, int phases, const float *x, long x_stride
         if (rc) return rc;
         rule_done = !skipped && T.normalize != 0;
     } else if (carry) {
+        if (carry->gain)
+            return bas_stream_epilogue_gain_f32(carry->x, carry->x_stride, carry->n_src, carry->halo, carry->B, carry->elev,
+                                                carry->azim, carry->gain, carry->ang_stride, carry->nh, carry->nb, carry->last,
+                                                carry->gain_last, y, T_out, reinterpret_cast<float *>(carry->running_peak),
+                                                stream);
         return bas_stream_epilogue_f32(carry->x, carry->x_stride, carry->n_src, carry->halo, carry->B, carry->elev, carry->azim,
                                        carry->ang_stride, carry->nh, carry->nb, carry->last, y, T_out,
                                        reinterpret_cast<float *>(carry->running_peak), stream);
@@ -961,17 +966,19 @@ extern "C" int bas_render_fused_reduce_f32(const float *x, long x_stride, const 
 static int stream_block_impl(const char *who, float *x, long x_stride, const float *packed, const void *plans, int n_src,
                              long T_in, int K, int S, int L, int U, int ndir, float *y, void *ws, size_t ws_bytes, int halo,
                              double *elev, double *azim, long ang_stride, int nh, int nb, double *last, float *running_peak,
-                             bas_stream_t stream, void *ev_begin, void *ev_end) {
+                             bas_stream_t stream, void *ev_begin, void *ev_end, double *gain = nullptr,
+                             double *gain_last = nullptr, bool need_gain = false) {
     const long B = T_in - halo;
     BAS_REQUIRE(n_src > 0 && halo >= 0 && B > 0 && nh >= 0 && nb >= 2, BAS_E_SHAPE,
                 "%s: need n_src>0, halo>=0, T_in>halo, nh>=0, nb>=2 (n_src=%d halo=%d T_in=%ld nh=%d nb=%d)", who, n_src, halo,
                 T_in, nh, nb);
     BAS_REQUIRE(ang_stride >= nh + nb, BAS_E_SHAPE, "%s: ang_stride shorter than nh + nb", who);
-    BAS_REQUIRE(x && elev && azim && last, BAS_E_NULL, "%s: null pointer", who);
+    BAS_REQUIRE(x && elev && azim && last && (!need_gain || (gain && gain_last)), BAS_E_NULL, "%s: null pointer", who);
     BasCarry C;
     C.x = x; C.x_stride = x_stride; C.n_src = n_src; C.halo = halo; C.B = B;
     C.elev = elev; C.azim = azim; C.ang_stride = ang_stride; C.nh = nh; C.nb = nb; C.last = last;
     C.running_peak = reinterpret_cast<unsigned int *>(running_peak);
+    C.gain = gain; C.gain_last = gain_last;
     return fused_impl(who, 3, x, x_stride, packed, plans, n_src, T_in, K, S, L, U, ndir, y, 0, nullptr, 0, ws, ws_bytes, stream,
                       ev_begin, ev_end, &C);
 }
@@ -992,4 +999,16 @@ extern "C" int bas_render_stream_block_profiled_f32(float *x, long x_stride, con
     return stream_block_impl("bas_render_stream_block_profiled_f32", x, x_stride, packed, plans, n_src, T_in, K, S, L, U, ndir,
                              y, ws, ws_bytes, halo, elev, azim, ang_stride, nh, nb, last, running_peak, stream, ev_begin,
                              ev_end);
+}
+
+// apply_hrtf.py:429-447 for a stream whose plans carry per-boundary gains (bas_interp2d_plan_angles_gain_f32): the render
+// itself is unchanged; the gains of the halo boundaries move to the front with the angles, gain_last[s] = gain[s][nh+nb-1]
+extern "C" int bas_render_stream_block_gain_f32(float *x, long x_stride, const float *packed, const void *plans, int n_src,
+                                                long T_in, int K, int S, int L, int U, int ndir, float *y, void *ws,
+                                                size_t ws_bytes, int halo, double *elev, double *azim, double *gain,
+                                                long ang_stride, int nh, int nb, double *last, double *gain_last,
+                                                float *running_peak, bas_stream_t stream) {
+    return stream_block_impl("bas_render_stream_block_gain_f32", x, x_stride, packed, plans, n_src, T_in, K, S, L, U, ndir, y,
+                             ws, ws_bytes, halo, elev, azim, ang_stride, nh, nb, last, running_peak, stream, nullptr, nullptr,
+                             gain, gain_last, true);
 }

@@ -34,6 +34,8 @@ struct BasCarry {
     int nh, nb;
     double *last;               // [2][n_src]: the angles at the block's end
     unsigned int *running_peak; // max|y| bits over the samples emitted so far (may be null)
+    double *gain;               // [n_src] rows of nh + nb gains at the angles' stride (null: no gain row)
+    double *gain_last;          // [n_src]: the gain at the block's end (with gain)
 };
 int bas_launch_slab_reduce(const float *slab, int tile, int n_src, int units_per_wg, int parts_per_wg, int n_wg,
                            long T_out, float *y, int accumulate, unsigned int *peak_bits, const BasTail *tail,
@@ -135,6 +137,11 @@ __device__ __forceinline__ void bas_carry_moves(const BasCarry &C, long tid, lon
         for (int j = 0; j < nh; ++j) {                       // ascending: source index nb - 1 + j > j
             e[j] = e[nb - 1 + j];
             a[j] = a[nb - 1 + j];
+        }
+        if (C.gain) {                                        // the gains of the same boundaries, as the angles
+            double *g = C.gain + s * C.ang_stride;
+            C.gain_last[s] = g[nh + nb - 1];
+            for (int j = 0; j < nh; ++j) g[j] = g[nb - 1 + j];
         }
     }
 }

@@ -260,13 +260,17 @@ struct PlanAngles {
 
 #define BAS_PLAN_WAVE_STAGED_FROM 32768   // queries from which the plan kernel stages its records per wave (see its end)
 
-// plan kernel: one thread per (query, ear)
-template <int ANG, int WAVE_STAGED = 0>
+// plan kernel: one thread per (query, ear).  GAIN: the chunk IR of query q is gain[q] times the
+// interpolated one - every one of the 16 weights is multiplied by gain[q] in binary64 and rounded to binary32 once (the
+// crossfade of apply_hrtf.py:443 then runs between gained IRs unchanged).  `gain` is the last argument so that the
+// GAIN = false instantiations read their other arguments at the same offsets as before and never touch it.
+template <int ANG, int WAVE_STAGED = 0, bool GAIN = false>
 __global__ __launch_bounds__(256) void bas_interp2d_plan_kernel(const double *__restrict__ diffs,
                                                                   const int32_t *__restrict__ idx,
                                                                   const double *__restrict__ w, int n,
                                                                   int ndir, int L, int U,
-                                                                  EarPlanS *__restrict__ plans, PlanAngles PA) {
+                                                                  EarPlanS *__restrict__ plans, PlanAngles PA,
+                                                                  const double *__restrict__ gain) {
     long t = blockIdx.x * 256L + threadIdx.x;
     if (t >= 2L * n) t = 2L * n - 1;                         // (idle threads of the last block redo its last record: barrier below)
     const long q = t >> 1;
@@ -340,7 +344,15 @@ __global__ __launch_bounds__(256) void bas_interp2d_plan_kernel(const double *__
             }
         }
     }
-    // fold the blend chain into 16 weights (apply_hrtf.py:90-91, :98-99, :268-269, :276-277)
+    // fold the blend chain into 16 weights (apply_hrtf.py:90-91, :98-99, :268-269, :276-277).  With GAIN the product of
+    // each finished binary64 weight and the query's gain is rounded once; the multiply follows the weight's last addition,
+    // so no contraction can fuse it into the chain (gain = 1 gives the GAIN = false weights bit for bit: tested).
+    double gq = 1.0;
+    if constexpr (GAIN) gq = gain[q];                                        // g_k H_k (apply_hrtf.py:435)
+    auto wt32 = [gq](double v) -> float {
+        if constexpr (GAIN) return (float)(v * gq);
+        else return (float)v;
+    };
     const double cC[2] = {1.0 - (double)f4, (double)f4};
     double wrb[3], wbb[4], wbt[3];
     {
@@ -350,24 +362,24 @@ __global__ __launch_bounds__(256) void bas_interp2d_plan_kernel(const double *__
         wbb[0] = wrb[0] * (1.0 - h); wbb[1] = wrb[0] * h + wrb[1] * (1.0 - h);
         wbb[2] = wrb[1] * h + wrb[2] * (1.0 - h); wbb[3] = wrb[2] * h;
         const double kk = (double)bot.f1;
-        ps.w[0] = (float)(ab * wbb[0] * (1.0 - kk));
-        ps.w[1] = (float)(ab * (wbb[0] * kk + wbb[1] * (1.0 - kk)));
-        ps.w[2] = (float)(ab * (wbb[1] * kk + wbb[2] * (1.0 - kk)));
-        ps.w[3] = (float)(ab * (wbb[2] * kk + wbb[3] * (1.0 - kk)));
-        ps.w[4] = (float)(ab * wbb[3] * kk);
+        ps.w[0] = wt32(ab * wbb[0] * (1.0 - kk));
+        ps.w[1] = wt32(ab * (wbb[0] * kk + wbb[1] * (1.0 - kk)));
+        ps.w[2] = wt32(ab * (wbb[1] * kk + wbb[2] * (1.0 - kk)));
+        ps.w[3] = wt32(ab * (wbb[2] * kk + wbb[3] * (1.0 - kk)));
+        ps.w[4] = wt32(ab * wbb[3] * kk);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ps.w[5 + j] = (float)((1.0 - ab) * wbb[j]);
+        for (int j = 0; j < 4; ++j) ps.w[5 + j] = wt32((1.0 - ab) * wbb[j]);
     }
     {
         const double r0 = a * cC[0], r1 = a * cC[1], h = (double)top.f2;
         wbt[0] = r0 * (1.0 - h); wbt[1] = r0 * h + r1 * (1.0 - h); wbt[2] = r1 * h;
         const double kk = (double)top.f1;
-        ps.w[9] = (float)(at * wbt[0] * (1.0 - kk));
-        ps.w[10] = (float)(at * (wbt[0] * kk + wbt[1] * (1.0 - kk)));
-        ps.w[11] = (float)(at * (wbt[1] * kk + wbt[2] * (1.0 - kk)));
-        ps.w[12] = (float)(at * wbt[2] * kk);
+        ps.w[9] = wt32(at * wbt[0] * (1.0 - kk));
+        ps.w[10] = wt32(at * (wbt[0] * kk + wbt[1] * (1.0 - kk)));
+        ps.w[11] = wt32(at * (wbt[1] * kk + wbt[2] * (1.0 - kk)));
+        ps.w[12] = wt32(at * wbt[2] * kk);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) ps.w[13 + j] = (float)((1.0 - at) * wbt[j]);
+        for (int j = 0; j < 3; ++j) ps.w[13 + j] = wt32((1.0 - at) * wbt[j]);
     }
     // 144-byte records written lane by lane would touch every 64-byte segment two or three times: the block's records go
     // through LDS (stride 37 words: conflict-free) and leave as one contiguous run of 16-byte stores
@@ -486,13 +498,15 @@ __global__ __launch_bounds__(256) void bas_interp2d_eval_kernel(const float *__r
 // Any upsampling factor: the planned evaluation above steps through up to five consecutive upsampled
 // positions with "previous plane, or plane + U one sample earlier" (bas_plan.h), which needs U >= 4.  Tables
 // with U = 1, 2, 3 (the reference accepts any factor, apply_hrtf.py:38) take this plain form instead: one
-// thread per output tap, every table sample addressed through tab_read's general position arithmetic.
+// thread per output tap, every table sample addressed through tab_read's general position arithmetic.  GAIN: the tap is
+// multiplied by the query's gain in binary64 and rounded once (these tables have no plans to carry it).
+template <bool GAIN>
 __global__ __launch_bounds__(256) void bas_interp2d_generic_kernel(const float *__restrict__ packed,
                                                                      const double *__restrict__ diffs,
                                                                      const int32_t *__restrict__ idx,
                                                                      const double *__restrict__ w, long n,
                                                                      int ndir, int L, int U,
-                                                                     float *__restrict__ H) {
+                                                                     float *__restrict__ H, const double *__restrict__ gain) {
     const int M = L * U;
     const long total = n * 2 * L;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
@@ -525,7 +539,9 @@ __global__ __launch_bounds__(256) void bas_interp2d_generic_kernel(const float *
             const float sb = (1.0f - f3) * rb[j] + f3 * rb[j + 1];                    // S(R_b, -Dv)
             c[j] = (1.0f - af) * sb + af * rt[j];                                      // :268-269
         }
-        H[i] = (1.0f - f4) * c[0] + f4 * c[1];                                         // :276-277
+        const float h = (1.0f - f4) * c[0] + f4 * c[1];                                // :276-277
+        if constexpr (GAIN) H[i] = (float)((double)h * gain[q]);
+        else H[i] = h;
     }
 }
 
@@ -535,45 +551,64 @@ extern "C" size_t bas_interp2d_workspace_bytes(int n) {
     return n > 0 ? (size_t)n * 2 * sizeof(EarPlanS) + 16 : 16;
 }
 
-extern "C" int bas_interp2d_plan_f32(const double *diffs, const int32_t *idx, const double *w, int n, int ndir,
-                                     int L, int U, void *plans, size_t plans_bytes, bas_stream_t stream) {
-    BAS_REQUIRE(diffs && ((idx && w) || n == 0), BAS_E_NULL, "bas_interp2d_plan_f32: null pointer");   // (no queries: idx, w may be null)
+// the plan kernel for a batch of n queries: per-wave staging from BAS_PLAN_WAVE_STAGED_FROM queries on, GAIN when `gain` is
+// given (the gain-less launches pick exactly the instantiations they always did)
+typedef void (*plan_fn)(const double *, const int32_t *, const double *, int, int, int, int, EarPlanS *, PlanAngles,
+                        const double *);
+template <int ANG>
+static plan_fn plan_kernel_for(int n, const double *gain) {
+    const bool big = n >= BAS_PLAN_WAVE_STAGED_FROM;
+    if (gain) return big ? bas_interp2d_plan_kernel<ANG, 1, true> : bas_interp2d_plan_kernel<ANG, 0, true>;
+    return big ? bas_interp2d_plan_kernel<ANG, 1, false> : bas_interp2d_plan_kernel<ANG, 0, false>;
+}
+
+// bas_interp2d_plan_f32 / bas_interp2d_plan_gain_f32 (gain == null: the former)
+static int plan_impl(const char *who, const double *diffs, const int32_t *idx, const double *w, const double *gain,
+                     bool need_gain, int n, int ndir, int L, int U, void *plans, size_t plans_bytes, bas_stream_t stream) {
+    BAS_REQUIRE(diffs && ((idx && w && (gain || !need_gain)) || n == 0), BAS_E_NULL, "%s: null pointer", who);   // (no queries: idx, w may be null)
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U > 0, BAS_E_SHAPE,
-                "bas_interp2d_plan_f32: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", n, ndir, L, U);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "bas_interp2d_plan_f32: table too large");
+                "%s: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", who, n, ndir, L, U);
+    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "%s: table too large", who);
     BAS_REQUIRE(U >= BAS_PLAN_MIN_U, BAS_E_SHAPE,
-                "bas_interp2d_plan_f32: read plans need an upsampling factor >= %d (U=%d): use bas_interp2d_f32",
-                BAS_PLAN_MIN_U, U);
+                "%s: read plans need an upsampling factor >= %d (U=%d): use bas_interp2d_f32", who, BAS_PLAN_MIN_U, U);
     if (n == 0) return 0;
     BAS_REQUIRE(plans && plans_bytes >= bas_interp2d_workspace_bytes(n) &&
                     reinterpret_cast<uintptr_t>(plans) % 16 == 0,
-                BAS_E_WORKSPACE, "bas_interp2d_plan_f32: 16-byte aligned buffer of %zu bytes needed, %zu given",
+                BAS_E_WORKSPACE, "%s: 16-byte aligned buffer of %zu bytes needed, %zu given", who,
                 bas_interp2d_workspace_bytes(n), plans_bytes);
     const long rows = 2L * n;
-    if (n >= BAS_PLAN_WAVE_STAGED_FROM)
-        hipLaunchKernelGGL((bas_interp2d_plan_kernel<0, 1>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                           bas_stream(stream), diffs, idx, w, n, ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PlanAngles{});
-    else
-        hipLaunchKernelGGL((bas_interp2d_plan_kernel<0, 0>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                           bas_stream(stream), diffs, idx, w, n, ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PlanAngles{});
-    return bas_check_launch("bas_interp2d_plan_f32");
+    hipLaunchKernelGGL(plan_kernel_for<0>(n, gain), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, bas_stream(stream),
+                       diffs, idx, w, n, ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PlanAngles{}, gain);
+    return bas_check_launch(who);
 }
 
-extern "C" int bas_interp2d_plan_angles_f32(const double *diffs, const double *elev, const double *azim, int n,
-                                            const double *ring_elev, const int32_t *ring_start,
-                                            const int32_t *ring_count, const float *node_az, int branch, int ndir,
-                                            int L, int U, void *plans, size_t plans_bytes, bas_stream_t stream) {
-    BAS_REQUIRE(diffs && ring_elev && ring_start && ring_count && node_az && ((elev && azim) || n == 0), BAS_E_NULL,
-                "bas_interp2d_plan_angles_f32: null pointer");
+extern "C" int bas_interp2d_plan_f32(const double *diffs, const int32_t *idx, const double *w, int n, int ndir,
+                                     int L, int U, void *plans, size_t plans_bytes, bas_stream_t stream) {
+    return plan_impl("bas_interp2d_plan_f32", diffs, idx, w, nullptr, false, n, ndir, L, U, plans, plans_bytes, stream);
+}
+
+// apply_hrtf.py:429-447 with the chunk IR at boundary q scaled by gain[q]
+extern "C" int bas_interp2d_plan_gain_f32(const double *diffs, const int32_t *idx, const double *w, const double *gain,
+                                          int n, int ndir, int L, int U, void *plans, size_t plans_bytes,
+                                          bas_stream_t stream) {
+    return plan_impl("bas_interp2d_plan_gain_f32", diffs, idx, w, gain, true, n, ndir, L, U, plans, plans_bytes, stream);
+}
+
+static int plan_angles_impl(const char *who, const double *diffs, const double *elev, const double *azim,
+                            const double *gain, bool need_gain, int n, const double *ring_elev, const int32_t *ring_start,
+                            const int32_t *ring_count, const float *node_az, int branch, int ndir, int L, int U,
+                            void *plans, size_t plans_bytes, bas_stream_t stream) {
+    BAS_REQUIRE(diffs && ring_elev && ring_start && ring_count && node_az &&
+                    ((elev && azim && (gain || !need_gain)) || n == 0),
+                BAS_E_NULL, "%s: null pointer", who);
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U >= BAS_PLAN_MIN_U, BAS_E_SHAPE,
-                "bas_interp2d_plan_angles_f32: need n>=0, ndir>0, L>0, U>=%d (n=%d ndir=%d L=%d U=%d)", BAS_PLAN_MIN_U, n,
-                ndir, L, U);
+                "%s: need n>=0, ndir>0, L>0, U>=%d (n=%d ndir=%d L=%d U=%d)", who, BAS_PLAN_MIN_U, n, ndir, L, U);
     BAS_REQUIRE(branch == BAS_BRANCH_F64 || branch == BAS_BRANCH_PYFLOAT, BAS_E_SHAPE,
-                "bas_interp2d_plan_angles_f32: branch must be BAS_BRANCH_F64 (0) or BAS_BRANCH_PYFLOAT (1), got %d", branch);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "bas_interp2d_plan_angles_f32: table too large");
+                "%s: branch must be BAS_BRANCH_F64 (0) or BAS_BRANCH_PYFLOAT (1), got %d", who, branch);
+    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "%s: table too large", who);
     if (n == 0) return 0;
     BAS_REQUIRE(plans && plans_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(plans) % 16 == 0,
-                BAS_E_WORKSPACE, "bas_interp2d_plan_angles_f32: 16-byte aligned buffer of %zu bytes needed, %zu given",
+                BAS_E_WORKSPACE, "%s: 16-byte aligned buffer of %zu bytes needed, %zu given", who,
                 bas_interp2d_workspace_bytes(n), plans_bytes);
     PlanAngles PA;
     PA.elev = elev; PA.azim = azim; PA.node_az = node_az;
@@ -582,53 +617,87 @@ extern "C" int bas_interp2d_plan_angles_f32(const double *diffs, const double *e
         PA.R.ring_start[i] = ring_start[i];
         PA.R.ring_count[i] = ring_count[i];
         BAS_REQUIRE(PA.R.ring_count[i] > 0 && PA.R.ring_start[i] >= 0 && PA.R.ring_start[i] + PA.R.ring_count[i] <= ndir,
-                    BAS_E_SHAPE, "bas_interp2d_plan_angles_f32: ring %d out of the %d-direction table", i, ndir);
+                    BAS_E_SHAPE, "%s: ring %d out of the %d-direction table", who, i, ndir);
     }
     const long rows = 2L * n;
-    typedef void (*plan_fn)(const double *, const int32_t *, const double *, int, int, int, int, EarPlanS *, PlanAngles);
-    const bool big = n >= BAS_PLAN_WAVE_STAGED_FROM;
-    const plan_fn fn = branch == BAS_BRANCH_PYFLOAT ? (big ? bas_interp2d_plan_kernel<2, 1> : bas_interp2d_plan_kernel<2, 0>)
-                                                    : (big ? bas_interp2d_plan_kernel<1, 1> : bas_interp2d_plan_kernel<1, 0>);
+    const plan_fn fn = branch == BAS_BRANCH_PYFLOAT ? plan_kernel_for<2>(n, gain) : plan_kernel_for<1>(n, gain);
     hipLaunchKernelGGL(fn, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, bas_stream(stream), diffs, nullptr, nullptr, n,
-                       ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PA);
-    return bas_check_launch("bas_interp2d_plan_angles_f32");
+                       ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PA, gain);
+    return bas_check_launch(who);
 }
 
-extern "C" int bas_interp2d_f32(const float *packed, const double *diffs, const int32_t *idx,
-                                const double *w, int n, int ndir, int L, int U, float *H, void *ws,
-                                size_t ws_bytes, bas_stream_t stream) {
-    BAS_REQUIRE(packed && diffs && ((idx && w && H) || n == 0), BAS_E_NULL, "bas_interp2d_f32: null pointer");   // (no queries: idx, w, H may be null)
+extern "C" int bas_interp2d_plan_angles_f32(const double *diffs, const double *elev, const double *azim, int n,
+                                            const double *ring_elev, const int32_t *ring_start,
+                                            const int32_t *ring_count, const float *node_az, int branch, int ndir,
+                                            int L, int U, void *plans, size_t plans_bytes, bas_stream_t stream) {
+    return plan_angles_impl("bas_interp2d_plan_angles_f32", diffs, elev, azim, nullptr, false, n, ring_elev, ring_start,
+                            ring_count, node_az, branch, ndir, L, U, plans, plans_bytes, stream);
+}
+
+// apply_hrtf.py:429-447 with the chunk IR at boundary q scaled by gain[q]
+extern "C" int bas_interp2d_plan_angles_gain_f32(const double *diffs, const double *elev, const double *azim,
+                                                 const double *gain, int n, const double *ring_elev,
+                                                 const int32_t *ring_start, const int32_t *ring_count, const float *node_az,
+                                                 int branch, int ndir, int L, int U, void *plans, size_t plans_bytes,
+                                                 bas_stream_t stream) {
+    return plan_angles_impl("bas_interp2d_plan_angles_gain_f32", diffs, elev, azim, gain, true, n, ring_elev, ring_start,
+                            ring_count, node_az, branch, ndir, L, U, plans, plans_bytes, stream);
+}
+
+static int interp2d_impl(const char *who, const float *packed, const double *diffs, const int32_t *idx, const double *w,
+                         const double *gain, bool need_gain, int n, int ndir, int L, int U, float *H, void *ws,
+                         size_t ws_bytes, bas_stream_t stream) {
+    BAS_REQUIRE(packed && diffs && ((idx && w && H && (gain || !need_gain)) || n == 0), BAS_E_NULL, "%s: null pointer",
+                who);   // (no queries: idx, w, H may be null)
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U > 0, BAS_E_SHAPE,
-                "bas_interp2d_f32: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", n, ndir, L, U);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "bas_interp2d_f32: table too large");
+                "%s: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", who, n, ndir, L, U);
+    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "%s: table too large", who);
     if (n == 0) return 0;
     BAS_REQUIRE(ws && ws_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
-                BAS_E_WORKSPACE, "bas_interp2d_f32: 16-byte aligned workspace of %zu bytes needed, %zu given",
+                BAS_E_WORKSPACE, "%s: 16-byte aligned workspace of %zu bytes needed, %zu given", who,
                 bas_interp2d_workspace_bytes(n), ws_bytes);
     EarPlanS *plans = reinterpret_cast<EarPlanS *>(ws);
     hipStream_t st = bas_stream(stream);
     const long rows = 2L * n;
+    char what[96];
     if (U < BAS_PLAN_MIN_U) {                                // small upsampling factors: plain evaluation
         long blocks = ((long)n * 2 * L + 255) / 256;
         if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(bas_interp2d_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, packed, diffs, idx,
-                           w, (long)n, ndir, L, U, H);
-        return bas_check_launch("bas_interp2d_f32(generic)");
+        if (gain)
+            hipLaunchKernelGGL(bas_interp2d_generic_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, packed, diffs,
+                               idx, w, (long)n, ndir, L, U, H, gain);
+        else
+            hipLaunchKernelGGL(bas_interp2d_generic_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, packed, diffs,
+                               idx, w, (long)n, ndir, L, U, H, gain);
+        snprintf(what, sizeof what, "%s(generic)", who);
+        return bas_check_launch(what);
     }
-    if (n >= BAS_PLAN_WAVE_STAGED_FROM)
-        hipLaunchKernelGGL((bas_interp2d_plan_kernel<0, 1>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, diffs, idx,
-                           w, n, ndir, L, U, plans, PlanAngles{});
-    else
-        hipLaunchKernelGGL((bas_interp2d_plan_kernel<0, 0>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, diffs, idx,
-                           w, n, ndir, L, U, plans, PlanAngles{});
-    int rc = bas_check_launch("bas_interp2d_f32(plan)");
+    hipLaunchKernelGGL(plan_kernel_for<0>(n, gain), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, diffs, idx, w, n,
+                       ndir, L, U, plans, PlanAngles{}, gain);
+    snprintf(what, sizeof what, "%s(plan)", who);
+    int rc = bas_check_launch(what);
     if (rc) return rc;
     long blocks = ((long)n + 3) / 4;
     if (blocks > 16384) blocks = 16384;
     const unsigned table_bytes = (unsigned)((size_t)2 * ndir * U * BAS_PLANE(L) * sizeof(float));
     hipLaunchKernelGGL(bas_interp2d_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, st, packed, table_bytes, plans,
                        (long)n, L, H);
-    return bas_check_launch("bas_interp2d_f32(eval)");
+    snprintf(what, sizeof what, "%s(eval)", who);
+    return bas_check_launch(what);
+}
+
+extern "C" int bas_interp2d_f32(const float *packed, const double *diffs, const int32_t *idx,
+                                const double *w, int n, int ndir, int L, int U, float *H, void *ws,
+                                size_t ws_bytes, bas_stream_t stream) {
+    return interp2d_impl("bas_interp2d_f32", packed, diffs, idx, w, nullptr, false, n, ndir, L, U, H, ws, ws_bytes, stream);
+}
+
+// apply_hrtf.py:429-447: the stored chunk IRs H[q] = gain[q] interpolate_2d(q)
+extern "C" int bas_interp2d_gain_f32(const float *packed, const double *diffs, const int32_t *idx, const double *w,
+                                     const double *gain, int n, int ndir, int L, int U, float *H, void *ws,
+                                     size_t ws_bytes, bas_stream_t stream) {
+    return interp2d_impl("bas_interp2d_gain_f32", packed, diffs, idx, w, gain, true, n, ndir, L, U, H, ws, ws_bytes,
+                         stream);
 }
 
 // ---------------------------------------------------------------------------

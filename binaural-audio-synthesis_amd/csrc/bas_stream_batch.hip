@@ -24,11 +24,13 @@ __device__ __forceinline__ bool sb_aligned16(const void *p) { return (reinterpre
 // of nb (elev, azim) pairs.  A quad moves as one 16-byte load and store when both rows are 16-byte aligned and B % 4 == 0
 // (every quad of the row then is), else as up to 4 scalars (still coalesced across a wave).  HEAD: the angles are world-frame
 // and head [G][nb][4] holds session g's orientation at each boundary; the slots get bas_head_relative's angles.
-template <bool HEAD>
+// GAIN: gain [G][n_src][nb] goes into gain_out's slots beside the angles, in the same launch.
+template <bool HEAD, bool GAIN>
 __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
     const float *__restrict__ blocks, const double *__restrict__ elev, const double *__restrict__ azim, int n_src,
     long B, long W, int halo, int nh, int nb, float *__restrict__ x, long x_stride, double *__restrict__ elev_out,
-    double *__restrict__ azim_out, long ang_stride, const double *__restrict__ head) {
+    double *__restrict__ azim_out, long ang_stride, const double *__restrict__ head, const double *__restrict__ gain,
+    double *__restrict__ gain_out) {
     const int g = blockIdx.y;
     const long nq = (B + 3) >> 2;
     const long n_x = (long)n_src * nq, n_items = n_x + (long)n_src * nb;
@@ -60,6 +62,7 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
                 elev_out[to] = elev[from];
                 azim_out[to] = azim[from];
             }
+            if constexpr (GAIN) gain_out[to] = gain[from];
         }
     }
 }
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
 __global__ __launch_bounds__(SB_THREADS) void bas_stream_block_epilogue_kernel(
     float *__restrict__ x, long x_stride, int n_src, int halo, long B, long W, double *__restrict__ elev,
     double *__restrict__ azim, long ang_stride, int nh, int nb, double *__restrict__ last, const float *__restrict__ y,
-    long y_stride, unsigned int *__restrict__ peak_bits) {
+    long y_stride, unsigned int *__restrict__ peak_bits, double *__restrict__ gain, double *__restrict__ gain_last) {
     const int g = blockIdx.y;
     const long tid = blockIdx.x * (long)SB_THREADS + threadIdx.x;
     const long nthreads = (long)gridDim.x * SB_THREADS;
@@ -94,6 +97,8 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_block_epilogue_kernel(
     C.x = x + (long)g * W; C.x_stride = x_stride; C.n_src = n_src; C.halo = halo; C.B = B;
     C.elev = elev + (long)g * (nh + nb); C.azim = azim + (long)g * (nh + nb); C.ang_stride = ang_stride;
     C.nh = nh; C.nb = nb; C.last = last + 2L * n_src * g; C.running_peak = nullptr;
+    C.gain = gain ? gain + (long)g * (nh + nb) : nullptr;      // (null: no gain row, as before)
+    C.gain_last = gain ? gain_last + (long)n_src * g : nullptr;
     bas_carry_moves(C, tid, nthreads);
 }
 
@@ -122,68 +127,116 @@ static int sb_check_layout(const char *what, int n_sessions, int n_src, long B, 
     return 0;
 }
 
-// both pack entry points: the layout checks, the pointers (head only with HEAD), one launch
-template <bool HEAD>
+// every pack entry point: the layout checks, the pointers (head only with HEAD, gain and gain_out only with GAIN), one launch
+template <bool HEAD, bool GAIN>
 static int sb_pack(const char *what, const float *blocks, const double *elev, const double *azim, const double *head,
-                   int n_sessions, int n_src, long B, int K, int halo, float *x, long x_stride, double *elev_out,
-                   double *azim_out, long ang_stride, bas_stream_t stream) {
+                   const double *gain, int n_sessions, int n_src, long B, int K, int halo, float *x, long x_stride,
+                   double *elev_out, double *azim_out, double *gain_out, long ang_stride, bas_stream_t stream) {
     int rc = sb_check_layout(what, n_sessions, n_src, B, K, halo, x_stride, ang_stride);
     if (rc) return rc;
-    BAS_REQUIRE(blocks && elev && azim && (!HEAD || head) && x && elev_out && azim_out, BAS_E_NULL, "%s: null pointer",
-                what);
+    BAS_REQUIRE(blocks && elev && azim && (!HEAD || head) && (!GAIN || (gain && gain_out)) && x && elev_out && azim_out,
+                BAS_E_NULL, "%s: null pointer", what);
     const long W = halo + B + K;
     const int nh = halo / K, nb = (int)(B / K + 1);
     const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
-    hipLaunchKernelGGL(bas_stream_batch_pack_kernel<HEAD>, grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks, elev,
-                       azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head);
+    hipLaunchKernelGGL((bas_stream_batch_pack_kernel<HEAD, GAIN>), grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks,
+                       elev, azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head, gain,
+                       gain_out);
     return bas_check_launch(what);
 }
 
 extern "C" int bas_stream_batch_pack_f32(const float *blocks, const double *elev, const double *azim, int n_sessions,
                                          int n_src, long B, int K, int halo, float *x, long x_stride, double *elev_out,
                                          double *azim_out, long ang_stride, bas_stream_t stream) {
-    return sb_pack<false>("bas_stream_batch_pack_f32", blocks, elev, azim, nullptr, n_sessions, n_src, B, K, halo, x,
-                          x_stride, elev_out, azim_out, ang_stride, stream);
+    return sb_pack<false, false>("bas_stream_batch_pack_f32", blocks, elev, azim, nullptr, nullptr, n_sessions, n_src, B, K,
+                                 halo, x, x_stride, elev_out, azim_out, nullptr, ang_stride, stream);
 }
 
 extern "C" int bas_stream_batch_pack_head_f32(const float *blocks, const double *elev, const double *azim,
                                               const double *head, int n_sessions, int n_src, long B, int K, int halo,
                                               float *x, long x_stride, double *elev_out, double *azim_out, long ang_stride,
                                               bas_stream_t stream) {
-    return sb_pack<true>("bas_stream_batch_pack_head_f32", blocks, elev, azim, head, n_sessions, n_src, B, K, halo, x,
-                         x_stride, elev_out, azim_out, ang_stride, stream);
+    return sb_pack<true, false>("bas_stream_batch_pack_head_f32", blocks, elev, azim, head, nullptr, n_sessions, n_src, B, K,
+                                halo, x, x_stride, elev_out, azim_out, nullptr, ang_stride, stream);
 }
 
-extern "C" int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
-                                             double *elev, double *azim, long ang_stride, double *last, const float *y,
-                                             long y_stride, float *peaks, bas_stream_t stream) {
-    int rc = sb_check_layout("bas_stream_batch_epilogue_f32", n_sessions, n_src, B, K, halo, x_stride, ang_stride);
+// apply_hrtf.py:429-447 per session with per-boundary gains: the pack with gain [G][n_src][nb] ->
+// gain_out[s][g (nh + nb) + nh + c]; head may be null (head-relative angles, as bas_stream_batch_pack_f32)
+extern "C" int bas_stream_batch_pack_gain_f32(const float *blocks, const double *elev, const double *azim,
+                                              const double *head, const double *gain, int n_sessions, int n_src, long B,
+                                              int K, int halo, float *x, long x_stride, double *elev_out, double *azim_out,
+                                              double *gain_out, long ang_stride, bas_stream_t stream) {
+    if (head)
+        return sb_pack<true, true>("bas_stream_batch_pack_gain_f32", blocks, elev, azim, head, gain, n_sessions, n_src, B, K,
+                                   halo, x, x_stride, elev_out, azim_out, gain_out, ang_stride, stream);
+    return sb_pack<false, true>("bas_stream_batch_pack_gain_f32", blocks, elev, azim, nullptr, gain, n_sessions, n_src, B, K,
+                                halo, x, x_stride, elev_out, azim_out, gain_out, ang_stride, stream);
+}
+
+static int sb_epilogue(const char *what, float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
+                       double *elev, double *azim, double *gain, long ang_stride, double *last, double *gain_last,
+                       bool need_gain, const float *y, long y_stride, float *peaks, bas_stream_t stream) {
+    int rc = sb_check_layout(what, n_sessions, n_src, B, K, halo, x_stride, ang_stride);
     if (rc) return rc;
     const long W = halo + B + K;
-    BAS_REQUIRE(y_stride >= n_sessions * W - K, BAS_E_SHAPE, "bas_stream_batch_epilogue_f32: y_stride %ld < T_in %ld",
-                y_stride, n_sessions * W - K);
-    BAS_REQUIRE(x && elev && azim && last && y && peaks, BAS_E_NULL, "bas_stream_batch_epilogue_f32: null pointer");
+    BAS_REQUIRE(y_stride >= n_sessions * W - K, BAS_E_SHAPE, "%s: y_stride %ld < T_in %ld", what, y_stride,
+                n_sessions * W - K);
+    BAS_REQUIRE(x && elev && azim && last && y && peaks && (!need_gain || (gain && gain_last)), BAS_E_NULL,
+                "%s: null pointer", what);
     const int nh = halo / K, nb = (int)(B / K + 1);
     const long work = (2 * B) / 4 > (long)n_src * halo ? (2 * B) / 4 : (long)n_src * halo;
     const dim3 grid(sb_blocks_x(n_sessions, work), n_sessions);
     hipLaunchKernelGGL(bas_stream_block_epilogue_kernel, grid, dim3(SB_THREADS), 0, bas_stream(stream), x, x_stride, n_src,
                        halo, B, W, elev, azim, ang_stride, nh, nb, last, y, y_stride,
-                       reinterpret_cast<unsigned int *>(peaks));
-    return bas_check_launch("bas_stream_batch_epilogue_f32");
+                       reinterpret_cast<unsigned int *>(peaks), gain, gain_last);
+    return bas_check_launch(what);
+}
+
+extern "C" int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
+                                             double *elev, double *azim, long ang_stride, double *last, const float *y,
+                                             long y_stride, float *peaks, bas_stream_t stream) {
+    return sb_epilogue("bas_stream_batch_epilogue_f32", x, x_stride, n_sessions, n_src, halo, B, K, elev, azim, nullptr,
+                       ang_stride, last, nullptr, false, y, y_stride, peaks, stream);
+}
+
+// apply_hrtf.py:429-447, carried per session: gain rows at the angles' stride move as the angles; gain_last [G][n_src]
+extern "C" int bas_stream_batch_epilogue_gain_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B,
+                                                  int K, double *elev, double *azim, double *gain, long ang_stride,
+                                                  double *last, double *gain_last, const float *y, long y_stride,
+                                                  float *peaks, bas_stream_t stream) {
+    return sb_epilogue("bas_stream_batch_epilogue_gain_f32", x, x_stride, n_sessions, n_src, halo, B, K, elev, azim, gain,
+                       ang_stride, last, gain_last, true, y, y_stride, peaks, stream);
+}
+
+static int stream_epilogue(const char *what, float *x, long x_stride, int n_src, int halo, long B, double *elev,
+                           double *azim, double *gain, long ang_stride, int nh, int nb, double *last, double *gain_last,
+                           bool need_gain, const float *y, long y_stride, float *running_peak, bas_stream_t stream) {
+    BAS_REQUIRE(n_src >= 0 && halo >= 0 && B > 0 && nh >= 0 && nb >= 2, BAS_E_SHAPE,
+                "%s: need n_src>=0, halo>=0, B>0, nh>=0, nb>=2 (n_src=%d halo=%d B=%ld nh=%d nb=%d)", what, n_src, halo, B,
+                nh, nb);
+    BAS_REQUIRE(x_stride >= halo + B && ang_stride >= nh + nb && y_stride >= halo + B, BAS_E_SHAPE,
+                "%s: strides shorter than the window", what);
+    BAS_REQUIRE(y && (n_src == 0 || (x && elev && azim && last && (!need_gain || (gain && gain_last)))), BAS_E_NULL,
+                "%s: null pointer", what);
+    long work = 2 * B > (long)n_src * halo ? 2 * B : (long)n_src * halo;
+    hipLaunchKernelGGL(bas_stream_block_epilogue_kernel, dim3(bas_grid_for(work, 1024)), dim3(SB_THREADS), 0,
+                       bas_stream(stream), x, x_stride, n_src, halo, B, 0L, elev, azim, ang_stride, nh, nb, last, y,
+                       y_stride, reinterpret_cast<unsigned int *>(running_peak), gain, gain_last);   // (one session: W unused)
+    return bas_check_launch(what);
 }
 
 extern "C" int bas_stream_epilogue_f32(float *x, long x_stride, int n_src, int halo, long B, double *elev, double *azim,
                                        long ang_stride, int nh, int nb, double *last, const float *y, long y_stride,
                                        float *running_peak, bas_stream_t stream) {
-    BAS_REQUIRE(n_src >= 0 && halo >= 0 && B > 0 && nh >= 0 && nb >= 2, BAS_E_SHAPE,
-                "bas_stream_epilogue_f32: need n_src>=0, halo>=0, B>0, nh>=0, nb>=2 (n_src=%d halo=%d B=%ld nh=%d nb=%d)",
-                n_src, halo, B, nh, nb);
-    BAS_REQUIRE(x_stride >= halo + B && ang_stride >= nh + nb && y_stride >= halo + B, BAS_E_SHAPE,
-                "bas_stream_epilogue_f32: strides shorter than the window");
-    BAS_REQUIRE(y && (n_src == 0 || (x && elev && azim && last)), BAS_E_NULL, "bas_stream_epilogue_f32: null pointer");
-    long work = 2 * B > (long)n_src * halo ? 2 * B : (long)n_src * halo;
-    hipLaunchKernelGGL(bas_stream_block_epilogue_kernel, dim3(bas_grid_for(work, 1024)), dim3(SB_THREADS), 0,
-                       bas_stream(stream), x, x_stride, n_src, halo, B, 0L, elev, azim, ang_stride, nh, nb, last, y,
-                       y_stride, reinterpret_cast<unsigned int *>(running_peak));      // (one session: W unused)
-    return bas_check_launch("bas_stream_epilogue_f32");
+    return stream_epilogue("bas_stream_epilogue_f32", x, x_stride, n_src, halo, B, elev, azim, nullptr, ang_stride, nh, nb,
+                           last, nullptr, false, y, y_stride, running_peak, stream);
+}
+
+// apply_hrtf.py:429-447, carried: gain [n_src] rows at the angles' stride move as the angles, gain_last [n_src]
+extern "C" int bas_stream_epilogue_gain_f32(float *x, long x_stride, int n_src, int halo, long B, double *elev,
+                                            double *azim, double *gain, long ang_stride, int nh, int nb, double *last,
+                                            double *gain_last, const float *y, long y_stride, float *running_peak,
+                                            bas_stream_t stream) {
+    return stream_epilogue("bas_stream_epilogue_gain_f32", x, x_stride, n_src, halo, B, elev, azim, gain, ang_stride, nh, nb,
+                           last, gain_last, true, y, y_stride, running_peak, stream);
 }

@@ -112,14 +112,19 @@ def gather_mix(partial, group=None, dst=0, mix_fn=None, scale_fn=None, normalize
 
 
 def render_sources_sharded(signals, chunksize, subchunksize, elev, azim, tbl, group=None, dst=0,
-                           normalize="mix", render_fn=None, mix_fn=None, scale_fn=None):
+                           normalize="mix", render_fn=None, mix_fn=None, scale_fn=None, gain=None):
     """Render THIS rank's sources (`signals`, `elev`, `azim` hold only the local shard)
     and gather the mix on rank dst.  render_fn(signals, K, S, elev, azim, tbl) must return
-    the un-normalised local mix as (T_out, 2); default: the HIP renderer."""
+    the un-normalised local mix as (T_out, 2); default: the HIP renderer.  gain: None, or the
+    local shard's gains (render_sources(gain=...)), passed to render_fn as gain=."""
     if render_fn is None:
         from .apply_hrtf import render_sources
-        render_fn = lambda s, k, ss, e, a, t: render_sources(s, k, ss, e, a, t, normalize="none")   # noqa: E731
-    local = render_fn(signals, chunksize, subchunksize, elev, azim, tbl)
+        render_fn = lambda s, k, ss, e, a, t, gain=None: render_sources(s, k, ss, e, a, t, normalize="none",  # noqa: E731
+                                                                         gain=gain)
+    if gain is None:
+        local = render_fn(signals, chunksize, subchunksize, elev, azim, tbl)
+    else:
+        local = render_fn(signals, chunksize, subchunksize, elev, azim, tbl, gain=gain)
     return gather_mix(local.t(), group=group, dst=dst, mix_fn=mix_fn, scale_fn=scale_fn, normalize=normalize)
 
 
@@ -238,9 +243,11 @@ class ShardedStreamRenderer:
         self._peak = peak if self._peak is None else self._peak.maximum(peak)
         return y
 
-    def process(self, block_local, elev_local, azim_local):
-        """block_local [len(self.sources), B] and the trajectories of THIS rank's sources."""
-        return self._combine(self.local.process(block_local, elev_local, azim_local))
+    def process(self, block_local, elev_local, azim_local, head=None, gain=None):
+        """block_local [len(self.sources), B] and the trajectories of THIS rank's sources; head and gain (the local
+        sources' gains) are passed to the local stream's process() when given."""
+        extra = {k: v for k, v in (("head", head), ("gain", gain)) if v is not None}
+        return self._combine(self.local.process(block_local, elev_local, azim_local, **extra))
 
     def finish(self):
         return self._combine(self.local.finish())

@@ -32,7 +32,8 @@ tiles of 2048 samples anyway - a 512-sample block with a 512-sample halo is ONE 
 source, exactly as it would be with a 128-sample halo.
 """
 from . import _hip, sphere
-from .apply_hrtf import as_device_table, plan_angles_device, render_angles_device
+from .apply_hrtf import (as_device_table, plan_angles_device, render_angles_device, check_gain, stage_gain,
+                         _is_device_gain)
 
 
 def rotate_into_views(elev, azim, head, views):
@@ -106,11 +107,11 @@ class _BlockStream:
         self._ws = _hip.new_workspace(wb, dev)
         self._ws_plans = torch.empty((lib.bas_interp2d_workspace_bytes(n_q),), dtype=torch.uint8, device=dev)
 
-    def _render_window(self, x, elev, azim):
+    def _render_window(self, x, elev, azim, gain=None):
         """a3, read plans, chunk IRs + FIR + mix (or the stored-IR path) of one window into self._y: no peak, no peak rule
-        (the epilogue takes the peak of the EMITTED samples)."""
+        (the epilogue takes the peak of the EMITTED samples).  gain: the window's gain rows or None."""
         render_angles_device(x, self.K, self.S, self.tbl, elev, azim, normalize="none", out=self._y, ws=self._ws,
-                             ws_plans=self._ws_plans, events=self._events, want_peak=False)
+                             ws_plans=self._ws_plans, events=self._events, want_peak=False, gain=gain)
 
     def _capture(self):
         import torch
@@ -180,6 +181,11 @@ class StreamRenderer(_BlockStream):
         self.samples_in = 0
         self._finished = False
         self._head_buf = None                             # device staging of host head orientations (process(head=...))
+        # per-source gains: None until the first gained block or gain_view() - until then the buffers,
+        # the launches and the graph are the gain-less ones.  Then [n_src, nh + nb] beside the angles (halo part carried)
+        # and the gain at the END of the last block, for finish()
+        self._gain_all = None
+        self._gain_last = None
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _reserve(self, B):
@@ -209,8 +215,21 @@ class StreamRenderer(_BlockStream):
         if self._halo_params is not None:
             self._elev_all[:, :nh], self._azim_all[:, :nh] = self._halo_params
             self._halo_params = None
+        if self._gain_all is not None:                    # live gains: the halo's carried across the re-layout
+            g = torch.ones((n, nh + nb), dtype=torch.float64, device=dev)
+            g[:, :nh] = self._gain_all[:, :nh]
+            self._gain_all = g
         self._y = torch.empty((2, self.halo + B + self.tbl.L - 1), dtype=torch.float32, device=dev)
         self._window_workspaces(n, self.halo + B, n * (nh + nb))
+
+    def _enable_gain(self):
+        """Make the gain rows live (ones: the gain-less render's bits), once; the block's launches change, so does its graph."""
+        import torch
+        if self._gain_all is None:
+            dev = self.tbl.device
+            self._gain_all = torch.ones((self.n_src, self.nh + self._nb), dtype=torch.float64, device=dev)
+            self._gain_last = torch.ones((self.n_src,), dtype=torch.float64, device=dev)
+            self._graph, self._blocks_in_layout = None, 0
 
     def input_view(self, B):
         """Device view [n_src, B] of the renderer's own input buffer.  A producer (decoder, H2D copy,
@@ -227,6 +246,14 @@ class StreamRenderer(_BlockStream):
         self._layout(B)
         return self._elev_all[:, self.nh:], self._azim_all[:, self.nh:]
 
+    def gain_view(self, B):
+        """Device view, float64 [n_src, B/K + 1], of the renderer's own gain buffer for blocks of B samples (DESIGN.md
+        §3.10), beside trajectory_views(B): a producer that writes the gains there and passes the view to process(gain=)
+        saves the copy.  Makes the gains live (a renderer never given a gain keeps the gain-less launches)."""
+        self._layout(B)
+        self._enable_gain()
+        return self._gain_all[:, self.nh:]
+
     # ---- one block -------------------------------------------------------------------------------------
     def _block_body(self):
         """The stream-ordered work of one block on the per-block buffers (captured into the hipGraph)."""
@@ -238,6 +265,20 @@ class StreamRenderer(_BlockStream):
         with _hip.on_device(dev):
             one_call = self.one_call and bool(lib.bas_render_fused_supported(n, halo + B, self.K, self.S, tbl.L)) and tbl.upsampling >= 4 \
                 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+        g = self._gain_all
+        if one_call and g is not None:
+            # the same with the gains folded into the plans and carried beside the angles
+            if self._events is not None:
+                raise ValueError("profiling events (bench.py) time gain-less blocks only: a gained block has no profiled "
+                                 "entry point")
+            plan_angles_device(tbl, self._elev_all, self._azim_all, self._ws_plans, gain=g)
+            with _hip.on_device(dev):
+                _hip.call("bas_render_stream_block_gain_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), _hip.ptr(tbl.packed),
+                          _hip.ptr(self._ws_plans), n, halo + B, self.K, self.S, tbl.L, tbl.upsampling, tbl.ndir,
+                          _hip.ptr(self._y), _hip.ptr(self._ws), self._ws.numel(), halo, _hip.ptr(self._elev_all),
+                          _hip.ptr(self._azim_all), _hip.ptr(g), self._elev_all.stride(0), nh, nb, _hip.ptr(self._last),
+                          _hip.ptr(self._gain_last), _hip.ptr(self._peak_dev), _hip.current_stream(dev))
+            return
         if one_call:
             # read plans (a3 inside), then ONE call: chunk IRs + FIR + mix, and behind the sums of its reduce kernel the
             # running peak over the emitted samples + the carry of the last `halo` inputs and of the angles at their chunk
@@ -254,15 +295,22 @@ class StreamRenderer(_BlockStream):
                     _hip.call("bas_render_stream_block_profiled_f32", *args, self._events[0], self._events[1])
             return
         # other shapes: the render of the window, then the epilogue launch
-        self._render_window(x, self._elev_all, self._azim_all)
+        self._render_window(x, self._elev_all, self._azim_all, gain=g)
         with _hip.on_device(dev):
-            _hip.call("bas_stream_epilogue_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), self.n_src, halo, B,
-                      _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0), nh, nb,
-                      _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peak_dev),
-                      _hip.current_stream(dev))
+            if g is None:
+                _hip.call("bas_stream_epilogue_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), self.n_src, halo, B,
+                          _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0), nh, nb,
+                          _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peak_dev),
+                          _hip.current_stream(dev))
+            else:
+                _hip.call("bas_stream_epilogue_gain_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), self.n_src, halo, B,
+                          _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), _hip.ptr(g), self._elev_all.stride(0), nh, nb,
+                          _hip.ptr(self._last), _hip.ptr(self._gain_last), _hip.ptr(self._y), self._y.stride(0),
+                          _hip.ptr(self._peak_dev), _hip.current_stream(dev))
 
     def _carried(self):
-        return self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev
+        gains = () if self._gain_all is None else (self._gain_all, self._gain_last)
+        return (self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev) + gains
 
     def _emitted(self):
         return self._y[:, self.halo:self.halo + self._B].t()
@@ -272,7 +320,7 @@ class StreamRenderer(_BlockStream):
         assert B % self.K == 0 and B > 0, 'block length must be a positive multiple of the chunk size'
         super().prepare(B)
 
-    def process(self, block, elev, azim, head=None):
+    def process(self, block, elev, azim, head=None, gain=None):
         """block: [n_src, B] (B a multiple of the chunk size); elev/azim: float64 [n_src, B/K + 1],
         the trajectory at t = t0, t0+K, .., t0+B of this block (radians; numpy arrays or device tensors).
         head: None (elev/azim are head-relative), or the listener's head orientation at the same boundaries, quaternions
@@ -280,6 +328,9 @@ class StreamRenderer(_BlockStream):
         bas_head_relative_f64 writes the head-relative angles into trajectory_views(B) (in place when elev/azim are
         those views).  A host head is validated (sphere.check_head: ValueError) and staged in a persistent device
         buffer; a device tensor is checked for shape and dtype only.
+        gain: None, or float64 [n_src, B/K + 1], every source's gain at the same boundaries (host gains
+        must be finite: ValueError; device tensors are checked for shape and dtype only; gain_view(B) is taken in place).
+        After the first gained block the gains are carried like the angles, and a block with gain=None has gains of one.
         Returns the B stereo samples this block completes as a device tensor (B, 2), un-normalised."""
         import torch
         assert not self._finished, "stream already finished"
@@ -289,20 +340,26 @@ class StreamRenderer(_BlockStream):
         assert B % self.K == 0 and B > 0, 'block length must be a positive multiple of the chunk size'
         self._layout(B)
         nb = self._nb
+        # every argument is checked before the renderer's state changes (a refused call leaves its launches and graph)
+        for t in (elev, azim):
+            if tuple(torch.as_tensor(t).shape) != (self.n_src, nb):
+                raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
+        if gain is not None and not _is_device_gain(gain, (self.n_src, nb)):
+            check_gain(gain, (self.n_src, nb))
+        if head is not None:
+            q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
+        if gain is not None:
+            self._enable_gain()
+            stage_gain(gain, self._gain_all[:, self.nh:])
+        elif self._gain_all is not None:
+            self._gain_all[:, self.nh:].fill_(1.0)
         if head is None:
             for src, dst in ((elev, self._elev_all[:, self.nh:]), (azim, self._azim_all[:, self.nh:])):
                 t = torch.as_tensor(src)
-                if tuple(t.shape) != (self.n_src, nb):
-                    raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
                 if not _is_buffer(t, dst, torch.float64):
                     dst.copy_(t)                          # (H2D for host arrays; float64 kept exactly)
         else:
-            views = (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:])
-            for t in (elev, azim):
-                if tuple(torch.as_tensor(t).shape) != (self.n_src, nb):
-                    raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
-            q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
-            rotate_into_views(elev, azim, q, views)
+            rotate_into_views(elev, azim, q, (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:]))
         x_dst = self._xbuf[:, self.halo:self.halo + B]
         if not _is_buffer(blk, x_dst, torch.float32):
             x_dst.copy_(blk)
@@ -332,7 +389,11 @@ class StreamRenderer(_BlockStream):
         elev = torch.cat([e_halo, e_last, e_last], dim=1).contiguous()
         azim = torch.cat([a_halo, a_last, a_last], dim=1).contiguous()
         x = torch.cat([self._xbuf[:, :self.halo], torch.zeros((self.n_src, self.K), dtype=torch.float32, device=dev)], dim=1)
-        y, _ = render_angles_device(x, self.K, self.S, self.tbl, elev, azim, normalize="none", want_peak=False)
+        gain = None
+        if self._gain_all is not None:                    # the halo's carried gains, then the end gain twice
+            g_last = self._gain_last.reshape(-1, 1)
+            gain = torch.cat([self._gain_all[:, :nh], g_last, g_last], dim=1).contiguous()
+        y, _ = render_angles_device(x, self.K, self.S, self.tbl, elev, azim, normalize="none", want_peak=False, gain=gain)
         out = y[:, self.halo:self.halo + L - 1]
         if out.numel():
             self._peak_dev = torch.maximum(self._peak_dev, out.abs().max().reshape(1))

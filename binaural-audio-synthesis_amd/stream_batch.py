@@ -27,6 +27,7 @@ import numpy as np
 
 from . import _hip, sphere
 from .batch import MAX_RENDER_SAMPLES, render_batch
+from .apply_hrtf import _is_device_gain, check_gain, gain_to_device, stage_gain
 from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views
 
 MAX_SESSIONS = 65535             # the epilogue and pack kernels have one row of workgroups per session (gridDim.y)
@@ -133,6 +134,11 @@ class StreamBatchRenderer(_BlockStream):
         # re-lays the per-block buffers out and cannot lose them
         self._last = torch.zeros((self.G, 2, self.n_src), dtype=torch.float64, device=dev)
         self._peaks = torch.zeros((self.G,), dtype=torch.float32, device=dev)
+        # per-source gains: None until the first gained block or gain_view(); then rows laid out as the
+        # angles [n_src, G (nh + nb)] and every session's gain at the end of its last block [G, n_src]
+        self._gain = None
+        self._gain_last = None
+        self._gain_in = None                              # dense staging of host gains for the fused pack
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _x3(self, x=None, lay=None):
@@ -156,11 +162,14 @@ class StreamBatchRenderer(_BlockStream):
         x = torch.zeros((n, (self.G * lay.W + 3) // 4 * 4), dtype=torch.float32, device=dev)
         elev = torch.zeros((n, lay.n_q), dtype=torch.float64, device=dev)
         azim = torch.zeros((n, lay.n_q), dtype=torch.float64, device=dev)
+        gain = None if self._gain is None else torch.ones((n, lay.n_q), dtype=torch.float64, device=dev)
         if self._lay is not None:                         # carry every session's halo into the new layout
             self._x3(x, lay)[:, :, :halo] = self._x3()[:, :, :halo]
-            for new, old in ((elev, self._elev), (azim, self._azim)):
-                self._a3(new, lay)[:, :, :nh] = self._a3(old)[:, :, :nh]
-        self._lay, self._x, self._elev, self._azim = lay, x, elev, azim
+            for new, old in ((elev, self._elev), (azim, self._azim), (gain, self._gain)):
+                if new is not None:
+                    self._a3(new, lay)[:, :, :nh] = self._a3(old)[:, :, :nh]
+        self._lay, self._x, self._elev, self._azim, self._gain = lay, x, elev, azim, gain
+        self._gain_in = None
         self._graph, self._blocks_in_layout = None, 0
         self._y = torch.empty((2, lay.T_out), dtype=torch.float32, device=dev)
         self._blk = None                                  # staging buffers of the pack (allocated on first use)
@@ -190,6 +199,25 @@ class StreamBatchRenderer(_BlockStream):
         shape, strides = (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1)
         return (torch.as_strided(self._elev, shape, strides, lay.nh), torch.as_strided(self._azim, shape, strides, lay.nh))
 
+    def _enable_gain(self):
+        """Make the gain rows live (ones: the gain-less render's bits), once; the block's launches change, so does its graph."""
+        import torch
+        if self._gain is None:
+            dev = self.tbl.device
+            self._gain = torch.ones((self.n_src, self._lay.n_q), dtype=torch.float64, device=dev)
+            self._gain_last = torch.ones((self.G, self.n_src), dtype=torch.float64, device=dev)
+            self._graph, self._blocks_in_layout = None, 0
+
+    def gain_view(self, B):
+        """Device view, float64 [G, n_src, B/K + 1] (strided), of the renderer's own gain buffer for blocks of B samples,
+        beside trajectory_views(B): a producer that writes the gains there and passes the view to
+        process(gain=) saves the copy.  Makes the gains live."""
+        import torch
+        self._layout(B)
+        self._enable_gain()
+        lay = self._lay
+        return torch.as_strided(self._gain, (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1), lay.nh)
+
     def _emitted(self):
         """[G, B, 2] view of the render output: the samples this block completes for every session."""
         import torch
@@ -200,17 +228,24 @@ class StreamBatchRenderer(_BlockStream):
     def _block_body(self):
         """The stream-ordered work of one block after the pack (captured into the hipGraph)."""
         lay, dev = self._lay, self.tbl.device
-        self._render_window(self._x[:, :lay.T_in], self._elev, self._azim)
+        self._render_window(self._x[:, :lay.T_in], self._elev, self._azim, gain=self._gain)
         with _hip.on_device(dev):
-            _hip.call("bas_stream_batch_epilogue_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src, self.halo,
-                      lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0),
-                      _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peaks),
-                      _hip.current_stream(dev))
+            if self._gain is None:
+                _hip.call("bas_stream_batch_epilogue_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src,
+                          self.halo, lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0),
+                          _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peaks),
+                          _hip.current_stream(dev))
+            else:
+                _hip.call("bas_stream_batch_epilogue_gain_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src,
+                          self.halo, lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), _hip.ptr(self._gain),
+                          self._elev.stride(0), _hip.ptr(self._last), _hip.ptr(self._gain_last), _hip.ptr(self._y),
+                          self._y.stride(0), _hip.ptr(self._peaks), _hip.current_stream(dev))
 
     def _carried(self):
-        return self._x, self._elev, self._azim, self._last, self._peaks
+        gains = () if self._gain is None else (self._gain, self._gain_last)
+        return (self._x, self._elev, self._azim, self._last, self._peaks) + gains
 
-    def process(self, blocks, elev, azim, head=None):
+    def process(self, blocks, elev, azim, head=None, gain=None):
         """blocks: [G, n_src, B] (B a multiple of the chunk size); elev/azim: float64 [G, n_src, B/K + 1], every session's
         trajectory at t0, t0 + K, .., t0 + B of this block (radians; numpy arrays or device tensors).  head: None
         (elev/azim are head-relative), or every session's listener orientation at the same boundaries, quaternions
@@ -218,8 +253,11 @@ class StreamBatchRenderer(_BlockStream):
         the pack launch (bas_stream_batch_pack_head_f32: no launch more); when the producer wrote in place through
         input_view / trajectory_views, one bas_head_relative_f64 launch rotates the angle views in place.  A host head is
         validated (sphere.check_head: ValueError) and staged in a persistent device buffer; a device tensor is checked for
-        shape and dtype only.  Returns the B stereo samples this block completes for every session, a device tensor
-        [G, B, 2], un-normalised."""
+        shape and dtype only.  gain: None, or float64 [G, n_src, B/K + 1], every source's gain at the same boundaries
+        (DESIGN.md §3.10): dense inputs take it in the pack launch (bas_stream_batch_pack_gain_f32), in-place producers
+        write it through gain_view(B).  Host gains must be finite (ValueError); device tensors are checked for shape and
+        dtype only.  After the first gained block the gains are carried, and a gain-less block has gains of one.
+        Returns the B stereo samples this block completes for every session, a device tensor [G, B, 2], un-normalised."""
         import torch
         blk = torch.as_tensor(blocks)
         if blk.dim() != 3 or tuple(blk.shape[:2]) != (self.G, self.n_src):
@@ -235,12 +273,21 @@ class StreamBatchRenderer(_BlockStream):
         for t in angs:
             if tuple(t.shape) != (self.G, self.n_src, lay.nb):
                 raise ValueError(f"elev/azim must have shape ({self.G}, {self.n_src}, {lay.nb})")
+        g_shape = (self.G, self.n_src, lay.nb)
+        if gain is not None and not _is_device_gain(gain, g_shape):
+            check_gain(gain, g_shape)                     # (host gains: validated before any device work)
         x_in_place = _is_buffer(blk, x_view, torch.float32)
         a_in_place = all(_is_buffer(t, v, torch.float64) for t, v in zip(angs, views))
         if head is not None:                              # (the renderer's own head buffer is dense: the fused pack reads it)
             q, self._head_in = sphere.head_to_device(head, (self.G, lay.nb, 4), dev, self._head_in)
             if not (x_in_place or a_in_place):
                 q = q.contiguous()
+        gview, g_in_place = None, False
+        if gain is not None:                              # every argument is valid: the gains go live
+            gview = self.gain_view(B)
+            g_in_place = _is_buffer(gain, gview, torch.float64) if isinstance(gain, torch.Tensor) else False
+        elif self._gain is not None:                      # a gain-less block of a gained renderer: gains of one
+            self.gain_view(B).fill_(1.0)
         if x_in_place or a_in_place:                      # the producer wrote part of the block in place: copy the rest
             if not x_in_place:
                 x_view.copy_(blk)
@@ -249,18 +296,18 @@ class StreamBatchRenderer(_BlockStream):
             elif not a_in_place:
                 for t, v in zip(angs, views):
                     v.copy_(t)
+            if gain is not None and not g_in_place:
+                stage_gain(gain, gview)
+        elif gain is not None and not g_in_place:         # one pack launch: blocks, angles (head) and gains
+            blk, angs = self._dense_inputs(blk, angs, B)
+            gq, self._gain_in = gain_to_device(gain, g_shape, dev, self._gain_in)
+            with _hip.on_device(dev):
+                _hip.call("bas_stream_batch_pack_gain_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
+                          _hip.ptr(q) if head is not None else None, _hip.ptr(gq), self.G, self.n_src, B, self.K, self.halo,
+                          _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev), _hip.ptr(self._azim),
+                          _hip.ptr(self._gain), self._elev.stride(0), _hip.current_stream(dev))
         else:                                             # one pack launch from dense device arrays
-            if not (blk.is_cuda and blk.dtype == torch.float32 and blk.is_contiguous() and blk.device == dev):
-                if self._blk is None:
-                    self._blk = torch.empty((self.G, self.n_src, B), dtype=torch.float32, device=dev)
-                self._blk.copy_(blk)                      # (H2D for host arrays)
-                blk = self._blk
-            for k, t in enumerate(angs):
-                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev):
-                    if self._ang_in is None:
-                        self._ang_in = torch.empty((2, self.G, self.n_src, lay.nb), dtype=torch.float64, device=dev)
-                    self._ang_in[k].copy_(t)              # (float64 kept exactly)
-                    angs[k] = self._ang_in[k]
+            blk, angs = self._dense_inputs(blk, angs, B)
             with _hip.on_device(dev):
                 if head is None:
                     _hip.call("bas_stream_batch_pack_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]), self.G,
@@ -271,6 +318,23 @@ class StreamBatchRenderer(_BlockStream):
                               _hip.ptr(q), self.G, self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0),
                               _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
         return self._run_block()
+
+    def _dense_inputs(self, blk, angs, B):
+        """The pack's operands as dense device arrays on the renderer's device (staged when they are not)."""
+        import torch
+        dev, nb = self.tbl.device, self._lay.nb
+        if not (blk.is_cuda and blk.dtype == torch.float32 and blk.is_contiguous() and blk.device == dev):
+            if self._blk is None:
+                self._blk = torch.empty((self.G, self.n_src, B), dtype=torch.float32, device=dev)
+            self._blk.copy_(blk)                          # (H2D for host arrays)
+            blk = self._blk
+        for k, t in enumerate(angs):
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == dev):
+                if self._ang_in is None:
+                    self._ang_in = torch.empty((2, self.G, self.n_src, nb), dtype=torch.float64, device=dev)
+                self._ang_in[k].copy_(t)                  # (float64 kept exactly)
+                angs[k] = self._ang_in[k]
+        return blk, angs
 
     # ---- per-session state -----------------------------------------------------------------------------
     @property
@@ -293,7 +357,8 @@ class StreamBatchRenderer(_BlockStream):
 
     def reset(self, sessions):
         """Drop the streams of these slots without a tail: their halo inputs, halo angles, end angles and peaks are
-        zeroed on the device (slice ops on the current stream, no synchronisation).  Their next block starts fresh."""
+        zeroed on the device (slice ops on the current stream, no synchronisation), their carried gains set to one.  Their
+        next block starts fresh."""
         for g0, g1 in _session_runs(self._sessions(sessions)):
             if self._lay is not None:
                 self._x3()[:, g0:g1, :self.halo].zero_()
@@ -301,10 +366,13 @@ class StreamBatchRenderer(_BlockStream):
                 self._a3(self._azim)[:, g0:g1, :self.nh].zero_()
             self._last[g0:g1].zero_()
             self._peaks[g0:g1].zero_()
+            if self._gain is not None:                    # carried gains back to one
+                self._a3(self._gain)[:, g0:g1, :self.nh].fill_(1.0)
+                self._gain_last[g0:g1].fill_(1.0)
 
     def finish(self, sessions, return_peaks=False):
         """Emit the last L-1 samples of these sessions' streams (the tail the reference appends, apply_hrtf.py:410), as
-        StreamRenderer.finish: each session's [halo | K zeros] window with its halo angles, then its end angle twice,
+        StreamRenderer.finish: each session's [halo | K zeros] window with its halo angles (and gains), then its end angle twice,
         rendered for the listed sessions only, in one batched render (render_batch: the gap behind each window is at least
         L-1 samples, so a tail reads no other session's inputs).  The tail's samples count into the sessions' peaks; then
         the slots restart as fresh streams (reset).  Returns a device tensor [len(sessions), L-1, 2] in ascending session
@@ -322,7 +390,11 @@ class StreamBatchRenderer(_BlockStream):
             for k, a in enumerate((self._elev, self._azim)):
                 end = self._last.index_select(0, sel)[:, k, :, None]                     # [n, n_src, 1]
                 ang.append(torch.cat([self._a3(a)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2))
-            out, _, _ = render_batch(sig, K, self.S, ang[0], ang[1], self.tbl, normalize="none")
+            gain = None
+            if self._gain is not None:                    # the halo's carried gains, then the end gain twice
+                end = self._gain_last.index_select(0, sel)[:, :, None]
+                gain = torch.cat([self._a3(self._gain)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2)
+            out, _, _ = render_batch(sig, K, self.S, ang[0], ang[1], self.tbl, normalize="none", gain=gain)
             tails.copy_(out[:, halo:halo + L - 1])
             self._peaks.index_copy_(0, sel, torch.maximum(self._peaks.index_select(0, sel), tails.abs().amax(dim=(1, 2))))
         final = self._peaks[idx].cpu().numpy() if return_peaks else None

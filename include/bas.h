@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BAS_ABI_VERSION 5
+#define BAS_ABI_VERSION 6
 
 #define BAS_E_NULL      (-1)   /* a required pointer is NULL                    */
 #define BAS_E_SHAPE     (-2)   /* inconsistent or unsupported sizes             */
@@ -396,6 +396,55 @@ int bas_stream_batch_epilogue_f32(float *x, long x_stride, int n_sessions, int n
 int bas_head_relative_f64(const double *elev, const double *azim, long in_stride_g, long in_stride_s, const double *head,
                           long head_stride_g, long head_stride_c, int n_groups, int n_src, int nb, double *elev_out,
                           double *azim_out, long out_stride_g, long out_stride_s, bas_stream_t stream);
+
+/* ---- per-source gain at chunk boundaries (no reference counterpart) -------------------------------
+ * gain [..] f64 (device) holds one value per chunk boundary, laid out exactly as the angles of the same call (one per
+ * query: source s at boundary k sits where elev[s][k] / azim[s][k] sit).  The chunk IR at a boundary becomes
+ * g_k interpolate_2d(el_k, az_k); the reference's subchunk crossfade (apply_hrtf.py:435, :443) then runs unchanged between
+ * g_k H_k and g_{k+1} H_{k+1}.  Any finite real gain is allowed (negative: polarity inverted, zero: silence); nothing is
+ * validated on the device.  The peak rules (make_signal_move_2d's :462-464, the batch's per item, the streams' running
+ * peaks) see the gained output.  Every entry point below is its gain-less namesake with the gain added (a required
+ * pointer: BAS_E_NULL when it is NULL and there is work); the namesakes are these calls with no gain and keep their code.
+ *   plans (bas_interp2d_plan_gain_f32, _plan_angles_gain_f32): every one of the 16 folded weights is multiplied by
+ *     gain[q] in binary64 and rounded to binary32 once, so the fused FIR kernels gain it without a change;
+ *   bas_interp2d_gain_f32: the stored chunk IRs H[q] = gain[q] interpolate_2d(q) (planned tables as above; U < 4 tables
+ *     scale every tap by gain[q] in binary64, rounded once);
+ *   carried stream state (bas_render_stream_block_gain_f32, bas_stream_epilogue_gain_f32, bas_stream_batch_epilogue_gain_f32):
+ *     gain rows at the angles' stride move as the angles do, gain_last [n_src] (one stream) / [G][n_src] (batched
+ *     streams) receives the gain at the block's end, as last[] receives the angles;
+ *   bas_stream_batch_pack_gain_f32: gain [G][n_src][nb] -> gain_out's slots beside the angles, in the same launch; head
+ *     may be NULL (head-relative angles) or as for bas_stream_batch_pack_head_f32;
+ *   bas_batch_pack_gain_f32: gain [B][n_src][n_q_max] -> gain_out [n_src][T_in/K + 1] as the angles (the gap's inner
+ *     boundaries repeat the item's last gain). */
+int bas_interp2d_plan_gain_f32(const double *diffs, const int32_t *idx, const double *w, const double *gain, int n,
+                               int ndir, int L, int U, void *plans, size_t plans_bytes, bas_stream_t stream);
+int bas_interp2d_plan_angles_gain_f32(const double *diffs, const double *elev, const double *azim, const double *gain,
+                                      int n, const double *ring_elev, const int32_t *ring_start,
+                                      const int32_t *ring_count, const float *node_az, int branch, int ndir, int L,
+                                      int U, void *plans, size_t plans_bytes, bas_stream_t stream);
+int bas_interp2d_gain_f32(const float *packed, const double *diffs, const int32_t *idx, const double *w,
+                          const double *gain, int n, int ndir, int L, int U, float *H, void *ws, size_t ws_bytes,
+                          bas_stream_t stream);
+int bas_render_stream_block_gain_f32(float *x, long x_stride, const float *packed, const void *plans, int n_src,
+                                     long T_in, int K, int S, int L, int U, int ndir, float *y, void *ws,
+                                     size_t ws_bytes, int halo, double *elev, double *azim, double *gain,
+                                     long ang_stride, int nh, int nb, double *last, double *gain_last,
+                                     float *running_peak, bas_stream_t stream);
+int bas_stream_epilogue_gain_f32(float *x, long x_stride, int n_src, int halo, long B, double *elev, double *azim,
+                                 double *gain, long ang_stride, int nh, int nb, double *last, double *gain_last,
+                                 const float *y, long y_stride, float *running_peak, bas_stream_t stream);
+int bas_stream_batch_pack_gain_f32(const float *blocks, const double *elev, const double *azim, const double *head,
+                                   const double *gain, int n_sessions, int n_src, long B, int K, int halo, float *x,
+                                   long x_stride, double *elev_out, double *azim_out, double *gain_out,
+                                   long ang_stride, bas_stream_t stream);
+int bas_stream_batch_epilogue_gain_f32(float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,
+                                       double *elev, double *azim, double *gain, long ang_stride, double *last,
+                                       double *gain_last, const float *y, long y_stride, float *peaks,
+                                       bas_stream_t stream);
+int bas_batch_pack_gain_f32(const float *sig, int n_items, int n_src, long N, const long *lengths, const long *offsets,
+                            const double *elev, const double *azim, const double *gain, long n_q_max, int K,
+                            long T_in, float *x, long x_stride, double *elev_out, double *azim_out, double *gain_out,
+                            bas_stream_t stream);
 
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All

@@ -9,8 +9,10 @@ both sides pay the same staging copies.  Per case it reports, as medians over th
   * wall_us: host time of one block up to a stream synchronisation, and rtf = G B / fs / wall (real-time factor).
 With --head both sides are head-tracked: world-frame angles and a device tensor of head orientations
 per block (the batch rotates inside its pack launch, each lone renderer with one bas_head_relative_f64 launch).
+With --gain both sides take per-source gains at every boundary: a device tensor per block, folded into
+the batch's pack launch and into the read plans (no launch more on either side).
 Prints one JSON line; --out also writes it to a file.
-    python3 tools/bench_stream_batch.py [--steps 50] [--warmup 5] [--case 256x512] [--head] [--out profiles/stream_batch_bench.json]"""
+    python3 tools/bench_stream_batch.py [--steps 50] [--warmup 5] [--case 256x512] [--head] [--gain] [--out profiles/stream_batch_bench.json]"""
 import argparse
 import json
 import os
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--case", action="append", default=None, metavar="GxB",
                     help="only these cases (e.g. 256x512; repeatable); default: all of CASES")
     ap.add_argument("--head", action="store_true", help="head-tracked: world angles + per-boundary head orientations")
+    ap.add_argument("--gain", action="store_true", help="per-source gains at every chunk boundary (DESIGN.md §3.10)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -63,7 +66,7 @@ def main():
     tbl = bas.irs_and_delaydiffs(host.upsampling, host.diffs_left, host.diffs_right, host.irs_left, host.irs_right)
     rng = np.random.default_rng(0)
     result = {"workload": f"G sessions x {N_SRC} sources, K={K} S={S} L={L}, fs={FS}; one block per step",
-              "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "head": args.head,
+              "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "head": args.head, "gain": args.gain,
               "cases": []}
     cases = CASES if args.case is None else [tuple(int(v) for v in c.lower().split("x")) for c in args.case]
     for G, B in cases:
@@ -74,21 +77,23 @@ def main():
         q = rng.standard_normal((G, nb, 4))
         hd = torch.from_numpy(q / np.linalg.norm(q, axis=-1, keepdims=True)).cuda() if args.head else None
         hg = (lambda g: None) if hd is None else (lambda g: hd[g])
+        gn = torch.from_numpy(rng.uniform(0.0, 1.5, (G, N_SRC, nb))).cuda() if args.gain else None
+        gg = (lambda g: None) if gn is None else (lambda g: gn[g])
         sb = bas.StreamBatchRenderer(tbl, G, N_SRC, K, S, graph=True, copy_out=False)
         sb.prepare(B)
-        batch = _time(lambda: sb.process(x, e, a, head=hd), args.steps, args.warmup)
+        batch = _time(lambda: sb.process(x, e, a, head=hd, gain=gn), args.steps, args.warmup)
         loop_r = [bas.StreamRenderer(tbl, N_SRC, K, S, graph=True, copy_out=False) for _ in range(G)]
         for r in loop_r:
             r.prepare(B)
 
         def loop_step():
             for g, r in enumerate(loop_r):
-                r.process(x[g], e[g], a[g], head=hg(g))
+                r.process(x[g], e[g], a[g], head=hg(g), gain=gg(g))
         loop = _time(loop_step, args.steps, args.warmup)
         # the same block through both: the batch's sessions against the lone renderers (carried state differs only by
         # the number of blocks each has seen, equal here)
-        y = sb.process(x, e, a, head=hd).clone()
-        diff = max(float((y[g] - r.process(x[g], e[g], a[g], head=hg(g))).abs().max()) for g, r in enumerate(loop_r))
+        y = sb.process(x, e, a, head=hd, gain=gn).clone()
+        diff = max(float((y[g] - r.process(x[g], e[g], a[g], head=hg(g), gain=gg(g))).abs().max()) for g, r in enumerate(loop_r))
         lay = sb.layout(B)
         audio_s = G * B / FS
         row = {"G": G, "n_src": N_SRC, "B": B, "T_in": lay.T_in,
