@@ -110,10 +110,22 @@ SIGNATURES = {
     "bas_batch_pack_gain_f32": (_c_int, [_c_void_p, _c_int, _c_int, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                          _c_void_p, _c_long, _c_int, _c_long, _c_void_p, _c_long, _c_void_p, _c_void_p,
                                          _c_void_p, _c_void_p]),
+    # per-source propagation delay
+    "bas_delay_rows_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_int, _c_void_p, _c_void_p, _c_long, _c_long, _c_int,
+                                    _c_int, _c_long, _c_int, _c_int, ctypes.c_double, _c_void_p, _c_long, _c_long,
+                                    _c_void_p]),
+    "bas_delay_carry_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_int, _c_int, _c_int, _c_long, _c_void_p]),
+    "bas_stream_batch_pack_delay_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                                 ctypes.c_double, _c_void_p, _c_long, _c_long, _c_int, _c_int, _c_int,
+                                                 _c_long, _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p,
+                                                 _c_void_p, _c_long, _c_void_p]),
+    "bas_batch_pack_delay_f32": (_c_int, [_c_void_p, _c_int, _c_int, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                          _c_void_p, _c_void_p, _c_int, _c_long, _c_int, _c_long, _c_void_p, _c_long,
+                                          _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lib = None
-ABI_VERSION = 6                                                      # BAS_ABI_VERSION of include/bas.h
+ABI_VERSION = 7                                                      # BAS_ABI_VERSION of include/bas.h
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libbas_hip_diag.so")   # -DBAS_DIAG build: reads BAS_FORCE_KERNEL (tests only)
 
 

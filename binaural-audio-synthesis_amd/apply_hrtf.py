@@ -482,7 +482,8 @@ def _params_to_device(tbl, idx, w):
     return idx_t, w_t
 
 
-def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize="mix", fused=None, gain=None):
+def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize="mix", fused=None, gain=None, delay=None,
+                   interp="cubic"):
     """Render and mix many independently moving sources.
 
     signals: [n_src, N] (numpy or tensor); elev/azim: float64 [n_src, n_chunks+1]
@@ -494,8 +495,13 @@ def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize=
     gain: None, or float64 [n_src, n_chunks+1], source s's gain at each chunk boundary: the chunk IR
     there becomes gain * interpolate_2d, crossfaded per subchunk as the IRs are.  Host gains must be finite (ValueError);
     device tensors are checked for shape and dtype only.
+    delay: None, or float64 [n_src, n_chunks+1], source s's propagation delay in samples at each chunk boundary (DESIGN.md
+    §3.11): the source's input becomes its delayed input (propagation.delayed_inputs; interp "cubic" or "linear"), written
+    by one bas_delay_rows_f32 launch straight into the padded rows the render reads.  Host delays must be finite and at
+    least the interpolator's d_min (ValueError); device tensors are checked for shape and dtype only.
     """
     import torch
+    from . import propagation
     tbl = as_device_table(tbl)
     dev = tbl.device
     assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
@@ -503,13 +509,21 @@ def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize=
     assert sig.dim() == 2, 'signals must be [n_src, N]'
     n_src, n = sig.shape
     in_length, _ = render_lengths(n, chunksize, tbl.L)
-    x = padded_rows(n_src, in_length, dev)                                   # :406
-    x[:, :n] = sig.to(device=dev, dtype=torch.float32)
     n_q = in_length // chunksize + 1
+    if delay is not None:
+        propagation.interp_code(interp)
     idx, w = sphere.interpolation_params_batch(elev, azim)
     if idx.shape[:-1] != (n_src, n_q):
         raise ValueError(f"elev/azim must have shape ({n_src}, {n_q})")
     g = None if gain is None else gain_to_device(gain, (n_src, n_q), dev)[0]
+    d = None if delay is None else propagation.delay_to_device(delay, (n_src, n_q), interp, dev)
+    x = padded_rows(n_src, in_length, dev)                                   # :406
+    if d is None:
+        x[:, :n] = sig.to(device=dev, dtype=torch.float32)
+    elif n:                                                                  # delayed inputs, read up to n, zero beyond
+        src = sig.to(device=dev, dtype=torch.float32).contiguous()
+        lens = torch.full((n_src,), n, dtype=torch.int64, device=dev)
+        propagation.delay_rows_device(src, d, chunksize, interp, x, lengths=lens)
     idx_t, w_t = _params_to_device(tbl, idx, w)
     y, _ = render_params_device(x, chunksize, subchunksize, tbl, idx_t, w_t, normalize, fused=fused, gain=g)
     return y.t()

@@ -132,7 +132,7 @@ def _all_finite(a):
 
 
 def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None, normalize="each", branch="f64",
-                 contiguous=False, check=False, max_samples=None, events=None, gain=None):
+                 contiguous=False, check=False, max_samples=None, events=None, gain=None, delay=None, interp="cubic"):
     """Render B independent clips in one device render, each as make_signal_move_2d renders it alone.
 
     signals: [B, N] (one source per item) or [B, n_src, N] (small scenes, mixed per item as render_sources mixes), numpy
@@ -151,9 +151,13 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
     and the finish (one-render batches: tools/bench_batch.py).
     gain: None, or float64 of elev's shape [B, (n_src,) n_q_max]: each source's gain at each of its item's chunk boundaries
     (DESIGN.md §3.10); the peak rule and peaks see the gained output.  Host gains must be finite (ValueError); device
-    tensors are checked for shape and dtype only."""
+    tensors are checked for shape and dtype only.
+    delay: None, or float64 of elev's shape [B, (n_src,) n_q_max]: each source's propagation delay in samples at each of its
+    item's chunk boundaries (interp "cubic" or "linear").  The pack launch writes the delayed inputs (no
+    launch more); item b's reads are bounded by its own valid length.  Host delays must be finite and at least the
+    interpolator's d_min (ValueError); device tensors are checked for shape and dtype only."""
     import torch
-    from . import _hip, sphere
+    from . import _hip, sphere, propagation
     from .apply_hrtf import as_device_table, render_angles_device, gain_to_device
     B, n_src, N, n = _check_args(tuple(signals.shape), lengths, tuple(np.shape(elev)), tuple(np.shape(azim)),
                                  chunksize, subchunksize, normalize)
@@ -164,6 +168,11 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
     g_all = None
     if gain is not None:                                  # (validated before any device work)
         g_all = gain_to_device(gain, tuple(np.shape(elev)), as_device_table(tbl).device)[0].reshape(B, n_src, -1)
+    d_all = None
+    if delay is not None:
+        code = propagation.interp_code(interp)
+        d_all = propagation.delay_to_device(delay, tuple(np.shape(elev)), interp, as_device_table(tbl).device)
+        d_all = d_all.reshape(B, n_src, -1)
     K, S = int(chunksize), int(subchunksize)
     tbl = as_device_table(tbl)
     dev = tbl.device
@@ -195,7 +204,12 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
             ang = torch.empty((2 if g_all is None else 3, n_src, lay.n_q), dtype=torch.float64, device=dev)
             if events is not None:
                 events[0].record()
-            if g_all is None:
+            if d_all is not None:
+                _hip.call("bas_batch_pack_delay_f32", _hip.ptr(sig[b0]), nb, n_src, N, _hip.ptr(meta[0]), _hip.ptr(meta[1]),
+                          _hip.ptr(e_all[b0]), _hip.ptr(a_all[b0]), None if g_all is None else _hip.ptr(g_all[b0]),
+                          _hip.ptr(d_all[b0]), code, n_q_max, K, lay.T_in, _hip.ptr(x), stride, _hip.ptr(ang[0]),
+                          _hip.ptr(ang[1]), None if g_all is None else _hip.ptr(ang[2]), stream)
+            elif g_all is None:
                 _hip.call("bas_batch_pack_f32", _hip.ptr(sig[b0]), nb, n_src, N, _hip.ptr(meta[0]), _hip.ptr(meta[1]),
                           _hip.ptr(e_all[b0]), _hip.ptr(a_all[b0]), n_q_max, K, lay.T_in, _hip.ptr(x), stride,
                           _hip.ptr(ang[0]), _hip.ptr(ang[1]), stream)

@@ -9,6 +9,7 @@
 //                          normalize, the rule per item (:463-464), in place or compacted to [B][2][T_out_max];
 //                          two launches (maxima, then scale/compact), no inter-workgroup waiting.
 #include "bas_internal.h"
+#include "bas_delay.h"
 
 #define BB_THREADS 256
 
@@ -16,13 +17,15 @@
 // x_stride), 4 samples per thread (16-byte store; rows 16-byte aligned, stride a multiple of 4 floats), then the segment's
 // chunk boundaries [off_b/K, off_{b+1}/K) (the last one to n_q), one (elev, azim) pair per thread.  Every float of
 // x[s][0 .. x_stride) is written: the pad and the gaps are 0.  No search: the item is the row's.  GAIN: gain [B][n_src]
-// [n_q_max] is packed into gain_out like the angles.
-template <bool GAIN>
+// [n_q_max] is packed into gain_out like the angles.  DELAY: every sample of an item's segment is its
+// delayed input, read from the item's own row and its own delay row delay[b][s][0 .. n_q_max) (no packed
+// delay array), bounded by the item's valid length: reads outside [0, len_b) are 0, and so are the outputs at t >= len_b.
+template <bool GAIN, bool DELAY>
 __global__ __launch_bounds__(BB_THREADS) void bas_batch_pack_kernel(
     const float *__restrict__ sig, int n_items, int n_src, long N, const long *__restrict__ len, const long *__restrict__ off,
     const double *__restrict__ elev, const double *__restrict__ azim, long n_q_max, int K, long n_q,
     float *__restrict__ x, long x_stride, double *__restrict__ elev_out, double *__restrict__ azim_out,
-    const double *__restrict__ gain, double *__restrict__ gain_out) {
+    const double *__restrict__ gain, double *__restrict__ gain_out, const double *__restrict__ delay, int interp) {
     const int b0 = blockIdx.y;
     const bool last = b0 + 1 == n_items;
     const long start = off[b0], end = last ? x_stride : off[b0 + 1];
@@ -41,7 +44,24 @@ __global__ __launch_bounds__(BB_THREADS) void bas_batch_pack_kernel(
             int b = b0;
             long o = start, n = n_own;
             const float *row = sig + ((long)b * n_src + s) * N;
-            if (t0 + 3 < o + n && sig_quads && ((t0 - o) & 3) == 0) {
+            if constexpr (DELAY) {
+                for (int k = 0; k < 4; ++k) {
+                    const long t = t0 + k;
+                    while (b + 1 < n_items && off[b + 1] <= t) {          // the quad crosses into the next segment
+                        ++b;
+                        o = off[b];
+                        n = min(len[b], N);
+                        row = sig + ((long)b * n_src + s) * N;
+                    }
+                    const long tl = t - o;                               // (o is a multiple of K: chunk-relative as alone)
+                    if (tl < n) {
+                        const long c = tl / K;
+                        const double *drow = delay + ((long)b * n_src + s) * n_q_max;
+                        v[k] = bas_delay_sample(row, 0, n, c * K, (int)(tl - c * K), K, drow[c], drow[c + 1],
+                                                bas_delay_min(interp), (double)n + 4.0, interp);
+                    }
+                }
+            } else if (t0 + 3 < o + n && sig_quads && ((t0 - o) & 3) == 0) {
                 const f32x4 q = *reinterpret_cast<const f32x4 *>(row + (t0 - o));
                 v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
             } else {
@@ -173,25 +193,39 @@ static int batch_blocks_x(int n_items, long max_len) {
 
 static int batch_pack(const char *who, const float *sig, int n_items, int n_src, long N, const long *lengths,
                       const long *offsets, const double *elev, const double *azim, const double *gain, bool need_gain,
-                      long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
-                      double *gain_out, bas_stream_t stream) {
+                      const double *delay, bool need_delay, int interp, long n_q_max, int K, long T_in, float *x,
+                      long x_stride, double *elev_out, double *azim_out, double *gain_out, bas_stream_t stream) {
     BAS_REQUIRE(n_items > 0 && n_src > 0 && N >= 0 && K > 0 && T_in > 0 && n_q_max > 0, BAS_E_SHAPE,
                 "%s: need n_items, n_src, K, T_in, n_q_max > 0 and N >= 0", who);
     BAS_REQUIRE(T_in % K == 0, BAS_E_SHAPE, "%s: T_in (%ld) must be a multiple of K (%d)", who, T_in, K);
     BAS_REQUIRE(x_stride >= T_in && x_stride % 4 == 0, BAS_E_SHAPE, "%s: x_stride must be >= T_in and a multiple of 4", who);
     BAS_REQUIRE(lengths && offsets && elev && azim && x && elev_out && azim_out && (sig || N == 0) &&
-                    (!need_gain || (gain && gain_out)),
+                    (!need_gain || (gain && gain_out)) && (!need_delay || delay),
                 BAS_E_NULL, "%s: null pointer", who);
+    BAS_REQUIRE(!need_delay || interp == BAS_DELAY_LINEAR || interp == BAS_DELAY_CUBIC, BAS_E_SHAPE,
+                "%s: interp must be 0 (linear) or 1 (cubic)", who);
     BAS_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0, BAS_E_ALIGN, "%s: x must be 16-byte aligned", who);
     BAS_REQUIRE(n_items <= 65535, BAS_E_SHAPE, "%s: more than 65535 items in one call", who);
     const long n_q = T_in / K + 1;
     const dim3 grid(batch_blocks_x(n_items, n_src * ((x_stride + n_items - 1) / n_items)), n_items);
-    if (need_gain)
-        hipLaunchKernelGGL(bas_batch_pack_kernel<true>, grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items, n_src, N,
-                           lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, gain, gain_out);
+    const double *g = need_gain ? gain : nullptr;
+    double *go = need_gain ? gain_out : nullptr;
+    if (need_delay && need_gain)
+        hipLaunchKernelGGL((bas_batch_pack_kernel<true, true>), grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items,
+                           n_src, N, lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, g, go,
+                           delay, interp);
+    else if (need_delay)
+        hipLaunchKernelGGL((bas_batch_pack_kernel<false, true>), grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items,
+                           n_src, N, lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, g, go,
+                           delay, interp);
+    else if (need_gain)
+        hipLaunchKernelGGL((bas_batch_pack_kernel<true, false>), grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items,
+                           n_src, N, lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, g, go,
+                           nullptr, 0);
     else
-        hipLaunchKernelGGL(bas_batch_pack_kernel<false>, grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items, n_src, N,
-                           lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, nullptr, nullptr);
+        hipLaunchKernelGGL((bas_batch_pack_kernel<false, false>), grid, dim3(BB_THREADS), 0, bas_stream(stream), sig, n_items,
+                           n_src, N, lengths, offsets, elev, azim, n_q_max, K, n_q, x, x_stride, elev_out, azim_out, nullptr,
+                           nullptr, nullptr, 0);
     return bas_check_launch(who);
 }
 
@@ -199,8 +233,8 @@ extern "C" int bas_batch_pack_f32(const float *sig, int n_items, int n_src, long
                                   const long *offsets, const double *elev, const double *azim, long n_q_max, int K,
                                   long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
                                   bas_stream_t stream) {
-    return batch_pack("bas_batch_pack_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, nullptr, false, n_q_max, K,
-                      T_in, x, x_stride, elev_out, azim_out, nullptr, stream);
+    return batch_pack("bas_batch_pack_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, nullptr, false, nullptr,
+                      false, 0, n_q_max, K, T_in, x, x_stride, elev_out, azim_out, nullptr, stream);
 }
 
 // apply_hrtf.py:429-447 per item with per-boundary gains: gain [B][n_src][n_q_max] -> gain_out
@@ -209,8 +243,19 @@ extern "C" int bas_batch_pack_gain_f32(const float *sig, int n_items, int n_src,
                                        const long *offsets, const double *elev, const double *azim, const double *gain,
                                        long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out,
                                        double *azim_out, double *gain_out, bas_stream_t stream) {
-    return batch_pack("bas_batch_pack_gain_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, gain, true, n_q_max,
-                      K, T_in, x, x_stride, elev_out, azim_out, gain_out, stream);
+    return batch_pack("bas_batch_pack_gain_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, gain, true, nullptr,
+                      false, 0, n_q_max, K, T_in, x, x_stride, elev_out, azim_out, gain_out, stream);
+}
+
+// apply_hrtf.py:405-406 per item with a per-source propagation delay: delay [B][n_src][n_q_max] is
+// read where it is, item b's delayed input goes into its segment; gain may be NULL (then gain_out is ignored)
+extern "C" int bas_batch_pack_delay_f32(const float *sig, int n_items, int n_src, long N, const long *lengths,
+                                        const long *offsets, const double *elev, const double *azim, const double *gain,
+                                        const double *delay, int interp, long n_q_max, int K, long T_in, float *x,
+                                        long x_stride, double *elev_out, double *azim_out, double *gain_out,
+                                        bas_stream_t stream) {
+    return batch_pack("bas_batch_pack_delay_f32", sig, n_items, n_src, N, lengths, offsets, elev, azim, gain, gain != nullptr,
+                      delay, true, interp, n_q_max, K, T_in, x, x_stride, elev_out, azim_out, gain_out, stream);
 }
 
 extern "C" int bas_batch_finish_f32(float *y, long y_stride, int n_items, const long *offsets, const long *out_lengths,

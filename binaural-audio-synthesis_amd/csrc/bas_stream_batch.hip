@@ -15,6 +15,7 @@
 //                                    carried state themselves (stream.py's two-call blocks, direct-output fused blocks).
 #include "bas_internal.h"
 #include "bas_head.h"
+#include "bas_delay.h"
 
 #define SB_THREADS 256
 
@@ -25,12 +26,17 @@ __device__ __forceinline__ bool sb_aligned16(const void *p) { return (reinterpre
 // (every quad of the row then is), else as up to 4 scalars (still coalesced across a wave).  HEAD: the angles are world-frame
 // and head [G][nb][4] holds session g's orientation at each boundary; the slots get bas_head_relative's angles.
 // GAIN: gain [G][n_src][nb] goes into gain_out's slots beside the angles, in the same launch.
-template <bool HEAD, bool GAIN>
+// DELAY: a block quad goes into the window as its delayed samples, read from the session's carried raw
+// history raw[g][s][0 .. H) and the dense block (bas_delay_sample_split, the same bits as bas_delay_rows_f32), with the
+// delays delay[G][n_src][nb] clamped to [d_min, max_delay]; the raw block is copied behind the history (raw[g][s][H ..)),
+// where bas_delay_carry_f32 finds it.  Nothing the launch reads is written by it.
+template <bool HEAD, bool GAIN, bool DELAY>
 __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
     const float *__restrict__ blocks, const double *__restrict__ elev, const double *__restrict__ azim, int n_src,
     long B, long W, int halo, int nh, int nb, float *__restrict__ x, long x_stride, double *__restrict__ elev_out,
     double *__restrict__ azim_out, long ang_stride, const double *__restrict__ head, const double *__restrict__ gain,
-    double *__restrict__ gain_out) {
+    double *__restrict__ gain_out, float *__restrict__ raw, long raw_g, long raw_s, int H, const double *__restrict__ delay,
+    int K, int interp, double max_delay) {
     const int g = blockIdx.y;
     const long nq = (B + 3) >> 2;
     const long n_x = (long)n_src * nq, n_items = n_x + (long)n_src * nb;
@@ -41,7 +47,17 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_batch_pack_kernel(
             const long j0 = (i - (long)s * nq) << 2;
             const float *src = blocks + ((long)g * n_src + s) * B;
             float *dst = x + (long)s * x_stride + (long)g * W + halo;
-            if ((B & 3) == 0 && sb_aligned16(src) && sb_aligned16(dst)) {
+            if constexpr (DELAY) {
+                float *hist = raw + (long)g * raw_g + (long)s * raw_s;
+                const double *drow = delay + ((long)g * n_src + s) * nb;
+                const double dmin = bas_delay_min(interp);
+                for (int m = 0; m < 4 && j0 + m < B; ++m) {
+                    const long t = j0 + m, k = t / K;
+                    dst[t] = bas_delay_sample_split(hist, H, src, B, k * K, (int)(t - k * K), K, drow[k], drow[k + 1], dmin,
+                                                    max_delay, interp);
+                    hist[H + t] = src[t];
+                }
+            } else if ((B & 3) == 0 && sb_aligned16(src) && sb_aligned16(dst)) {
                 *reinterpret_cast<f32x4 *>(dst + j0) = *reinterpret_cast<const f32x4 *>(src + j0);
             } else {
                 for (int k = 0; k < 4 && j0 + k < B; ++k) dst[j0 + k] = src[j0 + k];
@@ -127,21 +143,33 @@ static int sb_check_layout(const char *what, int n_sessions, int n_src, long B, 
     return 0;
 }
 
-// every pack entry point: the layout checks, the pointers (head only with HEAD, gain and gain_out only with GAIN), one launch
-template <bool HEAD, bool GAIN>
+// every pack entry point: the layout checks, the pointers (head only with HEAD, gain and gain_out only with GAIN, raw and
+// delay only with DELAY), one launch
+template <bool HEAD, bool GAIN, bool DELAY = false>
 static int sb_pack(const char *what, const float *blocks, const double *elev, const double *azim, const double *head,
                    const double *gain, int n_sessions, int n_src, long B, int K, int halo, float *x, long x_stride,
-                   double *elev_out, double *azim_out, double *gain_out, long ang_stride, bas_stream_t stream) {
+                   double *elev_out, double *azim_out, double *gain_out, long ang_stride, bas_stream_t stream,
+                   float *raw = nullptr, long raw_g = 0, long raw_s = 0, int H = 0, const double *delay = nullptr,
+                   int interp = 0, double max_delay = 0.0) {
     int rc = sb_check_layout(what, n_sessions, n_src, B, K, halo, x_stride, ang_stride);
     if (rc) return rc;
-    BAS_REQUIRE(blocks && elev && azim && (!HEAD || head) && (!GAIN || (gain && gain_out)) && x && elev_out && azim_out,
+    BAS_REQUIRE(blocks && elev && azim && (!HEAD || head) && (!GAIN || (gain && gain_out)) && x && elev_out && azim_out &&
+                    (!DELAY || (raw && delay)),
                 BAS_E_NULL, "%s: null pointer", what);
+    if (DELAY) {
+        BAS_REQUIRE(interp == BAS_DELAY_LINEAR || interp == BAS_DELAY_CUBIC, BAS_E_SHAPE,
+                    "%s: interp must be 0 (linear) or 1 (cubic)", what);
+        BAS_REQUIRE(max_delay >= (interp == BAS_DELAY_CUBIC ? 2.0 : 1.0) && max_delay + 2.0 <= (double)H, BAS_E_SHAPE,
+                    "%s: max_delay must lie in [d_min, H - 2]", what);
+        BAS_REQUIRE(raw_s >= H + B && raw_g >= (long)n_src * raw_s, BAS_E_SHAPE,
+                    "%s: raw strides shorter than [H | B] rows", what);
+    }
     const long W = halo + B + K;
     const int nh = halo / K, nb = (int)(B / K + 1);
     const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
-    hipLaunchKernelGGL((bas_stream_batch_pack_kernel<HEAD, GAIN>), grid, dim3(SB_THREADS), 0, bas_stream(stream), blocks,
-                       elev, azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head, gain,
-                       gain_out);
+    hipLaunchKernelGGL((bas_stream_batch_pack_kernel<HEAD, GAIN, DELAY>), grid, dim3(SB_THREADS), 0, bas_stream(stream),
+                       blocks, elev, azim, n_src, B, W, halo, nh, nb, x, x_stride, elev_out, azim_out, ang_stride, head, gain,
+                       gain_out, raw, raw_g, raw_s, H, delay, K, interp, max_delay);
     return bas_check_launch(what);
 }
 
@@ -171,6 +199,25 @@ extern "C" int bas_stream_batch_pack_gain_f32(const float *blocks, const double 
                                    halo, x, x_stride, elev_out, azim_out, gain_out, ang_stride, stream);
     return sb_pack<false, true>("bas_stream_batch_pack_gain_f32", blocks, elev, azim, nullptr, gain, n_sessions, n_src, B, K,
                                 halo, x, x_stride, elev_out, azim_out, gain_out, ang_stride, stream);
+}
+
+// the pack with per-source propagation delays: head and gain may each be NULL (then gain_out is ignored)
+extern "C" int bas_stream_batch_pack_delay_f32(const float *blocks, const double *elev, const double *azim,
+                                               const double *head, const double *gain, const double *delay, int interp,
+                                               double max_delay, float *raw, long raw_stride_g, long raw_stride_s, int H,
+                                               int n_sessions, int n_src, long B, int K, int halo, float *x, long x_stride,
+                                               double *elev_out, double *azim_out, double *gain_out, long ang_stride,
+                                               bas_stream_t stream) {
+    const char *w = "bas_stream_batch_pack_delay_f32";
+#define SB_PACK_DELAY(HD, GN)                                                                                              \
+    return sb_pack<HD, GN, true>(w, blocks, elev, azim, head, gain, n_sessions, n_src, B, K, halo, x, x_stride, elev_out,  \
+                                 azim_out, gain_out, ang_stride, stream, raw, raw_stride_g, raw_stride_s, H, delay, interp, \
+                                 max_delay)
+    if (head && gain) SB_PACK_DELAY(true, true);
+    if (head) SB_PACK_DELAY(true, false);
+    if (gain) SB_PACK_DELAY(false, true);
+    SB_PACK_DELAY(false, false);
+#undef SB_PACK_DELAY
 }
 
 static int sb_epilogue(const char *what, float *x, long x_stride, int n_sessions, int n_src, int halo, long B, int K,

@@ -31,7 +31,7 @@ is its offset inside its chunk, apply_hrtf.py:442), and their work is quantised 
 tiles of 2048 samples anyway - a 512-sample block with a 512-sample halo is ONE tile per
 source, exactly as it would be with a 128-sample halo.
 """
-from . import _hip, sphere
+from . import _hip, sphere, propagation
 from .apply_hrtf import (as_device_table, plan_angles_device, render_angles_device, check_gain, stage_gain,
                          _is_device_gain)
 
@@ -160,10 +160,13 @@ class _BlockStream:
 class StreamRenderer(_BlockStream):
     one_call = True      # bas_render_stream_block_f32 where the fused kernels serve the block (False: render + epilogue launch; A/B, tests)
 
-    def __init__(self, tbl, n_src, chunksize, subchunksize, graph=True, copy_out=True):
+    def __init__(self, tbl, n_src, chunksize, subchunksize, graph=True, copy_out=True, max_delay=None, interp="cubic"):
         """graph: replay each block as one captured hipGraph (captured by prepare(), else on the second block of a
         size).  copy_out: process() returns a fresh tensor (True) or a view of the renderer's output buffer that
-        the next process() call overwrites (False: no copy kernel; for callers that consume each block at once)."""
+        the next process() call overwrites (False: no copy kernel; for callers that consume each block at once).
+        max_delay: None, or the largest propagation delay in samples the stream takes: every block then
+        needs delay=, and the renderer carries the last history_samples(max_delay) raw input samples per source;
+        interp: the delay's interpolator ("cubic" or "linear")."""
         import torch
         super().__init__(tbl, chunksize, subchunksize, graph, copy_out)
         self.n_src = int(n_src)
@@ -186,6 +189,14 @@ class StreamRenderer(_BlockStream):
         # and the gain at the END of the last block, for finish()
         self._gain_all = None
         self._gain_last = None
+        # propagation delay: raw input rows [n_src, H + capacity] - columns [0, H) carry the last H raw
+        # samples, a block's raw input lands behind them and its delayed input goes into _xbuf - and the block's delays
+        propagation.interp_code(interp)
+        self.interp = interp
+        self.max_delay = None if max_delay is None else propagation.check_max_delay(max_delay, interp)
+        self.H = 0 if max_delay is None else propagation.history_samples(self.max_delay)
+        self._raw = None if max_delay is None else torch.zeros((self.n_src, self.H), dtype=torch.float32, device=dev)
+        self._delay_all = None
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _reserve(self, B):
@@ -196,6 +207,11 @@ class StreamRenderer(_BlockStream):
             grown[:, :self.halo] = self._xbuf[:, :self.halo]
             self._xbuf = grown
             self._graph = None                            # the captured pointers are gone
+        if self._raw is not None and self._raw.shape[1] - self.H < B:
+            grown = torch.zeros((self.n_src, self.H + (B + 3) // 4 * 4), dtype=torch.float32, device=self._raw.device)
+            grown[:, :self.H] = self._raw[:, :self.H]     # the carried raw history survives the growth
+            self._raw = grown
+            self._graph = None
 
     def _layout(self, B):
         """Per-block buffers for blocks of B samples (kept until another size arrives)."""
@@ -219,6 +235,8 @@ class StreamRenderer(_BlockStream):
             g = torch.ones((n, nh + nb), dtype=torch.float64, device=dev)
             g[:, :nh] = self._gain_all[:, :nh]
             self._gain_all = g
+        if self._raw is not None:                         # (not carried: each block brings its boundaries' delays)
+            self._delay_all = torch.zeros((n, nb), dtype=torch.float64, device=dev)
         self._y = torch.empty((2, self.halo + B + self.tbl.L - 1), dtype=torch.float32, device=dev)
         self._window_workspaces(n, self.halo + B, n * (nh + nb))
 
@@ -235,8 +253,11 @@ class StreamRenderer(_BlockStream):
         """Device view [n_src, B] of the renderer's own input buffer.  A producer (decoder, H2D copy,
         another kernel) that writes the next block here and passes this view to process() saves the
         staging copy of the block; the view is valid until the next input_view() call with a larger B.
-        Growing the buffer allocates and drops the captured graph: size it once, before prepare()."""
+        Growing the buffer allocates and drops the captured graph: size it once, before prepare().  With max_delay the
+        view holds the block's raw input (the renderer delays it)."""
         self._reserve(B)
+        if self._raw is not None:
+            return self._raw[:, self.H:self.H + B]
         return self._xbuf[:, self.halo:self.halo + B]
 
     def trajectory_views(self, B):
@@ -254,6 +275,15 @@ class StreamRenderer(_BlockStream):
         self._enable_gain()
         return self._gain_all[:, self.nh:]
 
+    def delay_view(self, B):
+        """Device view, float64 [n_src, B/K + 1], of the renderer's own delay buffer for blocks of B samples (DESIGN.md
+        §3.11), beside gain_view(B): a producer that writes the delays there and passes the view to process(delay=) saves
+        the copy.  Only for a renderer built with max_delay (ValueError otherwise)."""
+        if self.max_delay is None:
+            raise ValueError("delay_view: the renderer was built without max_delay")
+        self._layout(B)
+        return self._delay_all
+
     # ---- one block -------------------------------------------------------------------------------------
     def _block_body(self):
         """The stream-ordered work of one block on the per-block buffers (captured into the hipGraph)."""
@@ -262,6 +292,14 @@ class StreamRenderer(_BlockStream):
         x = self._xbuf[:, :halo + B]
         tbl, n = self.tbl, self.n_src
         lib = _hip.lib()
+        if self._raw is not None:
+            # the block's delayed input into the window behind the halo (one launch), then the raw history moves behind
+            # the block (one launch): the last H raw samples go to the front for the next block
+            propagation.delay_rows_device(self._raw[:, self.H:self.H + B], self._delay_all, self.K, self.interp,
+                                          self._xbuf[:, halo:halo + B], H=self.H, max_delay=self.max_delay)
+            with _hip.on_device(dev):
+                _hip.call("bas_delay_carry_f32", _hip.ptr(self._raw), 0, self._raw.stride(0), 1, n, self.H, B,
+                          _hip.current_stream(dev))
         with _hip.on_device(dev):
             one_call = self.one_call and bool(lib.bas_render_fused_supported(n, halo + B, self.K, self.S, tbl.L)) and tbl.upsampling >= 4 \
                 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
@@ -310,7 +348,8 @@ class StreamRenderer(_BlockStream):
 
     def _carried(self):
         gains = () if self._gain_all is None else (self._gain_all, self._gain_last)
-        return (self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev) + gains
+        raw = () if self._raw is None else (self._raw[:, :self.H + self._B], self._delay_all)
+        return (self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev) + gains + raw
 
     def _emitted(self):
         return self._y[:, self.halo:self.halo + self._B].t()
@@ -320,7 +359,7 @@ class StreamRenderer(_BlockStream):
         assert B % self.K == 0 and B > 0, 'block length must be a positive multiple of the chunk size'
         super().prepare(B)
 
-    def process(self, block, elev, azim, head=None, gain=None):
+    def process(self, block, elev, azim, head=None, gain=None, delay=None):
         """block: [n_src, B] (B a multiple of the chunk size); elev/azim: float64 [n_src, B/K + 1],
         the trajectory at t = t0, t0+K, .., t0+B of this block (radians; numpy arrays or device tensors).
         head: None (elev/azim are head-relative), or the listener's head orientation at the same boundaries, quaternions
@@ -331,6 +370,10 @@ class StreamRenderer(_BlockStream):
         gain: None, or float64 [n_src, B/K + 1], every source's gain at the same boundaries (host gains
         must be finite: ValueError; device tensors are checked for shape and dtype only; gain_view(B) is taken in place).
         After the first gained block the gains are carried like the angles, and a block with gain=None has gains of one.
+        delay: float64 [n_src, B/K + 1], every source's propagation delay in samples at the same boundaries (DESIGN.md
+        §3.11): required by a renderer built with max_delay, refused (ValueError) by one without.  Host delays must be
+        finite and in [d_min, max_delay] (ValueError); device tensors are checked for shape and dtype only (the kernel
+        clamps); delay_view(B) is taken in place.  Consecutive blocks should repeat their shared boundary's delay.
         Returns the B stereo samples this block completes as a device tensor (B, 2), un-normalised."""
         import torch
         assert not self._finished, "stream already finished"
@@ -346,6 +389,11 @@ class StreamRenderer(_BlockStream):
                 raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
         if gain is not None and not _is_device_gain(gain, (self.n_src, nb)):
             check_gain(gain, (self.n_src, nb))
+        if (delay is None) != (self.max_delay is None):
+            raise ValueError("delay= is required by a renderer built with max_delay" if delay is None else
+                             "delay= needs a renderer built with max_delay")
+        if delay is not None and not propagation.is_device_delay(delay, (self.n_src, nb)):
+            propagation.check_delay(delay, (self.n_src, nb), self.interp, self.max_delay)
         if head is not None:
             q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
         if gain is not None:
@@ -360,7 +408,9 @@ class StreamRenderer(_BlockStream):
                     dst.copy_(t)                          # (H2D for host arrays; float64 kept exactly)
         else:
             rotate_into_views(elev, azim, q, (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:]))
-        x_dst = self._xbuf[:, self.halo:self.halo + B]
+        if delay is not None:
+            propagation.stage_delay(delay, self._delay_all, self.interp, self.max_delay)
+        x_dst = self.input_view(B)
         if not _is_buffer(blk, x_dst, torch.float32):
             x_dst.copy_(blk)
         out = self._run_block()

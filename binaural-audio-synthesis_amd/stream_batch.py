@@ -25,7 +25,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _hip, sphere
+from . import _hip, sphere, propagation
 from .batch import MAX_RENDER_SAMPLES, render_batch
 from .apply_hrtf import _is_device_gain, check_gain, gain_to_device, stage_gain
 from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views
@@ -122,8 +122,10 @@ def _session_runs(idx):
 
 
 class StreamBatchRenderer(_BlockStream):
-    def __init__(self, tbl, n_sessions, n_src, chunksize, subchunksize, graph=True, copy_out=True):
-        """n_sessions independent streams of n_src sources each.  graph, copy_out: as for StreamRenderer."""
+    def __init__(self, tbl, n_sessions, n_src, chunksize, subchunksize, graph=True, copy_out=True, max_delay=None,
+                 interp="cubic"):
+        """n_sessions independent streams of n_src sources each.  graph, copy_out, max_delay, interp: as
+        for StreamRenderer (max_delay: every block needs delay=, and every session carries its own raw history)."""
         import torch
         self.G, self.n_src = int(n_sessions), int(n_src)
         plan_stream_layout(self.G, self.n_src, int(chunksize), 1, int(chunksize))   # (session and source counts: ValueError)
@@ -139,6 +141,14 @@ class StreamBatchRenderer(_BlockStream):
         self._gain = None
         self._gain_last = None
         self._gain_in = None                              # dense staging of host gains for the fused pack
+        # propagation delay: raw input [G, n_src, H + capacity] - [0, H) the session's last H raw samples,
+        # the block's raw input behind them - and the block's delays [G, n_src, nb]
+        propagation.interp_code(interp)
+        self.interp = interp
+        self.max_delay = None if max_delay is None else propagation.check_max_delay(max_delay, interp)
+        self.H = 0 if max_delay is None else propagation.history_samples(self.max_delay)
+        self._raw = None
+        self._delay = None
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _x3(self, x=None, lay=None):
@@ -169,6 +179,12 @@ class StreamBatchRenderer(_BlockStream):
                 if new is not None:
                     self._a3(new, lay)[:, :, :nh] = self._a3(old)[:, :, :nh]
         self._lay, self._x, self._elev, self._azim, self._gain = lay, x, elev, azim, gain
+        if self.max_delay is not None:                    # the raw histories survive the re-layout
+            raw = torch.zeros((self.G, n, self.H + (B + 3) // 4 * 4), dtype=torch.float32, device=dev)
+            if self._raw is not None:
+                raw[:, :, :self.H] = self._raw[:, :, :self.H]
+            self._raw = raw
+            self._delay = torch.zeros((self.G, n, lay.nb), dtype=torch.float64, device=dev)
         self._gain_in = None
         self._graph, self._blocks_in_layout = None, 0
         self._y = torch.empty((2, lay.T_out), dtype=torch.float32, device=dev)
@@ -188,6 +204,8 @@ class StreamBatchRenderer(_BlockStream):
         import torch
         self._layout(B)
         lay = self._lay
+        if self._raw is not None:                         # with max_delay: the raw block behind the carried history
+            return self._raw[:, :, self.H:self.H + B]
         return torch.as_strided(self._x, (self.G, self.n_src, B), (lay.W, self._x.stride(0), 1), self.halo)
 
     def trajectory_views(self, B):
@@ -218,6 +236,14 @@ class StreamBatchRenderer(_BlockStream):
         lay = self._lay
         return torch.as_strided(self._gain, (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1), lay.nh)
 
+    def delay_view(self, B):
+        """Device view, float64 [G, n_src, B/K + 1], of the renderer's own delay buffer for blocks of B samples (DESIGN.md
+        §3.11), beside gain_view(B).  Only for a renderer built with max_delay (ValueError otherwise)."""
+        if self.max_delay is None:
+            raise ValueError("delay_view: the renderer was built without max_delay")
+        self._layout(B)
+        return self._delay
+
     def _emitted(self):
         """[G, B, 2] view of the render output: the samples this block completes for every session."""
         import torch
@@ -228,6 +254,10 @@ class StreamBatchRenderer(_BlockStream):
     def _block_body(self):
         """The stream-ordered work of one block after the pack (captured into the hipGraph)."""
         lay, dev = self._lay, self.tbl.device
+        if self._raw is not None:                         # every session's last H raw samples to the front (DESIGN.md §3.11)
+            with _hip.on_device(dev):
+                _hip.call("bas_delay_carry_f32", _hip.ptr(self._raw), self._raw.stride(0), self._raw.stride(1), self.G,
+                          self.n_src, self.H, lay.B, _hip.current_stream(dev))
         self._render_window(self._x[:, :lay.T_in], self._elev, self._azim, gain=self._gain)
         with _hip.on_device(dev):
             if self._gain is None:
@@ -243,9 +273,10 @@ class StreamBatchRenderer(_BlockStream):
 
     def _carried(self):
         gains = () if self._gain is None else (self._gain, self._gain_last)
-        return (self._x, self._elev, self._azim, self._last, self._peaks) + gains
+        raw = () if self._raw is None else (self._raw, self._delay)
+        return (self._x, self._elev, self._azim, self._last, self._peaks) + gains + raw
 
-    def process(self, blocks, elev, azim, head=None, gain=None):
+    def process(self, blocks, elev, azim, head=None, gain=None, delay=None):
         """blocks: [G, n_src, B] (B a multiple of the chunk size); elev/azim: float64 [G, n_src, B/K + 1], every session's
         trajectory at t0, t0 + K, .., t0 + B of this block (radians; numpy arrays or device tensors).  head: None
         (elev/azim are head-relative), or every session's listener orientation at the same boundaries, quaternions
@@ -257,6 +288,10 @@ class StreamBatchRenderer(_BlockStream):
         (DESIGN.md §3.10): dense inputs take it in the pack launch (bas_stream_batch_pack_gain_f32), in-place producers
         write it through gain_view(B).  Host gains must be finite (ValueError); device tensors are checked for shape and
         dtype only.  After the first gained block the gains are carried, and a gain-less block has gains of one.
+        delay: float64 [G, n_src, B/K + 1], every source's propagation delay in samples at the same boundaries (DESIGN.md
+        §3.11): required by a renderer built with max_delay, refused (ValueError) by one without; host delays must be
+        finite and in [d_min, max_delay].  Dense inputs take it in the pack launch (bas_stream_batch_pack_delay_f32);
+        when the producer wrote the block in place through input_view(B), one bas_delay_rows_f32 launch delays it.
         Returns the B stereo samples this block completes for every session, a device tensor [G, B, 2], un-normalised."""
         import torch
         blk = torch.as_tensor(blocks)
@@ -276,6 +311,11 @@ class StreamBatchRenderer(_BlockStream):
         g_shape = (self.G, self.n_src, lay.nb)
         if gain is not None and not _is_device_gain(gain, g_shape):
             check_gain(gain, g_shape)                     # (host gains: validated before any device work)
+        if (delay is None) != (self.max_delay is None):
+            raise ValueError("delay= is required by a renderer built with max_delay" if delay is None else
+                             "delay= needs a renderer built with max_delay")
+        if delay is not None and not propagation.is_device_delay(delay, g_shape):
+            propagation.check_delay(delay, g_shape, self.interp, self.max_delay)
         x_in_place = _is_buffer(blk, x_view, torch.float32)
         a_in_place = all(_is_buffer(t, v, torch.float64) for t, v in zip(angs, views))
         if head is not None:                              # (the renderer's own head buffer is dense: the fused pack reads it)
@@ -298,6 +338,24 @@ class StreamBatchRenderer(_BlockStream):
                     v.copy_(t)
             if gain is not None and not g_in_place:
                 stage_gain(gain, gview)
+            if delay is not None:                         # one launch: every session's delayed block into its window
+                propagation.stage_delay(delay, self._delay, self.interp, self.max_delay)
+                propagation.delay_rows_device(self._raw[0, :, self.H:self.H + B], self._delay[0], self.K, self.interp,
+                                              self._x[:, self.halo:self.halo + B], H=self.H, max_delay=self.max_delay,
+                                              groups=(self.G, self._raw.stride(0), self._delay.stride(0), lay.W))
+        elif delay is not None:                           # one pack launch: delayed blocks, angles (head), gains
+            blk, angs = self._dense_inputs(blk, angs, B)
+            propagation.stage_delay(delay, self._delay, self.interp, self.max_delay)
+            gq = None
+            if gain is not None and not g_in_place:
+                gq, self._gain_in = gain_to_device(gain, g_shape, dev, self._gain_in)
+            with _hip.on_device(dev):
+                _hip.call("bas_stream_batch_pack_delay_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
+                          _hip.ptr(q) if head is not None else None, None if gq is None else _hip.ptr(gq),
+                          _hip.ptr(self._delay), propagation.interp_code(self.interp), self.max_delay, _hip.ptr(self._raw),
+                          self._raw.stride(0), self._raw.stride(1), self.H, self.G, self.n_src, B, self.K, self.halo,
+                          _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev), _hip.ptr(self._azim),
+                          None if gq is None else _hip.ptr(self._gain), self._elev.stride(0), _hip.current_stream(dev))
         elif gain is not None and not g_in_place:         # one pack launch: blocks, angles (head) and gains
             blk, angs = self._dense_inputs(blk, angs, B)
             gq, self._gain_in = gain_to_device(gain, g_shape, dev, self._gain_in)
@@ -356,9 +414,9 @@ class StreamBatchRenderer(_BlockStream):
         return idx
 
     def reset(self, sessions):
-        """Drop the streams of these slots without a tail: their halo inputs, halo angles, end angles and peaks are
-        zeroed on the device (slice ops on the current stream, no synchronisation), their carried gains set to one.  Their
-        next block starts fresh."""
+        """Drop the streams of these slots without a tail: their halo inputs, halo angles, end angles, peaks and raw delay
+        histories are zeroed on the device (slice ops on the current stream, no synchronisation), their carried gains set
+        to one.  Their next block starts fresh."""
         for g0, g1 in _session_runs(self._sessions(sessions)):
             if self._lay is not None:
                 self._x3()[:, g0:g1, :self.halo].zero_()
@@ -366,6 +424,8 @@ class StreamBatchRenderer(_BlockStream):
                 self._a3(self._azim)[:, g0:g1, :self.nh].zero_()
             self._last[g0:g1].zero_()
             self._peaks[g0:g1].zero_()
+            if self._raw is not None:                     # the raw histories too: the next block starts from silence
+                self._raw[g0:g1, :, :self.H].zero_()
             if self._gain is not None:                    # carried gains back to one
                 self._a3(self._gain)[:, g0:g1, :self.nh].fill_(1.0)
                 self._gain_last[g0:g1].fill_(1.0)

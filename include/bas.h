@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BAS_ABI_VERSION 6
+#define BAS_ABI_VERSION 7
 
 #define BAS_E_NULL      (-1)   /* a required pointer is NULL                    */
 #define BAS_E_SHAPE     (-2)   /* inconsistent or unsupported sizes             */
@@ -445,6 +445,49 @@ int bas_batch_pack_gain_f32(const float *sig, int n_items, int n_src, long N, co
                             const double *elev, const double *azim, const double *gain, long n_q_max, int K,
                             long T_in, float *x, long x_stride, double *elev_out, double *azim_out, double *gain_out,
                             bas_stream_t stream);
+
+/* ---- per-source propagation delay (no reference counterpart) --------------------------------------
+ * delay [..] f64 (device), in SAMPLES, one value per chunk boundary laid out as the angles of the same call.  A source's
+ * delayed input x' replaces its input x; everything after that (chunk IRs, crossfade, FIR, mix, peak rules) is unchanged.
+ * For t = kK + j, 0 <= j < K:  d = d_k + (j / K)(d_{k+1} - d_k), clamped to [d_min, d_max] with fmax(fmin(.)) (a NaN
+ * reads as d_max);  u = j - d,  n = floor(u),  f = u - n,  i = kK + n  (binary64, relative to the chunk start: the bits do
+ * not depend on the absolute time);  x'(t) = sum_m c_m(f) x(i + m) in binary64, rounded to binary32 once:
+ *   interp 1 (cubic): m = -1..2, 4-point Lagrange in product form, c_-1 = -f(f-1)(f-2)/6, c_0 = (f+1)(f-1)(f-2)/2,
+ *     c_1 = -(f+1)f(f-2)/2, c_2 = (f+1)f(f-1)/6 (f = 0: exactly (0, 1, 0, 0)); d_min = 2;
+ *   interp 0 (linear): m = 0..1, (1 - f, f) (apply_hrtf.py:178-199's fractional delay, per sample); d_min = 1.
+ * Neither reads a sample later than t.  Samples outside the readable range are 0.  Nothing is validated on the device.
+ *   bas_delay_rows_f32: rows (g, s), g < n_groups, s < n_src: input x + g x_stride_g + s x_stride_s (sample 0; samples
+ *     -H .. -1 in front are readable history, H may be 0), delay + g d_stride_g + s d_stride_s ((T-1)/K + 2 boundaries),
+ *     output y + g y_stride_g + s y_stride_s, T samples (16-byte stores where the output row is 16-byte aligned).
+ *     lengths [n_groups n_src] (NULL: T each): the row's valid samples; reads at or past it are 0, and so are the
+ *     outputs.  max_delay: the upper clamp, which must leave the reads inside the history (d_min <= max_delay <= H - 2),
+ *     or 0 offline: the row's valid length + 4 (no output changes: every read past it lands before sample 0).  One launch;
+ *     T < 2^30, n_groups n_src <= 65535.  y must not overlap x's readable range.
+ *   bas_delay_carry_f32: the raw history of a stream block: row[0 .. H) = row[B .. B + H) for every (g, s) row (row =
+ *     x + g x_stride_g + s x_stride_s at the history's start), B < H (overlapping) included.  One launch.
+ *   bas_batch_pack_delay_f32: bas_batch_pack_gain_f32 (gain NULL: bas_batch_pack_f32) with item b's DELAYED input in its
+ *     segment: delay [B][n_src][n_q_max] is read where it is (no packed delay array), item b's reads are bounded by its
+ *     own valid length (the offline rule above), the gaps stay zeros.  Still one launch.
+ *   bas_stream_batch_pack_delay_f32: bas_stream_batch_pack_gain_f32 (gain NULL: no gain, gain_out ignored; head NULL:
+ *     head-relative angles) with session g's DELAYED block in its window slots [halo, halo + B): raw + g raw_stride_g +
+ *     s raw_stride_s holds the H carried raw samples of (g, s) (raw_stride_s >= H + B); the delayed samples read them
+ *     and the dense block (the same bits as bas_delay_rows_f32 on [history | block]), with delay [G][n_src][nb] clamped
+ *     to [d_min, max_delay] (d_min <= max_delay <= H - 2), and the raw block is copied behind the history, where
+ *     bas_delay_carry_f32 moves the last H raw samples to the front after the block.  Still one launch. */
+int bas_delay_rows_f32(const float *x, long x_stride_g, long x_stride_s, int H, const long *lengths, const double *delay,
+                       long d_stride_g, long d_stride_s, int n_groups, int n_src, long T, int K, int interp,
+                       double max_delay, float *y, long y_stride_g, long y_stride_s, bas_stream_t stream);
+int bas_delay_carry_f32(float *x, long x_stride_g, long x_stride_s, int n_groups, int n_src, int H, long B,
+                        bas_stream_t stream);
+int bas_stream_batch_pack_delay_f32(const float *blocks, const double *elev, const double *azim, const double *head,
+                                    const double *gain, const double *delay, int interp, double max_delay, float *raw,
+                                    long raw_stride_g, long raw_stride_s, int H, int n_sessions, int n_src, long B, int K,
+                                    int halo, float *x, long x_stride, double *elev_out, double *azim_out,
+                                    double *gain_out, long ang_stride, bas_stream_t stream);
+int bas_batch_pack_delay_f32(const float *sig, int n_items, int n_src, long N, const long *lengths, const long *offsets,
+                             const double *elev, const double *azim, const double *gain, const double *delay, int interp,
+                             long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
+                             double *gain_out, bas_stream_t stream);
 
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
