@@ -1,0 +1,148 @@
+// Cartesian scenes (include/bas.h "Cartesian scenes"): source positions [G][n_src][nb][3], the listener's
+// position and head orientation per boundary and an optional shoebox room's image list -> the angles, gains and delays
+// of every image source, [G][n_src n_img][nb], strided on both sides so that a stream renderer's views take them in
+// place.  One launch.
+#include "bas_internal.h"
+#include "bas_scene.h"
+
+#define SC_THREADS 256
+
+struct BasSceneArgs {
+    const double *pos; long ps_g, ps_s, ps_c;
+    const double *prev; long pp_g, pp_s;
+    double spc;
+    const double *lpos; long lp_g, lp_c;
+    const double *head; long h_g, h_c;
+    const double *src_gain; long sg_g, sg_s;
+    const double *room_size; const int32_t *images; const double *img_gain;
+    double spm, r_ref, dmin, dmax;
+    int n_src, n_img, nb;
+    double *elev, *azim, *gain; long a_g, a_s;
+    double *delay; long d_g, d_s;
+};
+
+// one thread per (g, s, i, c) item, c fastest (the stores of a wave are consecutive along c), grid-stride
+__global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneArgs A, long n_items) {
+    const long per_s = (long)A.n_img * A.nb, per_g = per_s * A.n_src;
+    const bool room = A.room_size != nullptr;
+    double Lx = 0.0, Ly = 0.0, Lz = 0.0;
+    if (room) {
+        Lx = A.room_size[0]; Ly = A.room_size[1]; Lz = A.room_size[2];
+    }
+    for (long it = blockIdx.x * (long)SC_THREADS + threadIdx.x; it < n_items; it += (long)gridDim.x * SC_THREADS) {
+        const long g = it / per_g, r0 = it - g * per_g;
+        const long s = r0 / per_s, r1 = r0 - s * per_s;
+        const long i = r1 / A.nb, c = r1 - i * A.nb;
+        const double *p = A.pos + g * A.ps_g + s * A.ps_s + c * A.ps_c;
+        double lx = 0.0, ly = 0.0, lz = 0.0, w = 1.0, x = 0.0, y = 0.0, z = 0.0;
+        if (A.lpos) {
+            const double *l = A.lpos + g * A.lp_g + c * A.lp_c;
+            lx = l[0]; ly = l[1]; lz = l[2];
+        }
+        if (A.head) {
+            const double *q = A.head + g * A.h_g + c * A.h_c;
+            w = q[0]; x = q[1]; y = q[2]; z = q[3];
+        }
+        int mx = 0, my = 0, mz = 0;
+        double ig = 1.0;
+        if (room) {
+            mx = A.images[3 * i]; my = A.images[3 * i + 1]; mz = A.images[3 * i + 2];
+            ig = A.img_gain[i];
+        }
+        // the two positions a chunk apart that give the source's velocity at this boundary: (c - 1, c); at c = 0 the
+        // caller's previous boundary, else (0, 1)
+        const bool moving = A.spc > 0.0 && (c > 0 || A.prev || A.nb > 1);
+        const double *a = p, *b = p;
+        if (moving) {
+            if (c > 0) a = p - A.ps_c;
+            else if (A.prev) a = A.prev + g * A.pp_g + s * A.pp_s;
+            else b = p + A.ps_c;
+        }
+        const double sg = A.src_gain ? A.src_gain[g * A.sg_g + s * A.sg_s + c] : 1.0;
+        const BasScenePoint o = bas_scene_point(p[0], p[1], p[2], lx, ly, lz, moving, a[0], a[1], a[2], b[0], b[1],
+                                                b[2], A.spc, room, Lx, Ly, Lz, mx, my, mz, A.head != nullptr,
+                                                w, x, y, z, sg, ig, A.spm, A.r_ref, A.dmin, A.dmax);
+        const long row = s * A.n_img + i;
+        const long to = g * A.a_g + row * A.a_s + c;
+        A.elev[to] = o.el;
+        A.azim[to] = o.az;
+        if (A.gain) A.gain[to] = o.gain;
+        if (A.delay) A.delay[g * A.d_g + row * A.d_s + c] = o.delay;
+    }
+}
+
+// the written layout [G][rows][nb] with strides (sg, ss, 1) addresses no element twice: every dimension of more than one
+// element, in ascending stride order, steps over the whole extent of the ones before it
+static bool sc_one_to_one(long G, long rows, long nb, long sg, long ss) {
+    long st[3] = {1, ss, sg}, ex[3] = {nb, rows, G};
+    if (st[1] > st[2]) {
+        const long t = st[1], e = ex[1];
+        st[1] = st[2]; ex[1] = ex[2]; st[2] = t; ex[2] = e;
+    }
+    long span = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (ex[k] == 1) continue;
+        if (st[k] < span) return false;
+        span = st[k] * ex[k];
+    }
+    return true;
+}
+
+static bool sc_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+extern "C" int bas_scene_params_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                                    const double *pos_prev, long prev_stride_g, long prev_stride_s,
+                                    double samples_per_chunk, const double *lpos, long lpos_stride_g,
+                                    long lpos_stride_c, const double *head,
+                                    long head_stride_g, long head_stride_c, const double *src_gain, long sg_stride_g,
+                                    long sg_stride_s, const double *room_size, const int32_t *images,
+                                    const double *img_gain, int n_img, double samples_per_metre, double r_ref,
+                                    double d_min, double d_max, int n_groups, int n_src, int nb, double *elev,
+                                    double *azim, double *gain, long a_stride_g, long a_stride_s, double *delay,
+                                    long d_stride_g, long d_stride_s, bas_stream_t stream) {
+    const char *fn = "bas_scene_params_f64";
+    BAS_REQUIRE(n_groups > 0 && n_src > 0 && nb > 0 && n_img > 0, BAS_E_SHAPE,
+                "%s: need n_groups, n_src, nb, n_img > 0 (G=%d n_src=%d nb=%d n_img=%d)", fn, n_groups, n_src, nb, n_img);
+    BAS_REQUIRE((long)n_src * n_img <= 0x7fffffffL, BAS_E_SHAPE, "%s: n_src n_img must be below 2^31", fn);
+    BAS_REQUIRE(room_size || n_img == 1, BAS_E_SHAPE, "%s: free field (room_size NULL) has one image, not %d", fn, n_img);
+    BAS_REQUIRE(samples_per_chunk >= 0.0 && samples_per_chunk < HUGE_VAL && prev_stride_g >= 0 && prev_stride_s >= 0 &&
+                (!pos_prev || samples_per_chunk > 0.0), BAS_E_SHAPE,
+                "%s: need finite samples_per_chunk >= 0 (> 0 with pos_prev) and non-negative pos_prev strides", fn);
+    BAS_REQUIRE(pos_stride_g >= 0 && pos_stride_s >= 0 && pos_stride_c >= 0 && lpos_stride_g >= 0 && lpos_stride_c >= 0 &&
+                head_stride_g >= 0 && head_stride_c >= 0 && sg_stride_g >= 0 && sg_stride_s >= 0, BAS_E_SHAPE,
+                "%s: input strides must be non-negative", fn);
+    BAS_REQUIRE(samples_per_metre > 0.0 && samples_per_metre < HUGE_VAL && r_ref > 0.0 && r_ref < HUGE_VAL && d_min >= 0.0 &&
+                d_max >= d_min, BAS_E_SHAPE,
+                "%s: need finite samples_per_metre, r_ref > 0 and 0 <= d_min <= d_max (%g, %g, %g, %g)", fn, samples_per_metre,
+                r_ref, d_min, d_max);
+    const long rows = (long)n_src * n_img;
+    BAS_REQUIRE(a_stride_g >= 0 && a_stride_s >= 0 && sc_one_to_one(n_groups, rows, nb, a_stride_g, a_stride_s), BAS_E_SHAPE,
+                "%s: angle/gain output strides (%ld, %ld, 1) overlap for [%d][%ld][%d]", fn, a_stride_g, a_stride_s, n_groups,
+                rows, nb);
+    BAS_REQUIRE(!delay || (d_stride_g >= 0 && d_stride_s >= 0 && sc_one_to_one(n_groups, rows, nb, d_stride_g, d_stride_s)),
+                BAS_E_SHAPE, "%s: delay output strides (%ld, %ld, 1) overlap for [%d][%ld][%d]", fn, d_stride_g, d_stride_s,
+                n_groups, rows, nb);
+    BAS_REQUIRE(pos && elev && azim && (!room_size || (images && img_gain)), BAS_E_NULL, "%s: null pointer", fn);
+    BAS_REQUIRE(elev != azim && (!gain || (gain != elev && gain != azim)) &&
+                (!delay || (delay != elev && delay != azim && delay != gain)), BAS_E_SHAPE,
+                "%s: two outputs are one buffer", fn);
+    BAS_REQUIRE(sc_aligned(pos, 8) && sc_aligned(pos_prev, 8) && sc_aligned(lpos, 8) && sc_aligned(head, 8) && sc_aligned(src_gain, 8) &&
+                sc_aligned(room_size, 8) && sc_aligned(img_gain, 8) && sc_aligned(images, 4) && sc_aligned(elev, 8) &&
+                sc_aligned(azim, 8) && sc_aligned(gain, 8) && sc_aligned(delay, 8), BAS_E_ALIGN,
+                "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
+    BasSceneArgs A;
+    A.pos = pos; A.ps_g = pos_stride_g; A.ps_s = pos_stride_s; A.ps_c = pos_stride_c;
+    A.prev = pos_prev; A.pp_g = prev_stride_g; A.pp_s = prev_stride_s; A.spc = samples_per_chunk;
+    A.lpos = lpos; A.lp_g = lpos_stride_g; A.lp_c = lpos_stride_c;
+    A.head = head; A.h_g = head_stride_g; A.h_c = head_stride_c;
+    A.src_gain = src_gain; A.sg_g = sg_stride_g; A.sg_s = sg_stride_s;
+    A.room_size = room_size; A.images = images; A.img_gain = img_gain;
+    A.spm = samples_per_metre; A.r_ref = r_ref; A.dmin = d_min; A.dmax = d_max;
+    A.n_src = n_src; A.n_img = n_img; A.nb = nb;
+    A.elev = elev; A.azim = azim; A.gain = gain; A.a_g = a_stride_g; A.a_s = a_stride_s;
+    A.delay = delay; A.d_g = d_stride_g; A.d_s = d_stride_s;
+    const long n_items = (long)n_groups * rows * nb;
+    const int blocks = bas_grid_for(n_items, 8 * bas_device_cus());
+    hipLaunchKernelGGL(bas_scene_params_kernel, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
+    return bas_check_launch("bas_scene_params_f64");
+}

@@ -1,0 +1,426 @@
+"""Cartesian scenes: positions in, binaural out.
+
+A renderer consumes, per source and chunk boundary, a direction (elevation, azimuth), a gain (§3.10) and a propagation
+delay in samples (§3.11), relative to the listener's head (§3.9).  This module turns what a scene has - source positions,
+the listener's position and head orientation, perhaps an axis-aligned shoebox room - into those four arrays, on the
+device, and wraps the renderers that consume them.
+
+Conventions (the reference's, sphere.py:51-56): metres in the world frame, +y front, +z up, +x right; azimuth grows to
+the left.  The room occupies [0, L_a] on each axis.  For source position p, image index m = (mx, my, mz), listener
+position l, head orientation q, in binary64 and in this order:
+
+    1. q_a = m L_a + (m even ? p_a : L_a - p_a)          the image's position (free field: q = p)
+    1b. with a chunk size: q <- q - u d, where the image was when the sound left it (u: its velocity, d: the time of flight)
+    2. v = q - l,  r = sqrt(vx^2 + vy^2 + vz^2)
+    3. v_h = R(q / |q|)^T v                               (skipped without a head)
+    4. el = atan2(v_hz, hypot(v_hx, v_hy)),  az = atan2(-v_hx, v_hy)      (v == 0 exactly: el = az = 0)
+    5. gain = src_gain img_gain r_ref / fmax(r, r_ref)    the 1/r law, flat inside r_ref
+    6. delay = fmax(fmin(r fs / c, d_max), d_min)         samples
+
+Step 1b makes the Doppler shift that of a moving source, f / (1 + v/c) for one receding at v: the delay of §3.11 is indexed
+by the time of reception, and the distance at that time alone would give f (1 - v/c).  The velocity at a boundary is the
+difference to the boundary before it (at a call's first boundary: to `pos_prev`, a stream's carry, else to the one after
+it) over the chunk; for a subsonic velocity u per sample, w = q - l and A = (c / fs)^2 - |u|^2, the time of flight
+d = (sqrt((w.u)^2 + A |w|^2) - w.u) / A solves |w - u d| = d c / fs exactly for a straight path.
+
+`scene_params` is the float64 numpy definition, `scene_params_device` the kernel (bas_scene_params_f64, one launch).  The
+images of a source are extra rows of the same render, row = s n_img + i; they share the source's signal, which the delay
+kernel reads with a source stride of 0 (`render_scene`) or which one broadcast copy replicates (`SceneStreamRenderer`).
+Walls reflect all frequencies alike (one coefficient per wall); the image model holds for rigid or nearly rigid walls.
+"""
+import numpy as np
+
+from . import _hip, sphere, propagation
+
+MAX_ORDER = 3
+SPEED_OF_SOUND = 343.0
+
+
+def shoebox_images(order):
+    """Image indices of a shoebox room up to reflection order `order`: int32 [n_img, 3], all (mx, my, mz) with
+    |mx| + |my| + |mz| <= order, sorted by (|mx| + |my| + |mz|, mx, my, mz): row 0 is the direct path.  1, 7, 25, 63
+    images for orders 0 to 3."""
+    order = int(order)
+    if not 0 <= order <= MAX_ORDER:
+        raise ValueError(f"order must be in 0..{MAX_ORDER}, got {order}")
+    rng = range(-order, order + 1)
+    ms = sorted((abs(x) + abs(y) + abs(z), x, y, z) for x in rng for y in rng for z in rng if abs(x) + abs(y) + abs(z) <= order)
+    return np.array([m[1:] for m in ms], dtype=np.int32).reshape(-1, 3)
+
+
+def image_gains(images, beta):
+    """The reflection gain of every image: for wall coefficients beta = (x0, x1, y0, y1, z0, z1) the product over the axes
+    of beta_lo^n_lo beta_hi^n_hi, where index m > 0 hits the high wall ceil(m/2) times and the low wall floor(m/2) times,
+    and m < 0 the other way round.  float64 [n_img]."""
+    m = np.asarray(images, dtype=np.int64).reshape(-1, 3)
+    b = np.asarray(beta, dtype=np.float64).reshape(3, 2)
+    a = np.abs(m)
+    more, fewer = (a + 1) // 2, a // 2                                 # the wall met first is met once more for odd m
+    n_hi, n_lo = np.where(m > 0, more, fewer), np.where(m > 0, fewer, more)
+    return np.prod(b[:, 0] ** n_lo * b[:, 1] ** n_hi, axis=1)
+
+
+class Room:
+    """An axis-aligned shoebox room occupying [0, size_a] on each axis.  size: (Lx, Ly, Lz) in metres; beta: the walls'
+    reflection coefficients (x0, x1, y0, y1, z0, z1), |beta| <= 1, or one value for all six; order: the highest
+    reflection order rendered (0..3; n_img = 1, 7, 25, 63 rows per source).  ValueError otherwise."""
+
+    def __init__(self, size, beta=0.9, order=1):
+        size = np.asarray(size, dtype=np.float64)
+        if size.shape != (3,) or not np.isfinite(size).all() or not (size > 0).all():
+            raise ValueError("room size must be three finite lengths > 0")
+        beta = np.asarray(beta, dtype=np.float64)
+        if beta.shape == ():
+            beta = np.full(6, float(beta))
+        if beta.shape != (6,) or not np.isfinite(beta).all() or not (np.abs(beta) <= 1).all():
+            raise ValueError("beta must be six reflection coefficients (x0, x1, y0, y1, z0, z1) with |beta| <= 1")
+        self.size, self.beta = size, beta
+        self.images = shoebox_images(order)
+        self.order = int(order)
+        self.gains = image_gains(self.images, beta)
+        self.n_img = self.images.shape[0]
+        self._device = {}
+
+    def device_arrays(self, dev):
+        """(size [3] f64, images [n_img, 3] i32, gains [n_img] f64) on `dev`, uploaded once per device."""
+        import torch
+        key = str(dev)
+        if key not in self._device:
+            self._device[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                                      for a in (self.size, self.images, self.gains))
+        return self._device[key]
+
+
+def _n_img(room):
+    if room is not None and not isinstance(room, Room):
+        raise ValueError("room must be a scene.Room or None")
+    return 1 if room is None else room.n_img
+
+
+def _scalars(fs, c, r_ref, interp, max_delay):
+    """(samples per metre, r_ref, d_min, d_max) of a call, validated (ValueError)."""
+    fs, c, r_ref = float(fs), float(c), float(r_ref)
+    if not (np.isfinite(fs) and fs > 0 and np.isfinite(c) and c > 0 and np.isfinite(r_ref) and r_ref > 0):
+        raise ValueError("fs, c and r_ref must be finite and > 0")
+    propagation.interp_code(interp)
+    d_max = np.inf if max_delay is None else propagation.check_max_delay(max_delay, interp)
+    return fs / c, r_ref, propagation.D_MIN[interp], d_max
+
+
+def _is_device(a):
+    import torch
+    return isinstance(a, torch.Tensor) and a.is_cuda
+
+
+def _host_array(name, a, shape, room=None):
+    """Host data as a float64 array of `shape`: ValueError for another shape, non-finite values or, with a room,
+    positions outside it."""
+    arr = np.asarray(a.numpy() if hasattr(a, "numpy") else a, dtype=np.float64)
+    if arr.shape != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {arr.shape}")
+    if not np.isfinite(arr).all():
+        raise ValueError(f"{name} must be finite")
+    if room is not None and arr.size and ((arr < 0).any() or (arr > room.size).any()):
+        raise ValueError(f"{name} must lie inside the room [0, {tuple(room.size)}]")
+    return arr
+
+
+def _arg_shapes(pos_shape):
+    """The shapes of (listener_pos, head, src_gain) that go with pos (..., n_src, nb, 3); ValueError for a pos of
+    another form."""
+    s = tuple(pos_shape)
+    if len(s) < 3 or s[-1] != 3:
+        raise ValueError(f"pos must have shape (..., n_src, nb, 3), got {s}")
+    lead, nb = s[:-3], s[-2]
+    return lead + (nb, 3), lead + (nb, 4), s[:-1]
+
+
+def check_scene_args(pos_shape, pos, listener_pos, head, src_gain, room):
+    """Every argument of a scene against `pos_shape`, before any device work: host data is validated (shapes, finite
+    values, non-zero heads, positions inside the room) and returned as float64 arrays; device tensors are checked for
+    shape and dtype only and returned as they are.  Returns (pos, listener_pos, head, src_gain), None kept."""
+    import torch
+    _n_img(room)
+    shapes = _arg_shapes(pos_shape)
+    out = []
+    for name, a, shape, inside in (("pos", pos, tuple(pos_shape), room), ("listener_pos", listener_pos, shapes[0], room),
+                                   ("head", head, shapes[1], None), ("src_gain", src_gain, shapes[2], None)):
+        if a is None:
+            if name == "pos":
+                raise ValueError("pos is required")
+            out.append(None)
+        elif _is_device(a):
+            if tuple(a.shape) != shape or a.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 tensor of shape {shape}")
+            out.append(a)
+        else:
+            arr = _host_array(name, a, shape, inside)
+            if name == "head":
+                sphere.check_head(arr)
+            out.append(arr)
+    return tuple(out)
+
+
+def _check_motion(chunksize, pos_prev, pos_shape, room):
+    """(samples per chunk or 0.0, pos_prev): chunksize None means no motion correction; a host pos_prev is validated
+    like pos ((..., n_src, 3)), a device one checked for shape and dtype only."""
+    import torch
+    if chunksize is None:
+        if pos_prev is not None:
+            raise ValueError("pos_prev needs chunksize")
+        return 0.0, None
+    spc = float(chunksize)
+    if not (np.isfinite(spc) and spc > 0):
+        raise ValueError("chunksize must be finite and > 0")
+    if pos_prev is None:
+        return spc, None
+    shape = tuple(pos_shape[:-2]) + (3,)
+    if _is_device(pos_prev):
+        if tuple(pos_prev.shape) != shape or pos_prev.dtype != torch.float64:
+            raise ValueError(f"pos_prev must be a float64 tensor of shape {shape}")
+        return spc, pos_prev
+    return spc, _host_array("pos_prev", pos_prev, shape, room)
+
+
+def scene_params(pos, fs, listener_pos=None, head=None, room=None, src_gain=None, c=SPEED_OF_SOUND, r_ref=1.0,
+                 interp="cubic", max_delay=None, chunksize=None, pos_prev=None):
+    """The float64 definition (numpy; the module's steps).  pos (..., n_src, nb, 3): source positions at the nb chunk
+    boundaries; fs: sample rate; listener_pos (..., nb, 3) or None (the origin); head (..., nb, 4) quaternions (w, x, y, z)
+    or None (the identity); room: a Room or None (free field); src_gain (..., n_src, nb) or None (1); c: speed of sound
+    (m/s); r_ref: the distance of unit gain, inside which the 1/r law is flat; interp: the delay's interpolator (its d_min
+    is the lower clamp); max_delay: the upper clamp in samples (a stream's bound), None offline (no clamp).
+    chunksize: samples between boundaries, which turns step 1b on (None: the distance at reception, no motion
+    correction); pos_prev (..., n_src, 3): the sources' positions one chunk before the first boundary, or None.
+    Returns (elev, azim, gain, delay), float64 (..., n_src n_img, nb), row s n_img + i for image i of source s.
+    ValueError for non-finite values, wrong shapes, zero-norm heads and, with a room, positions outside it."""
+    spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
+    if any(_is_device(a) for a in (pos, listener_pos, head, src_gain)):
+        raise ValueError("scene_params takes host arrays (scene_params_device takes device tensors)")
+    if _is_device(pos_prev):
+        raise ValueError("scene_params takes host arrays (scene_params_device takes device tensors)")
+    p, l, q, sg = check_scene_args(np.shape(pos), pos, listener_pos, head, src_gain, room)
+    spc, prev = _check_motion(chunksize, pos_prev, p.shape, room)
+
+    def image(a):                                                      # (..., n_src, nb, 3) -> (..., n_src, n_img, nb, 3)
+        a = a[..., :, None, :, :]
+        if room is None:
+            return a
+        m = room.images[:, None, :]                                    # (n_img, 1, 3)
+        return m.astype(np.float64) * room.size + np.where(m % 2 != 0, room.size - a, a)
+    ends = None                                                        # the positions a chunk apart around each boundary
+    if spc and prev is not None:
+        ends = np.concatenate([prev[..., None, :], p[..., :-1, :]], axis=-2), p
+    elif spc and p.shape[-2] > 1:
+        ends = (np.concatenate([p[..., :1, :], p[..., :-1, :]], axis=-2), np.concatenate([p[..., 1:2, :], p[..., 1:, :]], axis=-2))
+    p = image(p)
+    if l is None:
+        l = np.zeros(3)
+    else:
+        l = l[..., None, None, :, :]                                   # (..., 1, 1, nb, 3)
+    if ends is not None:
+        u = (image(ends[1]) - image(ends[0])) / spc
+        w = p - l
+        ux, uy, uz, wx, wy, wz = u[..., 0], u[..., 1], u[..., 2], w[..., 0], w[..., 1], w[..., 2]
+        A = 1.0 / (spm * spm) - (ux * ux + uy * uy + uz * uz)
+        wu = wx * ux + wy * uy + wz * uz
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = (np.sqrt(wu * wu + A * (wx * wx + wy * wy + wz * wz)) - wu) / A
+            p = np.where((A > 0.0)[..., None], p - u * d[..., None], p)
+    v = p - l
+    vx, vy, vz = v[..., 0], v[..., 1], v[..., 2]
+    r = np.sqrt(vx * vx + vy * vy + vz * vz)
+    at_listener = (vx == 0) & (vy == 0) & (vz == 0)
+    if q is not None:
+        q = q[..., None, None, :, :]
+        w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+        n = np.sqrt(w * w + x * x + y * y + z * z)
+        w, x, y, z = w / n, x / n, y / n, z / n
+        xh = (1.0 - 2.0 * (y * y + z * z)) * vx + 2.0 * (x * y + w * z) * vy + 2.0 * (x * z - w * y) * vz
+        yh = 2.0 * (x * y - w * z) * vx + (1.0 - 2.0 * (x * x + z * z)) * vy + 2.0 * (y * z + w * x) * vz
+        zh = 2.0 * (x * z + w * y) * vx + 2.0 * (y * z - w * x) * vy + (1.0 - 2.0 * (x * x + y * y)) * vz
+        vx, vy, vz = xh, yh, zh
+    el = np.where(at_listener, 0.0, np.arctan2(vz, np.hypot(vx, vy)))
+    az = np.where(at_listener, 0.0, np.arctan2(-vx, vy))
+    sg = 1.0 if sg is None else sg[..., :, None, :]                    # (..., n_src, 1, nb)
+    ig = 1.0 if room is None else room.gains[:, None]                  # (n_img, 1)
+    gain = sg * ig * r_ref / np.fmax(r, r_ref)
+    delay = np.fmax(np.fmin(r * spm, d_max), d_min)
+    shape = r.shape[:-3] + (r.shape[-3] * r.shape[-2], r.shape[-1])
+    return tuple(np.ascontiguousarray(np.broadcast_to(a, r.shape)).reshape(shape) for a in (el, az, gain, delay))
+
+
+def _unit_last(t):
+    """A tensor the kernel can address: unit stride on the last axis, no negative strides (a copy otherwise)."""
+    return t if t.stride(-1) == 1 and all(s >= 0 for s in t.stride()) else t.contiguous()
+
+
+def scene_params_device(pos, fs, listener_pos=None, head=None, room=None, src_gain=None, c=SPEED_OF_SOUND, r_ref=1.0,
+                        interp="cubic", max_delay=None, out=None, chunksize=None, pos_prev=None):
+    """scene_params on the GPU (bas_scene_params_f64, one launch).  pos [G, n_src, nb, 3] or [n_src, nb, 3] and the other
+    arguments with the same leading axis.  Host arrays are validated as scene_params validates them, then uploaded;
+    device tensors must be float64 and are checked for shape and dtype only (nothing is validated on the device: a
+    non-finite position gives non-finite angles, a NaN delay reads as d_max).
+    out = (elev, azim, gain, delay): float64 device tensors [(G,) n_src n_img, nb] with unit stride on the last axis -
+    strided views such as a stream renderer's trajectory_views(B) + (gain_view(B), delay_view(B)) serve; elev, azim and
+    gain must share their strides; gain and delay may each be None (not computed).  Returns (elev, azim, gain, delay)."""
+    import torch
+    spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
+    pos_shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
+    if len(pos_shape) not in (3, 4):
+        raise ValueError(f"pos must have shape [G, n_src, nb, 3] or [n_src, nb, 3], got {pos_shape}")
+    args = check_scene_args(pos_shape, pos, listener_pos, head, src_gain, room)
+    spc, prev = _check_motion(chunksize, pos_prev, pos_shape, room)
+    n_img = _n_img(room)
+    tensors = [t for t in args + (prev,) + tuple(out or ()) if _is_device(t)]
+    dev = tensors[0].device if tensors else _hip.require_gpu()
+    p, l, q, sg, prev = (None if a is None else _unit_last(a.to(dev) if _is_device(a) else torch.from_numpy(a).to(dev))
+                         for a in args + (prev,))
+    batched = len(pos_shape) == 4
+    G = pos_shape[0] if batched else 1
+    n_src, nb = pos_shape[-3], pos_shape[-2]
+    if min(G, n_src, nb) < 1:
+        raise ValueError("pos must hold at least one group, source and boundary")
+    shape = pos_shape[:-3] + (n_src * n_img, nb)
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(4))
+    if len(out) != 4 or out[0] is None or out[1] is None:
+        raise ValueError("out must be (elev, azim, gain, delay); gain and delay may be None")
+    for t in out:
+        if t is not None and not (_is_device(t) and t.device == dev and t.dtype == torch.float64 and tuple(t.shape) == shape
+                                  and t.stride(-1) == 1):
+            raise ValueError(f"out tensors must be float64 of shape {shape} on {dev} with unit stride on the last axis")
+    eo, ao, go, do = out
+    if ao.stride() != eo.stride() or (go is not None and go.stride() != eo.stride()):
+        raise ValueError("out's elev, azim and gain must have equal strides")
+
+    def gs(t, k):                                                      # (group stride, stride of axis k) of an argument
+        return (0, 0) if t is None else (t.stride(0) if batched else 0, t.stride(k))
+    size, images, gains = (None, None, None) if room is None else room.device_arrays(dev)
+    with _hip.on_device(dev):
+        _hip.call("bas_scene_params_f64", _hip.ptr(p), *gs(p, -3), p.stride(-2), _hip.ptr(prev), *gs(prev, -2), spc,
+                  _hip.ptr(l), *gs(l, -2), _hip.ptr(q),
+                  *gs(q, -2), _hip.ptr(sg), *gs(sg, -2), _hip.ptr(size), _hip.ptr(images), _hip.ptr(gains), n_img, spm,
+                  r_ref, d_min, d_max, G, n_src, nb, _hip.ptr(eo), _hip.ptr(ao), _hip.ptr(go), *gs(eo, -2), _hip.ptr(do),
+                  *gs(do, -2), _hip.current_stream(dev))
+    return eo, ao, go, do
+
+
+def _table_L(tbl):
+    """IR length of a device table or a host struct with the reference's fields (no device work)."""
+    return int(np.shape(tbl.irs_left)[1]) // int(tbl.upsampling)
+
+
+def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=None, head=None, room=None, src_gain=None,
+                 normalize="mix", interp="cubic", c=SPEED_OF_SOUND, r_ref=1.0, fused=None):
+    """Render and mix moving sources given by their positions (render_sources with the geometry done on the device).
+
+    signals: [n_src, N] (numpy or tensor); pos: [n_src, n_chunks + 1, 3], the sources' positions in metres at t = 0, K, ..,
+    in_length; listener_pos [n_chunks + 1, 3], head [n_chunks + 1, 4], src_gain [n_src, n_chunks + 1], room: as for
+    scene_params (host arrays validated, device tensors checked for shape and dtype only).  With a room every source is
+    rendered as room.n_img image sources (row s n_img + i), all reading the source's one signal.
+    Three steps: the scene kernel (with step 1b: moving sources are heard where they were); one bas_delay_rows_f32 launch that writes every image's delayed input (source stride
+    0: nothing is replicated); render_angles_device with the gains.  Returns what render_sources returns: a device tensor
+    (out_length, 2), peak-normalised ("mix") or not ("none")."""
+    import torch
+    from .apply_hrtf import as_device_table, padded_rows, render_lengths, render_angles_device
+    K, S = int(chunksize), int(subchunksize)
+    assert K % S == 0, 'subchunksize does not divide chunksize evenly'
+    if normalize not in ("mix", "none"):
+        raise ValueError("normalize must be 'mix' or 'none'")
+    sig = torch.as_tensor(signals)
+    assert sig.dim() == 2, 'signals must be [n_src, N]'
+    n_src, n = sig.shape
+    n_img = _n_img(room)
+    if n_src < 1 or n_src * n_img > 65535:
+        raise ValueError("render_scene renders 1..65535 rows (n_src n_img) in one call")
+    in_length, _ = render_lengths(n, K, _table_L(tbl))
+    n_q = in_length // K + 1
+    _scalars(fs, c, r_ref, interp, None)
+    args = check_scene_args((n_src, n_q, 3), pos, listener_pos, head, src_gain, room)
+    tbl = as_device_table(tbl)
+    dev = tbl.device
+    args = tuple(a.to(dev) if _is_device(a) else a for a in args)
+    if not any(_is_device(a) for a in args):
+        args = (torch.from_numpy(args[0]).to(dev),) + args[1:]        # (so that the scene runs on the table's device)
+    el, az, g, d = scene_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp, chunksize=K)
+    x = padded_rows(n_src * n_img, in_length, dev)
+    if n:
+        src = sig.to(device=dev, dtype=torch.float32).contiguous()
+        lens = torch.full((n_src * n_img,), n, dtype=torch.int64, device=dev)
+        # groups = sources, rows of a group = its images: the input's row stride is 0, every image reads the one signal
+        propagation.delay_rows_device(src[:1].expand(n_img, n), d[:n_img], K, interp, x[:n_img], lengths=lens,
+                                      groups=(n_src, src.stride(0), n_img * d.stride(0), n_img * x.stride(0)))
+    y, _ = render_angles_device(x, K, S, tbl, el, az, normalize, fused=fused, gain=g)
+    return y.t()
+
+
+class SceneStreamRenderer:
+    """A StreamRenderer fed with positions: every block's angles, gains and delays are written by the scene kernel straight
+    into the inner renderer's own buffers (one launch in front of the block's graph, where §3.9's head launch sits)."""
+
+    def __init__(self, tbl, n_src, chunksize, subchunksize, fs, max_distance, room=None, interp="cubic", c=SPEED_OF_SOUND,
+                 r_ref=1.0, graph=True, copy_out=True):
+        """n_src sources (each rendered as room.n_img image sources: the inner StreamRenderer has n_src n_img rows);
+        max_distance: the largest source-to-listener path in metres, images included (a longer one is heard at
+        max_distance's delay: the clamp of §3.11); the stream carries max_distance / c * fs samples of history per row.
+        graph, copy_out: as for StreamRenderer."""
+        from .stream import StreamRenderer
+        self.n_src, self.n_img = int(n_src), _n_img(room)
+        if self.n_src < 1:
+            raise ValueError("n_src must be >= 1")
+        self._spm, self.r_ref, _, _ = _scalars(fs, c, r_ref, interp, None)
+        self.fs, self.c, self.room, self.interp = float(fs), float(c), room, interp
+        md = float(max_distance)
+        if not (np.isfinite(md) and md > 0):
+            raise ValueError("max_distance must be finite and > 0")
+        self.max_distance = md
+        self.max_delay = propagation.check_max_delay(md * self._spm, interp)
+        self.K = int(chunksize)
+        assert self.K % int(subchunksize) == 0, 'subchunksize does not divide chunksize evenly'
+        self._prev = None                                 # the sources' positions one chunk before the next block (device)
+        self.inner = StreamRenderer(tbl, self.n_src * self.n_img, chunksize, subchunksize, graph=graph, copy_out=copy_out,
+                                    max_delay=self.max_delay, interp=interp)
+
+    def prepare(self, B):
+        """StreamRenderer.prepare for blocks of B samples, with the gains live (so that the captured graph is the one
+        process() replays)."""
+        self.inner.gain_view(B)
+        self.inner.prepare(B)
+
+    def check_block(self, block_shape, pos, listener_pos, head, src_gain):
+        """The arguments of process() against a block of `block_shape`, before any device work (ValueError); returns
+        (B, checked (pos, listener_pos, head, src_gain))."""
+        if len(block_shape) != 2 or block_shape[0] != self.n_src:
+            raise ValueError(f"block must be [{self.n_src}, B]")
+        B = int(block_shape[1])
+        if B <= 0 or B % self.K:
+            raise ValueError("block length must be a positive multiple of the chunk size")
+        return B, check_scene_args((self.n_src, B // self.K + 1, 3), pos, listener_pos, head, src_gain, self.room)
+
+    def process(self, block, pos, listener_pos=None, head=None, src_gain=None):
+        """block: [n_src, B] (B a multiple of the chunk size); pos: [n_src, B/K + 1, 3], the sources' positions at the
+        block's chunk boundaries t0, t0 + K, .., t0 + B; listener_pos [B/K + 1, 3], head [B/K + 1, 4], src_gain
+        [n_src, B/K + 1]: as for scene_params_device.  Consecutive blocks should repeat their shared boundary.
+        Returns the B stereo samples this block completes as a device tensor (B, 2), un-normalised."""
+        import torch
+        blk = torch.as_tensor(block)
+        B, args = self.check_block(tuple(blk.shape), pos, listener_pos, head, src_gain)
+        st, dev = self.inner, self.inner.tbl.device
+        out = st.trajectory_views(B) + (st.gain_view(B), st.delay_view(B))
+        args = tuple(a.to(dev) if _is_device(a) else a for a in args)
+        p = args[0] if _is_device(args[0]) else torch.from_numpy(args[0]).to(dev)
+        el, az, g, d = scene_params_device(p, self.fs, args[1], args[2], self.room, args[3], self.c, self.r_ref,
+                                           self.interp, self.max_delay, out=out, chunksize=self.K, pos_prev=self._prev)
+        self._prev = p[:, -2].clone()                     # (the velocity at the next block's first boundary)
+        x = st.input_view(B)                                           # [n_src n_img, B]: every image's copy of the block
+        x.view(self.n_src, self.n_img, B).copy_(blk.to(dev).unsqueeze(1))   # (one broadcast copy, converts to float32)
+        return st.process(x, el, az, gain=g, delay=d)
+
+    def finish(self):
+        """The last L - 1 samples (StreamRenderer.finish)."""
+        return self.inner.finish()
+
+    @property
+    def peak(self):
+        """max |sample| emitted so far."""
+        return self.inner.peak

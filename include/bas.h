@@ -489,6 +489,47 @@ int bas_batch_pack_delay_f32(const float *sig, int n_items, int n_src, long N, c
                              long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
                              double *gain_out, bas_stream_t stream);
 
+/* ---- Cartesian scenes (no reference counterpart) -----------------------------------------------------
+ * Source positions, the listener's pose and an optional axis-aligned shoebox room -> the angles, gains and delays of every
+ * image source at every chunk boundary: what the three sections above consume.  All float64 on the device unless stated,
+ * all strides in elements and >= 0 (0 repeats), metres in the world frame (+y front, +z up, +x right: sphere.py:51-56).
+ *   pos [G][n_src][nb][3] at pos[g pos_stride_g + s pos_stride_s + c pos_stride_c + k];
+ *   lpos [G][nb][3] at lpos[g lpos_stride_g + c lpos_stride_c + k]: the listener's position; NULL: the origin;
+ *   head [G][nb][4] at head[g head_stride_g + c head_stride_c + k]: (w, x, y, z) as in "head tracking" (rotates head into
+ *     world coordinates, any non-zero norm, normalised here); NULL: the identity;
+ *   src_gain [G][n_src][nb] at src_gain[g sg_stride_g + s sg_stride_s + c]: a multiplier (volume, fades); NULL: 1;
+ *   room_size [3] (metres; the room occupies [0, L_a] on axis a), images int32 [n_img][3], img_gain [n_img].
+ *     room_size NULL: free field, n_img must be 1 (the one image is the source itself; images, img_gain are not read).
+ * For group g, source s, image i, boundary c, in binary64 without contraction, in this order:
+ *   1. q_a = m L_a + (m even ? p_a : L_a - p_a) for m = images[i][a] (m = 0: the source; 1: mirrored at the wall a = L_a;
+ *      -1: at the wall a = 0); free field: q = p;
+ *   1b. (samples_per_chunk > 0 only) a moving source is heard where it was when the sound left it.  The image's velocity
+ *      per sample is u = (q(b) - q(a)) / samples_per_chunk for the source's positions (a, b) = (c - 1, c); at c = 0,
+ *      (pos_prev, 0) when pos_prev [G][n_src][3] (at [g prev_stride_g + s prev_stride_s + k]: the boundary before this
+ *      call's first, a stream's carry) is given, else (0, 1), else (nb == 1) u = 0.  With w = q - listener and
+ *      A = 1 / samples_per_metre^2 - |u|^2 > 0 (subsonic; otherwise no correction), the time of flight in samples is
+ *      d = (sqrt((w.u)^2 + A |w|^2) - w.u) / A, the root of |w - u d| = d / samples_per_metre, and q becomes q - u d.
+ *      A source at rest keeps q bit for bit.  samples_per_chunk == 0: no correction (the distance at reception);
+ *   2. v = q - listener;  r = sqrt(vx^2 + vy^2 + vz^2);
+ *   3. v_h = R(head / |head|)^T v (the matrix of "head tracking"; skipped when head is NULL);
+ *   4. el = atan2(v_hz, hypot(v_hx, v_hy)),  az = atan2(-v_hx, v_hy), not wrapped;  v == 0 exactly: el = az = 0;
+ *   5. gain = src_gain img_gain[i] r_ref / fmax(r, r_ref);
+ *   6. delay = fmax(fmin(r samples_per_metre, d_max), d_min)   (samples; samples_per_metre = fs / c).
+ * Outputs, row = s n_img + i: elev, azim, gain at [g a_stride_g + row a_stride_s + c], delay at [g d_stride_g +
+ * row d_stride_s + c]; gain and delay may each be NULL (not written).  Each output layout must address every element once
+ * and the outputs must be distinct buffers (BAS_E_SHAPE); samples_per_chunk finite and >= 0, > 0 with pos_prev; n_groups, n_src, nb, n_img > 0, samples_per_metre and r_ref
+ * finite and > 0, 0 <= d_min <= d_max (d_max may be +inf) (BAS_E_SHAPE); pos, elev, azim and, with a room, images and
+ * img_gain are required (BAS_E_NULL); float64 pointers 8-byte aligned, images 4-byte (BAS_E_ALIGN).  Nothing is validated
+ * on the device.  One launch. */
+int bas_scene_params_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                         const double *pos_prev, long prev_stride_g, long prev_stride_s, double samples_per_chunk,
+                         const double *lpos, long lpos_stride_g, long lpos_stride_c, const double *head, long head_stride_g,
+                         long head_stride_c, const double *src_gain, long sg_stride_g, long sg_stride_s,
+                         const double *room_size, const int32_t *images, const double *img_gain, int n_img,
+                         double samples_per_metre, double r_ref, double d_min, double d_max, int n_groups, int n_src,
+                         int nb, double *elev, double *azim, double *gain, long a_stride_g, long a_stride_s,
+                         double *delay, long d_stride_g, long d_stride_s, bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's
