@@ -122,6 +122,9 @@ SIGNATURES = {
     "bas_batch_pack_delay_f32": (_c_int, [_c_void_p, _c_int, _c_int, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                           _c_void_p, _c_void_p, _c_int, _c_long, _c_int, _c_long, _c_void_p, _c_long,
                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    # per-source colour
+    "bas_color_rows_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_int, _c_void_p, _c_void_p, _c_long, _c_long, _c_long,
+                                    _c_int, _c_int, _c_int, _c_long, _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),
     # Cartesian scenes
     "bas_scene_params_f64": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, ctypes.c_double,
                                       _c_void_p, _c_long, _c_long, _c_void_p, _c_long,

@@ -483,7 +483,7 @@ def _params_to_device(tbl, idx, w):
 
 
 def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize="mix", fused=None, gain=None, delay=None,
-                   interp="cubic"):
+                   interp="cubic", color=None):
     """Render and mix many independently moving sources.
 
     signals: [n_src, N] (numpy or tensor); elev/azim: float64 [n_src, n_chunks+1]
@@ -499,6 +499,10 @@ def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize=
     §3.11): the source's input becomes its delayed input (propagation.delayed_inputs; interp "cubic" or "linear"), written
     by one bas_delay_rows_f32 launch straight into the padded rows the render reads.  Host delays must be finite and at
     least the interpolator's d_min (ValueError); device tensors are checked for shape and dtype only.
+    color: None, or float32 [n_src, n_chunks+1, M] (1 <= M <= 64), source s's FIR coefficients at each chunk boundary, or
+    [n_src, M], the same filter throughout: the source's (delayed) input becomes its coloured input
+    (propagation.colored_inputs), written by one bas_color_rows_f32 launch into the padded rows the render reads.  Host
+    coefficients must be finite (ValueError); device tensors are checked for shape and dtype only.
     """
     import torch
     from . import propagation
@@ -517,13 +521,18 @@ def render_sources(signals, chunksize, subchunksize, elev, azim, tbl, normalize=
         raise ValueError(f"elev/azim must have shape ({n_src}, {n_q})")
     g = None if gain is None else gain_to_device(gain, (n_src, n_q), dev)[0]
     d = None if delay is None else propagation.delay_to_device(delay, (n_src, n_q), interp, dev)
+    col = None if color is None else propagation.color_to_device(color, n_src, n_q, dev)
     x = padded_rows(n_src, in_length, dev)                                   # :406
+    pre = x if col is None else padded_rows(n_src, in_length, dev)           # with a colour: the rows in front of it
     if d is None:
-        x[:, :n] = sig.to(device=dev, dtype=torch.float32)
+        pre[:, :n] = sig.to(device=dev, dtype=torch.float32)
     elif n:                                                                  # delayed inputs, read up to n, zero beyond
         src = sig.to(device=dev, dtype=torch.float32).contiguous()
         lens = torch.full((n_src,), n, dtype=torch.int64, device=dev)
-        propagation.delay_rows_device(src, d, chunksize, interp, x, lengths=lens)
+        propagation.delay_rows_device(src, d, chunksize, interp, pre, lengths=lens)
+    if col is not None and n:                                                # coloured inputs, zero from n on
+        lens = torch.full((n_src,), n, dtype=torch.int64, device=dev)
+        propagation.color_rows_device(pre, col, chunksize, x, lengths=lens)
     idx_t, w_t = _params_to_device(tbl, idx, w)
     y, _ = render_params_device(x, chunksize, subchunksize, tbl, idx_t, w_t, normalize, fused=fused, gain=g)
     return y.t()

@@ -192,3 +192,189 @@ def delayed_inputs_device(x, K, delay, interp="cubic", out=None, lengths=None):
         lens = torch.as_tensor(np.asarray(lengths, dtype=np.int64).reshape(R)).to(dev)
     delay_rows_device(xs, d, K, interp, out, lengths=lens)
     return out
+
+
+# ---- per-source colour: a short FIR per row, interpolated between chunk boundaries ------------------
+# color[s, k, :] is M coefficients (1 <= M <= 64) of source row s at chunk boundary k (t = kK), boundaries laid out as the
+# delays of the same call; [rows, M] is the static form, the same filter at every boundary.  With x' the delayed input
+# (x' = x without a delay), t = kK + j, 0 <= j < K:
+#     A = sum_m c_k[m] x'(t - m),  B = sum_m c_{k+1}[m] x'(t - m),  x''(t) = A + (j / K)(B - A)
+# x'' replaces the row's input, indexed by the time of reception as the gain is.  `colored_inputs` is the definition in
+# float64; the device (bas_color_rows_f32) accumulates A and B in float32 by fused multiply-adds with m ascending and
+# interpolates with one more (include/bas.h), which is what makes a stream's block the offline one bit for bit.
+MAX_TAPS = 64
+FIR_GRID = 4096                                            # FFT length of min_phase_fir's design
+FIR_FLOOR = 1e-6                                           # magnitudes are floored here (-120 dB) before the logarithm
+
+
+def tail_samples(taps):
+    """Pre-colour samples a stream carries per row for filters of `taps` coefficients: taps - 1 rounded up to a multiple
+    of 4 (16-byte aligned blocks behind them)."""
+    return (int(taps) - 1 + 3) // 4 * 4
+
+
+def _color_dims(shape, rows, n_q, taps):
+    shape = tuple(shape)
+    ok = len(shape) in (2, 3) and shape[0] == rows and 1 <= shape[-1] <= MAX_TAPS and (len(shape) == 2 or shape[1] == n_q) \
+        and (taps is None or shape[-1] == taps)
+    if not ok:
+        m = "M" if taps is None else str(taps)
+        raise ValueError(f"color must have shape ({rows}, {n_q}, {m}) or ({rows}, {m}) with 1 <= M <= {MAX_TAPS}, got {shape}")
+
+
+def check_color(color, rows, n_q, taps=None):
+    """A host colour argument as a float32 numpy array [rows, n_q, M] or [rows, M] (static): ValueError for another
+    shape, M outside 1..64 (or other than `taps`) or non-finite values."""
+    arr = np.asarray(color.numpy() if hasattr(color, "numpy") else color)
+    _color_dims(arr.shape, rows, n_q, taps)
+    arr = arr.astype(np.float32)
+    if not np.isfinite(arr).all():
+        raise ValueError("colour coefficients must be finite")
+    return arr
+
+
+def is_device_color(color, rows, n_q, taps=None):
+    """color is a device tensor: checked for shape and float32 dtype only (as the other primitives are).  False for host
+    data."""
+    import torch
+    if not (isinstance(color, torch.Tensor) and color.is_cuda):
+        return False
+    _color_dims(color.shape, rows, n_q, taps)
+    if color.dtype != torch.float32:
+        raise ValueError("a device color must be float32")
+    return True
+
+
+def color_to_device(color, rows, n_q, dev, taps=None):
+    """A colour argument as a float32 tensor on `dev` with unit stride along the taps (host data validated by check_color
+    first; a device tensor keeps its other strides: an expanded bank is read where it is)."""
+    import torch
+    if is_device_color(color, rows, n_q, taps):
+        t = color.to(dev)
+        return t if t.stride(-1) == 1 and all(s >= 0 for s in t.stride()) else t.contiguous()
+    return torch.from_numpy(np.ascontiguousarray(check_color(color, rows, n_q, taps))).to(dev)
+
+
+def stage_color(color, view):
+    """Copy a colour argument (already checked) into a renderer's colour view (the view itself: nothing to do)."""
+    import torch
+    if isinstance(color, torch.Tensor) and color.is_cuda:
+        if color.data_ptr() == view.data_ptr() and color.stride() == view.stride():
+            return
+        view.copy_(color)
+    else:
+        view.copy_(torch.from_numpy(np.asarray(color.numpy() if hasattr(color, "numpy") else color, dtype=np.float32)))
+
+
+def colored_inputs(x, K, color, lengths=None, history=None):
+    """The float64 definition of the coloured inputs.  x: [rows, T] (any T); color: [rows, >= (T-1)//K + 2, M] at the
+    boundaries t = 0, K, .., or [rows, M] (static); lengths: valid samples per row (default T): reads at or past them are
+    0, and so are the outputs; history: [rows, H] samples before x[:, 0] (a stream's carried tail; default none: zeros).
+    The sums run over m ascending.  Returns float64 [rows, T]."""
+    K = int(K)
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[None]
+    R, T = x.shape
+    c = np.asarray(color, dtype=np.float64)
+    if c.ndim == 2:
+        c = c[:, None, :]
+    if c.ndim != 3 or c.shape[0] != R:
+        raise ValueError(f"color must be [{R}, n_q, M] or [{R}, M]")
+    static = c.shape[1] == 1
+    M = c.shape[2]
+    n_valid = np.full(R, T, dtype=np.int64) if lengths is None else np.minimum(np.asarray(lengths, np.int64).reshape(R), T)
+    H = 0 if history is None else int(np.shape(history)[1])
+    pad = np.zeros((R, max(M - 1 - H, 0)))
+    front = pad if history is None else np.concatenate([pad, np.asarray(history, dtype=np.float64).reshape(R, H)], axis=1)
+    F = front.shape[1]
+    out = np.zeros((R, T), dtype=np.float64)
+    t = np.arange(T, dtype=np.int64)
+    k = t // K
+    w = (t - k * K).astype(np.float64) / float(K)
+    for r in range(R):
+        hi = int(n_valid[r])
+        if hi == 0:
+            continue
+        full = np.concatenate([front[r], x[r, :hi]])
+        kk = np.zeros(hi, dtype=np.int64) if static else k[:hi]
+        A = np.zeros(hi)
+        B = np.zeros(hi)
+        for m in range(M):
+            v = full[F - m:F - m + hi]                                 # x'(t - m), t < hi
+            A += c[r, kk, m] * v
+            if not static:
+                B += c[r, kk + 1, m] * v
+        out[r, :hi] = A if static else A + w[:hi] * (B - A)
+    return out
+
+
+def color_rows_device(x, color, K, out, lengths=None, Hc=0, groups=None):
+    """One bas_color_rows_f32 launch on device tensors.  x, out: float32 [n_src, T] views (unit sample stride; x may have
+    Hc readable samples in front of each row); color: float32 [n_src, >= (T-1)//K + 2, M] or [n_src, M] (static), unit
+    stride along the taps, any other strides >= 0 (0 repeats); lengths: None or an int64 device tensor of valid lengths
+    per row.  groups: None, or (n_groups, x_stride_g, c_stride_g, out_stride_g) for two-level rows (x, color, out then
+    address group 0)."""
+    n_src, T = int(out.shape[-2]), int(out.shape[-1])
+    G, xg, cg, yg = (1, 0, 0, 0) if groups is None else groups
+    assert x.stride(-1) == 1 and out.stride(-1) == 1 and color.stride(-1) == 1 and color.dim() in (2, 3)
+    ck = color.stride(1) if color.dim() == 3 else 0
+    dev = out.device
+    with _hip.on_device(dev):
+        _hip.call("bas_color_rows_f32", _hip.ptr(x), xg, x.stride(-2), int(Hc), None if lengths is None else _hip.ptr(lengths),
+                  _hip.ptr(color), cg, color.stride(0), ck, int(color.shape[-1]), G, n_src, T, int(K), _hip.ptr(out), yg,
+                  out.stride(-2), _hip.current_stream(dev))
+
+
+def colored_inputs_device(x, K, color, out=None, lengths=None):
+    """The device entry for offline callers and tests: x [rows, T] (numpy or tensor), color [rows, >= (T-1)//K + 2, M] or
+    [rows, M] (host data validated as check_color does; device float32 tensors checked for shape and dtype only).
+    lengths: valid samples per row (default T).  Returns float32 [rows, T] on the device (or fills `out`)."""
+    import torch
+    from .apply_hrtf import padded_rows
+    dev = torch.device("cuda", torch.cuda.current_device())
+    xt = torch.as_tensor(x)
+    if xt.dim() == 1:
+        xt = xt.reshape(1, -1)
+    R, T = xt.shape
+    if xt.is_cuda:
+        dev = xt.device
+    shape = tuple(np.shape(color))
+    n_q = (T - 1) // int(K) + 2 if T else 1
+    if len(shape) == 3 and shape[1] < n_q:
+        raise ValueError(f"color must hold >= {n_q} boundaries")
+    c = color_to_device(color, R, shape[1] if len(shape) == 3 else n_q, dev)
+    xs = xt.to(device=dev, dtype=torch.float32).contiguous()
+    if out is None:
+        out = padded_rows(R, T, dev)
+    lens = None
+    if lengths is not None:
+        lens = torch.as_tensor(np.asarray(lengths, dtype=np.int64).reshape(R)).to(dev)
+    color_rows_device(xs, c, K, out, lengths=lens)
+    return out
+
+
+def min_phase_fir(freqs, mags, fs, taps):
+    """Minimum-phase FIR taps from band magnitudes (numpy only).  freqs: band centres in Hz, ascending and > 0; mags: the
+    magnitude at each centre (>= 0).  The log-magnitude is interpolated linearly over log-frequency on a fixed grid of
+    FIR_GRID FFT bins, flat outside the bands, after the magnitudes are floored at FIR_FLOOR; the folded-cepstrum
+    (homomorphic) method turns it into the minimum-phase response, truncated to `taps` coefficients.  Minimum phase, not
+    linear phase: the energy sits at the front, so a reflection keeps its arrival time.  Returns float64 [taps]."""
+    f = np.asarray(freqs, dtype=np.float64).reshape(-1)
+    a = np.asarray(mags, dtype=np.float64).reshape(-1)
+    taps, fs = int(taps), float(fs)
+    if f.size < 1 or a.shape != f.shape or not np.isfinite(f).all() or not (f > 0).all() or not (np.diff(f) > 0).all():
+        raise ValueError("freqs must be ascending band centres > 0, with one magnitude each")
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("mags must be finite and >= 0")
+    if not 1 <= taps <= FIR_GRID // 2 or not (np.isfinite(fs) and fs > 0):
+        raise ValueError(f"taps must be in 1..{FIR_GRID // 2} and fs > 0")
+    N = FIR_GRID
+    grid = np.arange(N // 2 + 1, dtype=np.float64) * (fs / N)
+    logmag = np.interp(np.log(np.maximum(grid, 1e-300)), np.log(f), np.log(np.maximum(a, FIR_FLOOR)))
+    cep = np.fft.irfft(logmag, N)                                      # real, even: the cepstrum of the magnitude
+    fold = np.zeros(N)
+    fold[0], fold[N // 2] = cep[0], cep[N // 2]
+    fold[1:N // 2] = 2.0 * cep[1:N // 2]                               # causal part doubled: the minimum-phase cepstrum
+    h = np.fft.irfft(np.exp(np.fft.rfft(fold)), N)
+    return h[:taps].copy()

@@ -26,7 +26,10 @@ d = (sqrt((w.u)^2 + A |w|^2) - w.u) / A solves |w - u d| = d c / fs exactly for 
 `scene_params` is the float64 numpy definition, `scene_params_device` the kernel (bas_scene_params_f64, one launch).  The
 images of a source are extra rows of the same render, row = s n_img + i; they share the source's signal, which the delay
 kernel reads with a source stride of 0 (`render_scene`) or which one broadcast copy replicates (`SceneStreamRenderer`).
-Walls reflect all frequencies alike (one coefficient per wall); the image model holds for rigid or nearly rigid walls.
+Walls reflect all frequencies alike (one coefficient per wall) unless the room has `bands`: then every wall has a
+reflection magnitude per frequency band, every image a short minimum-phase FIR designed from the product of the walls it
+met (Room.image_filters), and one colour launch (§3.13) filters every image's delayed input.  The image model holds for
+rigid or nearly rigid walls.
 """
 import numpy as np
 
@@ -60,15 +63,44 @@ def image_gains(images, beta):
     return np.prod(b[:, 0] ** n_lo * b[:, 1] ** n_hi, axis=1)
 
 
+def image_band_magnitudes(images, beta):
+    """image_gains per frequency band: beta [6, n_bands] -> float64 [n_img, n_bands]."""
+    b = np.asarray(beta, dtype=np.float64)
+    return np.stack([image_gains(images, b[:, i]) for i in range(b.shape[1])], axis=1)
+
+
 class Room:
     """An axis-aligned shoebox room occupying [0, size_a] on each axis.  size: (Lx, Ly, Lz) in metres; beta: the walls'
     reflection coefficients (x0, x1, y0, y1, z0, z1), |beta| <= 1, or one value for all six; order: the highest
-    reflection order rendered (0..3; n_img = 1, 7, 25, 63 rows per source).  ValueError otherwise."""
+    reflection order rendered (0..3; n_img = 1, 7, 25, 63 rows per source).  ValueError otherwise.
+    bands: None, or the centre frequencies in Hz (ascending, > 0) of frequency-dependent walls: beta is
+    then [6, n_bands], or [n_bands] for all six walls, reflection magnitudes in [0, 1]; every image gets a minimum-phase
+    FIR of `taps` coefficients (image_filters) which carries its level, and the scalar `gains` are all 1."""
 
-    def __init__(self, size, beta=0.9, order=1):
+    def __init__(self, size, beta=0.9, order=1, bands=None, taps=32):
         size = np.asarray(size, dtype=np.float64)
         if size.shape != (3,) or not np.isfinite(size).all() or not (size > 0).all():
             raise ValueError("room size must be three finite lengths > 0")
+        self.bands, self.taps, self._filters = None, None, {}
+        if bands is not None:
+            bands = np.asarray(bands, dtype=np.float64)
+            if bands.ndim != 1 or bands.size < 1 or not np.isfinite(bands).all() or not (bands > 0).all() \
+                    or not (np.diff(bands) > 0).all():
+                raise ValueError("bands must be centre frequencies in Hz, ascending and > 0")
+            if int(taps) != taps or not 1 <= int(taps) <= propagation.MAX_TAPS:
+                raise ValueError(f"taps must be in 1..{propagation.MAX_TAPS}")
+            beta = np.asarray(beta, dtype=np.float64)
+            if beta.shape == (bands.size,):
+                beta = np.tile(beta, (6, 1))
+            if beta.shape != (6, bands.size) or not np.isfinite(beta).all() or not ((beta >= 0) & (beta <= 1)).all():
+                raise ValueError("with bands, beta must be [6, n_bands] or [n_bands] reflection magnitudes in [0, 1]")
+            self.size, self.beta, self.bands, self.taps = size, beta, bands, int(taps)
+            self.images = shoebox_images(order)
+            self.order = int(order)
+            self.n_img = self.images.shape[0]
+            self.gains = np.ones(self.n_img)                           # the filters carry the level
+            self._device = {}
+            return
         beta = np.asarray(beta, dtype=np.float64)
         if beta.shape == ():
             beta = np.full(6, float(beta))
@@ -88,6 +120,28 @@ class Room:
         if key not in self._device:
             self._device[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev)
                                       for a in (self.size, self.images, self.gains))
+        return self._device[key]
+
+    def image_filters(self, fs):
+        """The images' wall filters of a banded room for sample rate fs: float32 [n_img, taps].  Image i's band magnitudes
+        are the product over the walls of beta_wall,band ^ n_wall (image_gains' hit counts); its taps are
+        propagation.min_phase_fir of them; the direct path is exactly (1, 0, ..).  Cached per fs."""
+        if self.bands is None:
+            raise ValueError("image_filters: the room has no bands")
+        fs = float(fs)
+        if fs not in self._filters:
+            mags = image_band_magnitudes(self.images, self.beta)
+            f = np.stack([propagation.min_phase_fir(self.bands, m, fs, self.taps) for m in mags]).astype(np.float32)
+            f[~self.images.any(axis=1)] = np.eye(1, self.taps, dtype=np.float32)[0]
+            self._filters[fs] = f
+        return self._filters[fs]
+
+    def device_filters(self, fs, dev):
+        """image_filters(fs) on `dev`, uploaded once per device and sample rate."""
+        import torch
+        key = (str(dev), float(fs))
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.image_filters(fs)).to(dev)
         return self._device[key]
 
 
@@ -320,7 +374,9 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     rendered as room.n_img image sources (row s n_img + i), all reading the source's one signal.
     Three steps: the scene kernel (with step 1b: moving sources are heard where they were); one bas_delay_rows_f32 launch that writes every image's delayed input (source stride
     0: nothing is replicated); render_angles_device with the gains.  Returns what render_sources returns: a device tensor
-    (out_length, 2), peak-normalised ("mix") or not ("none")."""
+    (out_length, 2), peak-normalised ("mix") or not ("none").
+    A room with bands adds one step: the delay launch writes a staging buffer, and one bas_color_rows_f32 launch (groups =
+    sources, the n_img filters of room.image_filters(fs) shared by all of them, static) writes the rows the render reads."""
     import torch
     from .apply_hrtf import as_device_table, padded_rows, render_lengths, render_angles_device
     K, S = int(chunksize), int(subchunksize)
@@ -343,13 +399,18 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     if not any(_is_device(a) for a in args):
         args = (torch.from_numpy(args[0]).to(dev),) + args[1:]        # (so that the scene runs on the table's device)
     el, az, g, d = scene_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp, chunksize=K)
+    banded = room is not None and room.bands is not None
     x = padded_rows(n_src * n_img, in_length, dev)
     if n:
         src = sig.to(device=dev, dtype=torch.float32).contiguous()
         lens = torch.full((n_src * n_img,), n, dtype=torch.int64, device=dev)
+        pre = padded_rows(n_src * n_img, in_length, dev) if banded else x
         # groups = sources, rows of a group = its images: the input's row stride is 0, every image reads the one signal
-        propagation.delay_rows_device(src[:1].expand(n_img, n), d[:n_img], K, interp, x[:n_img], lengths=lens,
-                                      groups=(n_src, src.stride(0), n_img * d.stride(0), n_img * x.stride(0)))
+        propagation.delay_rows_device(src[:1].expand(n_img, n), d[:n_img], K, interp, pre[:n_img], lengths=lens,
+                                      groups=(n_src, src.stride(0), n_img * d.stride(0), n_img * pre.stride(0)))
+        if banded:                                                     # every source's images read the one bank
+            propagation.color_rows_device(pre[:n_img], room.device_filters(fs, dev), K, x[:n_img], lengths=lens,
+                                          groups=(n_src, n_img * pre.stride(0), 0, n_img * x.stride(0)))
     y, _ = render_angles_device(x, K, S, tbl, el, az, normalize, fused=fused, gain=g)
     return y.t()
 
@@ -378,8 +439,14 @@ class SceneStreamRenderer:
         self.K = int(chunksize)
         assert self.K % int(subchunksize) == 0, 'subchunksize does not divide chunksize evenly'
         self._prev = None                                 # the sources' positions one chunk before the next block (device)
+        banded = room is not None and room.bands is not None
         self.inner = StreamRenderer(tbl, self.n_src * self.n_img, chunksize, subchunksize, graph=graph, copy_out=copy_out,
-                                    max_delay=self.max_delay, interp=interp)
+                                    max_delay=self.max_delay, interp=interp, color_taps=room.taps if banded else None)
+        self._bank = None
+        if banded:                                        # the static bank, every source's images alike: written once into
+            dev = self.inner.tbl.device                   # the inner renderer's own static colour buffer, passed every block
+            self._bank = self.inner.color_view(None, static=True)
+            self._bank.view(self.n_src, self.n_img, room.taps).copy_(room.device_filters(fs, dev).unsqueeze(0))
 
     def prepare(self, B):
         """StreamRenderer.prepare for blocks of B samples, with the gains live (so that the captured graph is the one
@@ -414,7 +481,7 @@ class SceneStreamRenderer:
         self._prev = p[:, -2].clone()                     # (the velocity at the next block's first boundary)
         x = st.input_view(B)                                           # [n_src n_img, B]: every image's copy of the block
         x.view(self.n_src, self.n_img, B).copy_(blk.to(dev).unsqueeze(1))   # (one broadcast copy, converts to float32)
-        return st.process(x, el, az, gain=g, delay=d)
+        return st.process(x, el, az, gain=g, delay=d, color=self._bank)
 
     def finish(self):
         """The last L - 1 samples (StreamRenderer.finish)."""

@@ -160,14 +160,19 @@ class _BlockStream:
 class StreamRenderer(_BlockStream):
     one_call = True      # bas_render_stream_block_f32 where the fused kernels serve the block (False: render + epilogue launch; A/B, tests)
 
-    def __init__(self, tbl, n_src, chunksize, subchunksize, graph=True, copy_out=True, max_delay=None, interp="cubic"):
+    def __init__(self, tbl, n_src, chunksize, subchunksize, graph=True, copy_out=True, max_delay=None, interp="cubic",
+                 color_taps=None):
         """graph: replay each block as one captured hipGraph (captured by prepare(), else on the second block of a
         size).  copy_out: process() returns a fresh tensor (True) or a view of the renderer's output buffer that
         the next process() call overwrites (False: no copy kernel; for callers that consume each block at once).
         max_delay: None, or the largest propagation delay in samples the stream takes: every block then
         needs delay=, and the renderer carries the last history_samples(max_delay) raw input samples per source;
-        interp: the delay's interpolator ("cubic" or "linear")."""
+        interp: the delay's interpolator ("cubic" or "linear").
+        color_taps: None, or M in 1..64: every block then needs color= with M coefficients, and the
+        renderer carries the last propagation.tail_samples(M) pre-colour samples per source."""
         import torch
+        if color_taps is not None and not 1 <= int(color_taps) <= propagation.MAX_TAPS:
+            raise ValueError(f"color_taps must be in 1..{propagation.MAX_TAPS}")
         super().__init__(tbl, chunksize, subchunksize, graph, copy_out)
         self.n_src = int(n_src)
         dev = self.tbl.device
@@ -197,6 +202,15 @@ class StreamRenderer(_BlockStream):
         self.H = 0 if max_delay is None else propagation.history_samples(self.max_delay)
         self._raw = None if max_delay is None else torch.zeros((self.n_src, self.H), dtype=torch.float32, device=dev)
         self._delay_all = None
+        # colour: pre-colour rows [n_src, Tc + capacity] - columns [0, Tc) carry the last Tc pre-colour
+        # samples; what would fill the FIR window (the block, or its delayed input) lands behind them and the colour launch
+        # writes the window - the block's coefficient sets [n_src, nb, M], and the one set per row of the static form
+        self.color_taps = None if color_taps is None else int(color_taps)
+        self.Tc = 0 if color_taps is None else propagation.tail_samples(self.color_taps)
+        self._pre = None if color_taps is None else torch.zeros((self.n_src, self.Tc), dtype=torch.float32, device=dev)
+        self._color_all = None
+        self._color_static = None
+        self._static_color = False                        # the block's colour launch reads _color_static
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _reserve(self, B):
@@ -211,6 +225,11 @@ class StreamRenderer(_BlockStream):
             grown = torch.zeros((self.n_src, self.H + (B + 3) // 4 * 4), dtype=torch.float32, device=self._raw.device)
             grown[:, :self.H] = self._raw[:, :self.H]     # the carried raw history survives the growth
             self._raw = grown
+            self._graph = None
+        if self._pre is not None and self._pre.shape[1] - self.Tc < B:
+            grown = torch.zeros((self.n_src, self.Tc + (B + 3) // 4 * 4), dtype=torch.float32, device=self._pre.device)
+            grown[:, :self.Tc] = self._pre[:, :self.Tc]   # the carried pre-colour tail survives the growth
+            self._pre = grown
             self._graph = None
 
     def _layout(self, B):
@@ -237,6 +256,8 @@ class StreamRenderer(_BlockStream):
             self._gain_all = g
         if self._raw is not None:                         # (not carried: each block brings its boundaries' delays)
             self._delay_all = torch.zeros((n, nb), dtype=torch.float64, device=dev)
+        if self._pre is not None:                         # (not carried either: each block brings its boundaries' sets)
+            self._color_all = torch.zeros((n, nb, self.color_taps), dtype=torch.float32, device=dev)
         self._y = torch.empty((2, self.halo + B + self.tbl.L - 1), dtype=torch.float32, device=dev)
         self._window_workspaces(n, self.halo + B, n * (nh + nb))
 
@@ -258,6 +279,8 @@ class StreamRenderer(_BlockStream):
         self._reserve(B)
         if self._raw is not None:
             return self._raw[:, self.H:self.H + B]
+        if self._pre is not None:
+            return self._pre[:, self.Tc:self.Tc + B]
         return self._xbuf[:, self.halo:self.halo + B]
 
     def trajectory_views(self, B):
@@ -284,6 +307,28 @@ class StreamRenderer(_BlockStream):
         self._layout(B)
         return self._delay_all
 
+    def _use_static_color(self, static):
+        """Switch the block's colour launch between the per-boundary sets and the one set per row (its graph changes)."""
+        import torch
+        if static and self._color_static is None:
+            self._color_static = torch.zeros((self.n_src, self.color_taps), dtype=torch.float32, device=self.tbl.device)
+        if static != self._static_color:
+            self._static_color = static
+            self._graph, self._blocks_in_layout = None, 0
+
+    def color_view(self, B, static=False):
+        """Device view, float32 [n_src, B/K + 1, M], of the renderer's own colour buffer for blocks of B samples (DESIGN.md
+        §3.13), beside delay_view(B): a producer that writes the coefficients there and passes the view to process(color=)
+        saves the copy.  static=True: the [n_src, M] buffer of the static form instead (B is not used), which also makes
+        the static launch the one prepare() captures.  Only for a renderer built with color_taps (ValueError otherwise)."""
+        if self.color_taps is None:
+            raise ValueError("color_view: the renderer was built without color_taps")
+        if static:
+            self._use_static_color(True)
+            return self._color_static
+        self._layout(B)
+        return self._color_all
+
     # ---- one block -------------------------------------------------------------------------------------
     def _block_body(self):
         """The stream-ordered work of one block on the per-block buffers (captured into the hipGraph)."""
@@ -295,10 +340,20 @@ class StreamRenderer(_BlockStream):
         if self._raw is not None:
             # the block's delayed input into the window behind the halo (one launch), then the raw history moves behind
             # the block (one launch): the last H raw samples go to the front for the next block
+            dst = self._xbuf[:, halo:halo + B] if self._pre is None else self._pre[:, self.Tc:self.Tc + B]
             propagation.delay_rows_device(self._raw[:, self.H:self.H + B], self._delay_all, self.K, self.interp,
-                                          self._xbuf[:, halo:halo + B], H=self.H, max_delay=self.max_delay)
+                                          dst, H=self.H, max_delay=self.max_delay)
             with _hip.on_device(dev):
                 _hip.call("bas_delay_carry_f32", _hip.ptr(self._raw), 0, self._raw.stride(0), 1, n, self.H, B,
+                          _hip.current_stream(dev))
+        if self._pre is not None:
+            # the block's coloured input into the window behind the halo (one launch), then the last Tc pre-colour samples
+            # move to the front for the next block (one launch; nothing to move at M = 1)
+            propagation.color_rows_device(self._pre[:, self.Tc:self.Tc + B],
+                                          self._color_static if self._static_color else self._color_all, self.K,
+                                          self._xbuf[:, halo:halo + B], Hc=self.Tc)
+            with _hip.on_device(dev):
+                _hip.call("bas_delay_carry_f32", _hip.ptr(self._pre), 0, self._pre.stride(0), 1, n, self.Tc, B,
                           _hip.current_stream(dev))
         with _hip.on_device(dev):
             one_call = self.one_call and bool(lib.bas_render_fused_supported(n, halo + B, self.K, self.S, tbl.L)) and tbl.upsampling >= 4 \
@@ -349,7 +404,8 @@ class StreamRenderer(_BlockStream):
     def _carried(self):
         gains = () if self._gain_all is None else (self._gain_all, self._gain_last)
         raw = () if self._raw is None else (self._raw[:, :self.H + self._B], self._delay_all)
-        return (self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev) + gains + raw
+        pre = () if self._pre is None else (self._pre[:, :self.Tc + self._B], self._color_all)
+        return (self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev) + gains + raw + pre
 
     def _emitted(self):
         return self._y[:, self.halo:self.halo + self._B].t()
@@ -359,7 +415,7 @@ class StreamRenderer(_BlockStream):
         assert B % self.K == 0 and B > 0, 'block length must be a positive multiple of the chunk size'
         super().prepare(B)
 
-    def process(self, block, elev, azim, head=None, gain=None, delay=None):
+    def process(self, block, elev, azim, head=None, gain=None, delay=None, color=None):
         """block: [n_src, B] (B a multiple of the chunk size); elev/azim: float64 [n_src, B/K + 1],
         the trajectory at t = t0, t0+K, .., t0+B of this block (radians; numpy arrays or device tensors).
         head: None (elev/azim are head-relative), or the listener's head orientation at the same boundaries, quaternions
@@ -374,6 +430,10 @@ class StreamRenderer(_BlockStream):
         §3.11): required by a renderer built with max_delay, refused (ValueError) by one without.  Host delays must be
         finite and in [d_min, max_delay] (ValueError); device tensors are checked for shape and dtype only (the kernel
         clamps); delay_view(B) is taken in place.  Consecutive blocks should repeat their shared boundary's delay.
+        color: float32 [n_src, B/K + 1, M], every source's FIR coefficients at the same boundaries, or [n_src, M], one
+        filter throughout the block: required by a renderer built with color_taps=M, refused
+        (ValueError) by one without.  Host coefficients must be finite (ValueError); device tensors are checked for shape
+        and dtype only; color_view(B) is taken in place.  Consecutive blocks should repeat their shared boundary's set.
         Returns the B stereo samples this block completes as a device tensor (B, 2), un-normalised."""
         import torch
         assert not self._finished, "stream already finished"
@@ -394,6 +454,11 @@ class StreamRenderer(_BlockStream):
                              "delay= needs a renderer built with max_delay")
         if delay is not None and not propagation.is_device_delay(delay, (self.n_src, nb)):
             propagation.check_delay(delay, (self.n_src, nb), self.interp, self.max_delay)
+        if (color is None) != (self.color_taps is None):
+            raise ValueError("color= is required by a renderer built with color_taps" if color is None else
+                             "color= needs a renderer built with color_taps")
+        if color is not None and not propagation.is_device_color(color, self.n_src, nb, self.color_taps):
+            color = propagation.check_color(color, self.n_src, nb, self.color_taps)
         if head is not None:
             q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
         if gain is not None:
@@ -410,6 +475,9 @@ class StreamRenderer(_BlockStream):
             rotate_into_views(elev, azim, q, (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:]))
         if delay is not None:
             propagation.stage_delay(delay, self._delay_all, self.interp, self.max_delay)
+        if color is not None:
+            self._use_static_color(len(color.shape) == 2)
+            propagation.stage_color(color, self._color_static if self._static_color else self._color_all)
         x_dst = self.input_view(B)
         if not _is_buffer(blk, x_dst, torch.float32):
             x_dst.copy_(blk)

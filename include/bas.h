@@ -489,6 +489,30 @@ int bas_batch_pack_delay_f32(const float *sig, int n_items, int n_src, long N, c
                              long n_q_max, int K, long T_in, float *x, long x_stride, double *elev_out, double *azim_out,
                              double *gain_out, bas_stream_t stream);
 
+/* ---- per-source colour (no reference counterpart) ----------------------------------------------------
+ * color [..] f32 (device): M coefficients (1 <= M <= 64) of a short FIR per source row and chunk boundary, boundaries laid
+ * out in time as the angles, gains and delays of the same call.  A source's coloured input x'' replaces its (delayed) input
+ * x'; everything after that (chunk IRs, crossfade, FIR, mix, gains, peak rules) is unchanged.  For t = kK + j, 0 <= j < K:
+ *   A = sum_{m < M} c_k[m] x'(t - m),  B = sum_{m < M} c_{k+1}[m] x'(t - m),  x''(t) = A + (j / K)(B - A).
+ * Precision: A and B are accumulated in binary32 by fused multiply-adds, acc = fma(c[m], x'(t - m), acc) from acc = 0 with
+ * m ascending (M is padded to a multiple of 4 with zero taps, which add exact zeros); w = (float)j * (1.0f / (float)K);
+ * x'' = fma(w, B - A, A).  The bits of an output depend on (j, K, c_k, c_{k+1}) and its M inputs alone - not on the absolute
+ * time nor on where a tile starts - so a stream's coloured block is the offline one bit for bit; (1, 0, .., 0) returns its
+ * input bit for bit; B == A returns A.  Samples outside the readable range are 0.  Nothing is validated on the device.
+ *   bas_color_rows_f32: rows (g, s), g < n_groups, s < n_src: input x + g x_stride_g + s x_stride_s (sample 0; samples
+ *     -Hc .. -1 in front are readable, Hc may be 0: the missing samples are zeros; an input stride of 0 repeats a signal),
+ *     coefficients at color + g c_stride_g + s c_stride_s + k c_stride_k, M contiguous floats for each of the (T-1)/K + 2
+ *     boundaries k; any coefficient stride may be 0: c_stride_k == 0 is the static form (one set per row, B is skipped: the
+ *     bits of the per-boundary form fed repeated sets), c_stride_g == 0 shares one bank over the groups; otherwise
+ *     c_stride_k >= M.  Output y + g y_stride_g + s y_stride_s, T samples (16-byte loads and stores where a row is
+ *     16-byte aligned).  lengths [n_groups n_src] (NULL: T each): the row's valid samples; reads at or past it are 0, and
+ *     so are the outputs.  One launch, no allocation, no synchronisation (capturable); T < 2^30, n_groups n_src <= 65535,
+ *     strides >= 0, K > 0 (BAS_E_SHAPE); x, color, y required (BAS_E_NULL) and 4-byte aligned, lengths 8-byte
+ *     (BAS_E_ALIGN).  y must not overlap x's readable range. */
+int bas_color_rows_f32(const float *x, long x_stride_g, long x_stride_s, int Hc, const long *lengths, const float *color,
+                       long c_stride_g, long c_stride_s, long c_stride_k, int M, int n_groups, int n_src, long T, int K,
+                       float *y, long y_stride_g, long y_stride_s, bas_stream_t stream);
+
 /* ---- Cartesian scenes (no reference counterpart) -----------------------------------------------------
  * Source positions, the listener's pose and an optional axis-aligned shoebox room -> the angles, gains and delays of every
  * image source at every chunk boundary: what the three sections above consume.  All float64 on the device unless stated,
