@@ -184,7 +184,7 @@ __global__ __launch_bounds__(BB_THREADS) void bas_batch_compact_kernel(const flo
 // workgroups per item: about 8 per CU over the whole batch, at least one, at most one per 1024 samples of the longest window
 static int batch_blocks_x(int n_items, long max_len) {
     long want = (8L * bas_device_cus() + n_items - 1) / n_items;
-    const long cap = (max_len + 1023) / 1024;
+    const long cap = max_len / 1024 + (max_len % 1024 != 0);  // (ceil without max_len + 1023: any long)
     if (want > cap) want = cap;
     if (want < 1) want = 1;
     if (want > 65535) want = 65535;
@@ -198,7 +198,8 @@ static int batch_pack(const char *who, const float *sig, int n_items, int n_src,
     BAS_REQUIRE(n_items > 0 && n_src > 0 && N >= 0 && K > 0 && T_in > 0 && n_q_max > 0, BAS_E_SHAPE,
                 "%s: need n_items, n_src, K, T_in, n_q_max > 0 and N >= 0", who);
     BAS_REQUIRE(T_in % K == 0, BAS_E_SHAPE, "%s: T_in (%ld) must be a multiple of K (%d)", who, T_in, K);
-    BAS_REQUIRE(x_stride >= T_in && x_stride % 4 == 0, BAS_E_SHAPE, "%s: x_stride must be >= T_in and a multiple of 4", who);
+    BAS_REQUIRE(T_in <= BAS_MAX_T_IN && x_stride >= T_in && x_stride % 4 == 0, BAS_E_SHAPE,
+                "%s: x_stride must be >= T_in and a multiple of 4, T_in <= 2^41", who);
     BAS_REQUIRE(lengths && offsets && elev && azim && x && elev_out && azim_out && (sig || N == 0) &&
                     (!need_gain || (gain && gain_out)) && (!need_delay || delay),
                 BAS_E_NULL, "%s: null pointer", who);
@@ -207,7 +208,9 @@ static int batch_pack(const char *who, const float *sig, int n_items, int n_src,
     BAS_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0, BAS_E_ALIGN, "%s: x must be 16-byte aligned", who);
     BAS_REQUIRE(n_items <= 65535, BAS_E_SHAPE, "%s: more than 65535 items in one call", who);
     const long n_q = T_in / K + 1;
-    const dim3 grid(batch_blocks_x(n_items, n_src * ((x_stride + n_items - 1) / n_items)), n_items);
+    long per_item = x_stride / n_items + (x_stride % n_items != 0);   // ceil; capped: the product with n_src stays a long
+    if (per_item > (1L << 31)) per_item = 1L << 31;
+    const dim3 grid(batch_blocks_x(n_items, n_src * per_item), n_items);
     const double *g = need_gain ? gain : nullptr;
     double *go = need_gain ? gain_out : nullptr;
     if (need_delay && need_gain)

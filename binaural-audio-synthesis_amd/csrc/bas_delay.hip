@@ -87,6 +87,7 @@ extern "C" int bas_delay_carry_f32(float *x, long x_stride_g, long x_stride_s, i
                                    bas_stream_t stream) {
     BAS_REQUIRE(n_groups >= 0 && n_src >= 0 && H >= 0 && B > 0, BAS_E_SHAPE,
                 "bas_delay_carry_f32: need n_groups, n_src, H >= 0 and B > 0");
+    BAS_REQUIRE((long)n_groups * n_src <= 0x7fffffffL, BAS_E_SHAPE, "bas_delay_carry_f32: n_groups n_src must be below 2^31");
     if ((long)n_groups * n_src == 0 || H == 0) return 0;
     BAS_REQUIRE(x, BAS_E_NULL, "bas_delay_carry_f32: null pointer");
     hipLaunchKernelGGL(bas_delay_carry_kernel, dim3((unsigned)(n_groups * n_src)), dim3(DL_THREADS), 0, bas_stream(stream), x,

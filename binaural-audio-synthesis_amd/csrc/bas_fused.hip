@@ -599,20 +599,42 @@ static int fz_slots(int nw, int K) {                         // chunk slots a wi
 // The same for the windows that really occur: tile t, tap segment sg start at t * tile - 128 sg - 32 halo, whose offset
 // inside its chunk repeats with period K / gcd(tile, K) - chunk sizes that divide the tile (512, 1024, ..) always start
 // 128 samples before a chunk boundary and need one slot less than the worst case.
+// The largest offset decides (the slot count grows with it), per halo size: the whole 128-tap segments (halo 4) start at
+// 128 (t tile / 128 - j), j = 1 .. their number; the last, shorter segment has a start of its own per tile.  Bounded by
+// the ceilings of bas.h: no loop below runs more than (BAS_MAX_K / 32) x (tile / 128) = 2^25 times, whatever T_in and L.
+static long fz_gcd(long a, long b) {
+    while (b) { const long r = a % b; a = b; b = r; }
+    return a;
+}
+
 static int fz_slots_exact(int nw, int K, int Lp, long n_tiles) {
     const long tile = 2048L * nw;
-    const int nseg = (Lp + RT_SEG - 1) / RT_SEG;
+    const long period = K / fz_gcd(tile, K);                 // t -> (t tile) mod K repeats after this many tiles
+    const long t_max = n_tiles < period ? n_tiles : period;
+    const int n_whole = Lp / RT_SEG, L_last = Lp % RT_SEG;
     int worst = 1;
-    const long t_max = n_tiles < K ? n_tiles : K;
-    for (long t = 0; t < t_max; ++t) {
-        for (int sg = 0; sg < nseg; ++sg) {
-            const int Lseg = Lp - sg * RT_SEG < RT_SEG ? Lp - sg * RT_SEG : RT_SEG;
-            const int halo = (Lseg + 31) >> 5;
-            const long xbase = t * tile - (long)sg * RT_SEG - 32L * halo;
-            long mo = xbase % K;
-            if (mo < 0) mo += K;
-            const int slots = (int)((mo + 32L * (tile / 32 + halo - 1)) / K) + 1;
-            if (slots > worst) worst = slots;
+    auto take = [&](long xbase, int halo) {
+        long mo = xbase % K;
+        if (mo < 0) mo += K;
+        const int slots = (int)((mo + 32L * (tile / 32 + halo - 1)) / K) + 1;
+        if (slots > worst) worst = slots;
+        return mo;
+    };
+    if (L_last) {
+        const int halo = (L_last + 31) >> 5;
+        for (long t = 0; t < t_max; ++t) take(t * tile - (long)n_whole * RT_SEG - 32L * halo, halo);
+    }
+    if (n_whole) {
+        const int halo = RT_SEG >> 5;
+        const long q = tile / RT_SEG, g = fz_gcd(RT_SEG, K), top = K - g;   // starts are multiples of g modulo K
+        if (n_whole >= q) {                                  // the j ranges of consecutive tiles meet: every i = t q - j of an interval
+            const long n_i = (t_max - 1) * q + n_whole;
+            if (n_i >= K / g) take(top, halo);               // .. which covers every multiple of g
+            else for (long i = -(long)n_whole; i < (t_max - 1) * q; ++i) take(i * RT_SEG, halo);
+        } else {
+            bool at_top = false;                             // (no larger offset exists)
+            for (long t = 0; t < t_max && !at_top; ++t)
+                for (int j = 1; j <= n_whole && !at_top; ++j) at_top = take(t * tile - (long)j * RT_SEG, halo) == top;
         }
     }
     return worst;
@@ -645,8 +667,9 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
     // subchunks: multiples of 32 (a row of 32 inputs meets one crossfaded tap set), or 16 / 8 - two / four sets per row, which only the
     // unit blocks of the split-role kernel hold (scenes with more than one (tile of 8192, source) unit per CU; L = 97 .. 104, 121 .. 128,
     // or several whole 128-tap segments: bas_fs_unit_len)
-    const bool s16 = (S == 16 || S == 8) && FZ_SPLIT && bas_fs_unit_len((L + 7) & ~7) != 0;    // (8: four sets per row)
-    if (n_src <= 0 || T_in <= 0 || K < 32 || K % 32 != 0 || (S % 32 != 0 && !s16) || K % S != 0 || L <= 0) return p;
+    const bool s16 = (S == 16 || S == 8) && FZ_SPLIT && L > 0 && L <= BAS_MAX_L && bas_fs_unit_len((L + 7) & ~7) != 0;    // (8: four sets per row)
+    if (n_src <= 0 || T_in <= 0 || K < 32 || K % 32 != 0 || S <= 0 || L <= 0 || !bas_sizes_in_range(n_src, T_in, K, S, L)) return p;
+    if ((S % 32 != 0 && !s16) || K % S != 0) return p;
     const long T_out = T_in + L - 1;
     const int cus = bas_device_cus();
     if (fz_slots(4, K) > FZ_MAXSLOTS) {                      // K < 448 or so: h-only rows, four-wave workgroups, two per CU
@@ -668,12 +691,8 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
         p.spw = spw;
         p.n_tiles = n_tiles;
         p.units_total = units;
-        const long wg = 2L * cus;
-        p.units_per_wg = (int)((units + wg - 1) / wg);
-        p.n_wg = (int)((units + p.units_per_wg - 1) / p.units_per_wg);
-        p.parts_per_wg = (p.units_per_wg + n_src - 2) / n_src + 1;
+        bas_deal_units(units, 2L * cus, n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg, &p.slab_bytes);
         p.lds_bytes = lds;
-        p.slab_bytes = (size_t)p.n_wg * p.parts_per_wg * 2 * p.tile * sizeof(float);
         return p;
     }
     // largest tile that still gives every workgroup slot of the chip a unit; scenes with few sources (one source
@@ -694,7 +713,8 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
         if (nw == 4) {                                       // short signals (real-time blocks): a tile of 8192 that is mostly past the
 #endif
             const long n1 = (T_out + 2047) / 2048;           // end of the output costs as much as a full one - narrow tiles then
-            if (4 * T_out * n1 * 2048 < 3 * T_out * n_tiles_nw * 8192) continue;   // useful fraction below 3/4 of the narrow tiles'
+            if (n1 < 3 * n_tiles_nw) continue;               // useful fraction T_out / (n_tiles_nw 8192) below 3/4 of the narrow tiles'
+                                                             // T_out / (n1 2048), as 4 n1 2048 < 3 n_tiles_nw 8192: no product with T_out
             // small scenes: the tiles of 2048 fit in FZ_QUAD_ROUNDS rounds of four-wave workgroups (below): narrow tiles
             if (FZ_QUAD && n1 * n_src <= (long)FZ_QUAD_ROUNDS * 2 * cus) continue;
         }
@@ -752,12 +772,8 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
         p.spw = spw;
         p.n_tiles = n_tiles;
         p.units_total = units;
-        const long wg = units < slots ? units : slots;
-        p.units_per_wg = (int)((units + wg - 1) / wg);
-        p.n_wg = (int)((units + p.units_per_wg - 1) / p.units_per_wg);
-        p.parts_per_wg = (p.units_per_wg + n_src - 2) / n_src + 1;
+        bas_deal_units(units, slots, n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg, &p.slab_bytes);
         p.lds_bytes = split ? bas_fs_lds_bytes(nslots) : quad ? quad_lds : lds;
-        p.slab_bytes = (size_t)p.n_wg * p.parts_per_wg * 2 * p.tile * sizeof(float);
         return p;
     }
     return p;
@@ -809,6 +825,7 @@ static int fused_impl(const char *who, int phases, const float *x, long x_stride
     BAS_REQUIRE(y, BAS_E_NULL, "%s: y is null", who);
     BAS_REQUIRE(n_src >= 0 && T_in >= 0 && K > 0 && S > 0 && L > 0 && ndir > 0, BAS_E_SHAPE,
                 "%s: need n_src>=0, T_in>=0, K,S,L,ndir>0 (n_src=%d T_in=%ld K=%d S=%d L=%d)", who, n_src, T_in, K, S, L);
+    BAS_REQUIRE_SIZES(who, n_src, T_in, K, S, L);
     BAS_REQUIRE(U >= BAS_PLAN_MIN_U, BAS_E_SHAPE, "%s: needs an upsampling factor >= %d (U=%d)", who, BAS_PLAN_MIN_U, U);
     BAS_REQUIRE(K % S == 0, BAS_E_SHAPE, "%s: subchunksize does not divide chunksize evenly (K=%d S=%d)", who, K, S);
     BAS_REQUIRE(T_in % K == 0, BAS_E_SHAPE, "%s: T_in (%ld) must be a multiple of K (%d)", who, T_in, K);
@@ -968,11 +985,11 @@ static int stream_block_impl(const char *who, float *x, long x_stride, const flo
                              double *elev, double *azim, long ang_stride, int nh, int nb, double *last, float *running_peak,
                              bas_stream_t stream, void *ev_begin, void *ev_end, double *gain = nullptr,
                              double *gain_last = nullptr, bool need_gain = false) {
-    const long B = T_in - halo;
-    BAS_REQUIRE(n_src > 0 && halo >= 0 && B > 0 && nh >= 0 && nb >= 2, BAS_E_SHAPE,
+    BAS_REQUIRE(n_src > 0 && halo >= 0 && T_in > halo && nh >= 0 && nb >= 2, BAS_E_SHAPE,
                 "%s: need n_src>0, halo>=0, T_in>halo, nh>=0, nb>=2 (n_src=%d halo=%d T_in=%ld nh=%d nb=%d)", who, n_src, halo,
                 T_in, nh, nb);
-    BAS_REQUIRE(ang_stride >= nh + nb, BAS_E_SHAPE, "%s: ang_stride shorter than nh + nb", who);
+    BAS_REQUIRE(ang_stride >= (long)nh + nb, BAS_E_SHAPE, "%s: ang_stride shorter than nh + nb", who);
+    const long B = T_in - halo;
     BAS_REQUIRE(x && elev && azim && last && (!need_gain || (gain && gain_last)), BAS_E_NULL, "%s: null pointer", who);
     BasCarry C;
     C.x = x; C.x_stride = x_stride; C.n_src = n_src; C.halo = halo; C.B = B;

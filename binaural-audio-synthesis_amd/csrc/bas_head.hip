@@ -24,22 +24,8 @@ __global__ __launch_bounds__(HR_THREADS) void bas_head_relative_kernel(
     }
 }
 
-// the written layout [G][n_src][nb] with strides (sg, ss, 1) addresses no element twice: every dimension of more than one
-// element, in ascending stride order, steps over the whole extent of the ones before it
-static bool hr_one_to_one(int G, int n_src, int nb, long sg, long ss) {
-    long st[3] = {1, ss, sg}, ex[3] = {nb, n_src, G};
-    if (st[1] > st[2]) {
-        const long t = st[1], e = ex[1];
-        st[1] = st[2]; ex[1] = ex[2]; st[2] = t; ex[2] = e;
-    }
-    long span = 1;                                       // elements covered by the dimensions so far, stride 1 first
-    for (int k = 0; k < 3; ++k) {
-        if (ex[k] == 1) continue;
-        if (st[k] < span) return false;
-        span = st[k] * ex[k];
-    }
-    return true;
-}
+// the written layout [G][n_src][nb] with strides (sg, ss, 1) addresses no element twice (bas_internal.h)
+static bool hr_one_to_one(int G, int n_src, int nb, long sg, long ss) { return bas_layout_one_to_one(G, n_src, nb, sg, ss); }
 
 static bool hr_aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 

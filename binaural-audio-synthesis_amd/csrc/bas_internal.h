@@ -49,6 +49,76 @@ int bas_launch_slab_reduce(const float *slab, int tile, int n_src, int units_per
 #define BAS_REQUIRE(cond, code, ...) \
     do { if (!(cond)) return bas_fail((code), __VA_ARGS__); } while (0)
 
+// Render sizes inside the ceilings of bas.h (BAS_MAX_*): the planners compute nothing beyond them - they answer "not
+// served" - and the render entry points return BAS_E_SHAPE.  Inside, every expression of the planners fits its type.
+static inline bool bas_sizes_in_range(int n_src, long T_in, int K, int S, int L) {
+    return n_src <= BAS_MAX_N_SRC && T_in <= BAS_MAX_T_IN && K <= BAS_MAX_K && S <= BAS_MAX_K && L <= BAS_MAX_L;
+}
+#define BAS_REQUIRE_SIZES(who, n_src, T_in, K, S, L)                                                                    \
+    BAS_REQUIRE(bas_sizes_in_range(n_src, T_in, K, S, L), BAS_E_SHAPE,                                                  \
+                "%s: sizes beyond the ceilings of bas.h (n_src=%d T_in=%ld K=%d S=%d L=%d; BAS_MAX_N_SRC=%d "           \
+                "BAS_MAX_T_IN=%ld BAS_MAX_K=%d BAS_MAX_L=%d)", who, n_src, T_in, K, S, L, BAS_MAX_N_SRC, BAS_MAX_T_IN, \
+                BAS_MAX_K, BAS_MAX_L)
+
+// (tile, source) work units are int indices in the kernels; the launchers refuse more than this
+#define BAS_MAX_UNITS ((1L << 31) - 65536)
+
+// The deal of `units` work units over at most `slots` workgroups: equal contiguous shares, so every workgroup finishes
+// at the same time; a workgroup whose share crosses source boundaries leaves one partial tile per boundary.  False (all
+// zero) when the units do not fit an int index: the launchers then refuse the shape.
+static inline bool bas_deal_units(long units, long slots, int n_src, int tile, int *units_per_wg, int *n_wg,
+                                  int *parts_per_wg, size_t *slab_bytes) {
+    *units_per_wg = *n_wg = *parts_per_wg = 0;
+    *slab_bytes = 0;
+    if (units <= 0 || slots <= 0 || units >= BAS_MAX_UNITS) return false;
+    const long wg = units < slots ? units : slots;
+    *units_per_wg = (int)((units + wg - 1) / wg);
+    *n_wg = (int)((units + *units_per_wg - 1) / *units_per_wg);
+    *parts_per_wg = (int)(((long)*units_per_wg + n_src - 2) / n_src + 1);
+    *slab_bytes = (size_t)*n_wg * *parts_per_wg * 2 * tile * sizeof(float);
+    return true;
+}
+
+// A written layout [G][rows][nb] with element strides (sg, ss, 1), all >= 0, addresses no element twice.  Exact: two
+// elements share an address exactly when some (dr, dg) != (0, 0) with |dr| < rows, |dg| < G has |dr ss + dg sg| < nb.
+// The nested layouts every renderer uses pass the first test (every dimension of more than one element, in ascending stride
+// order, steps over the whole extent of the ones before it); the others - interleaved, non-nested - take the search: for
+// every dg the dr that brings dr ss + dg sg nearest to zero, min(G, rows) steps in 128-bit arithmetic.
+static inline bool bas_layout_one_to_one(long G, long rows, long nb, long sg, long ss) {
+    if (G <= 0 || rows <= 0 || nb <= 0 || sg < 0 || ss < 0) return false;
+    {
+        long st[3] = {1, ss, sg}, ex[3] = {nb, rows, G};
+        if (st[1] > st[2]) {
+            const long t = st[1], e = ex[1];
+            st[1] = st[2]; ex[1] = ex[2]; st[2] = t; ex[2] = e;
+        }
+        long span = 1;                                   // elements covered by the dimensions so far, stride 1 first
+        bool nested = true;
+        for (int k = 0; k < 3 && nested; ++k) {
+            if (ex[k] == 1) continue;
+            if (st[k] < span || __builtin_mul_overflow(st[k], ex[k], &span)) nested = false;
+        }
+        if (nested) return true;
+    }
+    if (G > rows) {                                      // the outer loop over the shorter dimension
+        const long t = G, u = sg;
+        G = rows; sg = ss; rows = t; ss = u;
+    }
+    if (rows > 1 && ss < nb) return false;               // dg = 0
+    for (long dg = 1; dg < G; ++dg) {
+        const __int128 v = (__int128)dg * sg;            // dr = -k: v - k ss, k = 0 .. rows - 1
+        if (ss == 0) {
+            if (v < nb) return false;
+            continue;
+        }
+        __int128 k = v / ss;
+        if (k > rows - 1) k = rows - 1;
+        if (v - k * ss < nb) return false;               // from above (>= 0)
+        if (k + 1 <= rows - 1 && (k + 1) * ss - v < nb) return false;   // from below
+    }
+    return true;
+}
+
 // non-negative remainder for any int c and M > 0
 __device__ __forceinline__ int bas_pmod(long long c, int M) {
     long long r = c % (long long)M;

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void bas_pack_kernel(const float *__restrict__
 
 extern "C" size_t bas_table_packed_floats(int ndir, int M, int U) {
     if (ndir <= 0 || U <= 0 || M <= 0 || M % U) return 0;
-    return (size_t)2 * ndir * U * BAS_PLANE(M / U);
+    return (size_t)2 * ndir * U * BAS_PLANE((size_t)(M / U));   // (the plane in size_t: M / U + 4 may not fit an int)
 }
 
 extern "C" int bas_table_pack_f32(const float *irs, int ndir, int M, int U, float *packed,
@@ -56,8 +56,9 @@ extern "C" int bas_table_pack_f32(const float *irs, int ndir, int M, int U, floa
     BAS_REQUIRE(irs && packed, BAS_E_NULL, "bas_table_pack_f32: null pointer");
     BAS_REQUIRE(ndir > 0 && U > 0 && M > 0 && M % U == 0, BAS_E_SHAPE,
                 "bas_table_pack_f32: need ndir>0, U>0, M>0, M %% U == 0 (ndir=%d M=%d U=%d)", ndir, M, U);
+    BAS_REQUIRE(bas_table_floats(ndir, M / U, U) >= 0, BAS_E_SHAPE, "bas_table_pack_f32: table too large");
     long rows = 2L * ndir;
-    long total = rows * U * BAS_PLANE(M / U);
+    long total = bas_table_floats(ndir, M / U, U);
     int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(bas_pack_kernel, dim3(grid), dim3(256), 0, bas_stream(stream), irs, rows, M, U,
                        M / U, packed);
@@ -91,7 +92,7 @@ extern "C" int bas_delay_signal_f32(const float *x, const double *shifts, int n,
     BAS_REQUIRE(n >= 0 && M > 0 && down >= 1, BAS_E_SHAPE,
                 "bas_delay_signal_f32: need n>=0, M>0, down>=1 (n=%d M=%d down=%d)", n, M, down);
     if (n == 0) return 0;
-    int Mout = (M + down - 1) / down;
+    int Mout = (int)(((long)M + down - 1) / down);
     long total = (long)n * Mout;
     int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(bas_delay_kernel, dim3(grid), dim3(256), 0, bas_stream(stream), x, shifts, n, M,
@@ -568,12 +569,11 @@ static int plan_impl(const char *who, const double *diffs, const int32_t *idx, c
     BAS_REQUIRE(diffs && ((idx && w && (gain || !need_gain)) || n == 0), BAS_E_NULL, "%s: null pointer", who);   // (no queries: idx, w may be null)
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U > 0, BAS_E_SHAPE,
                 "%s: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", who, n, ndir, L, U);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "%s: table too large", who);
+    BAS_REQUIRE(bas_table_floats(ndir, L, U) >= 0, BAS_E_SHAPE, "%s: table too large", who);
     BAS_REQUIRE(U >= BAS_PLAN_MIN_U, BAS_E_SHAPE,
                 "%s: read plans need an upsampling factor >= %d (U=%d): use bas_interp2d_f32", who, BAS_PLAN_MIN_U, U);
     if (n == 0) return 0;
-    BAS_REQUIRE(plans && plans_bytes >= bas_interp2d_workspace_bytes(n) &&
-                    reinterpret_cast<uintptr_t>(plans) % 16 == 0,
+    BAS_REQUIRE(plans && plans_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(plans) % 16 == 0,
                 BAS_E_WORKSPACE, "%s: 16-byte aligned buffer of %zu bytes needed, %zu given", who,
                 bas_interp2d_workspace_bytes(n), plans_bytes);
     const long rows = 2L * n;
@@ -605,7 +605,7 @@ static int plan_angles_impl(const char *who, const double *diffs, const double *
                 "%s: need n>=0, ndir>0, L>0, U>=%d (n=%d ndir=%d L=%d U=%d)", who, BAS_PLAN_MIN_U, n, ndir, L, U);
     BAS_REQUIRE(branch == BAS_BRANCH_F64 || branch == BAS_BRANCH_PYFLOAT, BAS_E_SHAPE,
                 "%s: branch must be BAS_BRANCH_F64 (0) or BAS_BRANCH_PYFLOAT (1), got %d", who, branch);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "%s: table too large", who);
+    BAS_REQUIRE(bas_table_floats(ndir, L, U) >= 0, BAS_E_SHAPE, "%s: table too large", who);
     if (n == 0) return 0;
     BAS_REQUIRE(plans && plans_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(plans) % 16 == 0,
                 BAS_E_WORKSPACE, "%s: 16-byte aligned buffer of %zu bytes needed, %zu given", who,
@@ -616,7 +616,7 @@ static int plan_angles_impl(const char *who, const double *diffs, const double *
         PA.R.ring_elev[i] = ring_elev[i];
         PA.R.ring_start[i] = ring_start[i];
         PA.R.ring_count[i] = ring_count[i];
-        BAS_REQUIRE(PA.R.ring_count[i] > 0 && PA.R.ring_start[i] >= 0 && PA.R.ring_start[i] + PA.R.ring_count[i] <= ndir,
+        BAS_REQUIRE(PA.R.ring_count[i] > 0 && PA.R.ring_start[i] >= 0 && PA.R.ring_start[i] <= ndir - PA.R.ring_count[i],
                     BAS_E_SHAPE, "%s: ring %d out of the %d-direction table", who, i, ndir);
     }
     const long rows = 2L * n;
@@ -651,7 +651,7 @@ static int interp2d_impl(const char *who, const float *packed, const double *dif
                 who);   // (no queries: idx, w, H may be null)
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U > 0, BAS_E_SHAPE,
                 "%s: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", who, n, ndir, L, U);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "%s: table too large", who);
+    BAS_REQUIRE(bas_table_floats(ndir, L, U) >= 0, BAS_E_SHAPE, "%s: table too large", who);
     if (n == 0) return 0;
     BAS_REQUIRE(ws && ws_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
                 BAS_E_WORKSPACE, "%s: 16-byte aligned workspace of %zu bytes needed, %zu given", who,
@@ -735,7 +735,7 @@ extern "C" int bas_ring_interp_f32(const float *packed, const double *diffs, con
     BAS_REQUIRE(packed && diffs && pq && alpha && out, BAS_E_NULL, "bas_ring_interp_f32: null pointer");
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U > 0, BAS_E_SHAPE,
                 "bas_ring_interp_f32: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", n, ndir, L, U);
-    BAS_REQUIRE((long)2 * ndir * BAS_PLANE(L) * U < (1L << 31), BAS_E_SHAPE, "bas_ring_interp_f32: table too large");
+    BAS_REQUIRE(bas_table_floats(ndir, L, U) >= 0, BAS_E_SHAPE, "bas_ring_interp_f32: table too large");
     if (n == 0) return 0;
     int step = return_upsampled ? 1 : U;
     int Mout = return_upsampled ? L * U : L;
@@ -787,10 +787,10 @@ static int traj_params_launch(const char *who, const double *elev, const double 
         R.ring_elev[i] = ring_elev[i];
         R.ring_start[i] = ring_start[i];
         R.ring_count[i] = ring_count[i];
-        BAS_REQUIRE(R.ring_count[i] > 0 && R.ring_start[i] >= 0 && R.ring_start[i] + R.ring_count[i] <= 187,
+        BAS_REQUIRE(R.ring_count[i] > 0 && R.ring_start[i] >= 0 && R.ring_start[i] <= 187 - R.ring_count[i],
                     BAS_E_SHAPE, "%s: ring %d out of the 187-direction table", who, i);
     }
-    long blocks = (n + 255) / 256;
+    long blocks = n / 256 + (n % 256 != 0);
     if (blocks > 8192) blocks = 8192;
     if (branch == BAS_BRANCH_PYFLOAT)
         hipLaunchKernelGGL(bas_traj_params_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, bas_stream(stream), elev,

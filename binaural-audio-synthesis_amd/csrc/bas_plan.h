@@ -23,6 +23,14 @@
 #define BAS_PLANE(L) ((L) + 4)
 #endif
 
+// Floats of a packed table of positive sizes, 2 ears x ndir x U planes, or -1 where that is 2^31 or more: the kernels address
+// the table through 32-bit offsets.  In 128 bits: the product of three ints does not fit 64.
+static inline long bas_table_floats(int ndir, int L, int U) {
+    if (ndir <= 0 || L <= 0 || U <= 0) return -1;
+    const __int128 f = (__int128)2 * ndir * U * BAS_PLANE((__int128)L);
+    return f < ((__int128)1 << 31) ? (long)f : -1;
+}
+
 // A set's five reads need j - ph0 <= U for every j <= 4: upsampling factors below 4 use bas_interp2d_f32's plain kernel.
 #define BAS_PLAN_MIN_U 4
 

@@ -989,7 +989,7 @@ __global__ __launch_bounds__(256) void bas_mix_finish_kernel(const float *__rest
 }
 
 int bas_grid_for(long items, int cap) {
-    long g = (items + 255) / 256;
+    long g = items / 256 + (items % 256 != 0);           // (not (items + 255) / 256: any long)
     if (g < 1) g = 1;
     return (int)(g < cap ? g : cap);
 }
@@ -1104,7 +1104,7 @@ struct RenderPlan {
 static RenderPlan plan_render(int n_src, long T_in, int K, int S, int L, bool aligned) {
     RenderPlan p = {};
     p.kind = KIND_GENERIC;
-    const bool s_pow2 = (S & (S - 1)) == 0;
+    const bool s_pow2 = S > 0 && (S & (S - 1)) == 0;
     const bool hd_small_s = s_pow2 && S >= 4 && S < 32 && K % 32 == 0;        // rows of 32 hold 2 / 4 / 8 subchunks
                                                                               // (16 / 32 per row build for minutes: not offered)
 #ifdef BAS_DIAG
@@ -1112,7 +1112,7 @@ static RenderPlan plan_render(int n_src, long T_in, int K, int S, int L, bool al
 #else
     const char *force = nullptr;
 #endif
-    if (!(aligned && n_src > 0 && T_in > 0)) return p;
+    if (!(aligned && n_src > 0 && T_in > 0 && K > 0 && S > 0 && L > 0 && bas_sizes_in_range(n_src, T_in, K, S, L))) return p;
     if (!(S % 32 == 0 || hd_small_s)) {
         // Any other subchunk size >= 2 (any chunk size >= 32; the caller keeps rows 16-byte aligned through x_stride):
         // the hd kernel's multi-part row step.  One slot more than the rows reach: the part of a row behind a chunk
@@ -1133,12 +1133,8 @@ static RenderPlan plan_render(int n_src, long T_in, int K, int S, int L, bool al
         const long T_out = T_in + L - 1;
         p.n_tiles = (T_out + p.tile - 1) / p.tile;
         p.units_total = p.n_tiles * n_src;
-        long slots = wg_per_cu * bas_device_cus();
-        long wg = p.units_total < slots ? p.units_total : slots;
-        p.units_per_wg = (int)((p.units_total + wg - 1) / wg);
-        p.n_wg = (int)((p.units_total + p.units_per_wg - 1) / p.units_per_wg);
-        p.parts_per_wg = (p.units_per_wg + n_src - 2) / n_src + 1;
-        p.slab_bytes = (size_t)p.n_wg * p.parts_per_wg * 2 * p.tile * sizeof(float);
+        bas_deal_units(p.units_total, wg_per_cu * bas_device_cus(), n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg,
+                       &p.slab_bytes);
         return p;
     }
     const int hd_slots = (K - 32 + 32 * (HD_ROWS - 1)) / K + 1;
@@ -1172,12 +1168,8 @@ static RenderPlan plan_render(int n_src, long T_in, int K, int S, int L, bool al
     const long T_out = T_in + L - 1;
     p.n_tiles = (T_out + p.tile - 1) / p.tile;
     p.units_total = p.n_tiles * n_src;
-    long slots = wg_per_cu * bas_device_cus();
-    long wg = p.units_total < slots ? p.units_total : slots;
-    p.units_per_wg = (int)((p.units_total + wg - 1) / wg);
-    p.n_wg = (int)((p.units_total + p.units_per_wg - 1) / p.units_per_wg);
-    p.parts_per_wg = (p.units_per_wg + n_src - 2) / n_src + 1;
-    p.slab_bytes = (size_t)p.n_wg * p.parts_per_wg * 2 * p.tile * sizeof(float);
+    bas_deal_units(p.units_total, wg_per_cu * bas_device_cus(), n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg,
+                   &p.slab_bytes);
     return p;
 }
 
@@ -1193,12 +1185,8 @@ extern "C" size_t bas_render_workspace_bytes(int n_src, long T_in, int K, int S,
         q.tile = RT_TILE;
         q.n_tiles = (T_out + RT_TILE - 1) / RT_TILE;
         q.units_total = q.n_tiles * n_src;
-        long slots = 2L * bas_device_cus();
-        long wg = q.units_total < slots ? q.units_total : slots;
-        q.units_per_wg = (int)((q.units_total + wg - 1) / wg);
-        q.n_wg = (int)((q.units_total + q.units_per_wg - 1) / q.units_per_wg);
-        q.parts_per_wg = (q.units_per_wg + n_src - 2) / n_src + 1;
-        size_t alt = (size_t)q.n_wg * q.parts_per_wg * 2 * RT_TILE * sizeof(float);
+        size_t alt = 0;
+        bas_deal_units(q.units_total, 2L * bas_device_cus(), n_src, RT_TILE, &q.units_per_wg, &q.n_wg, &q.parts_per_wg, &alt);
         if (alt > need) need = alt;
     }
     return BAS_WS_HEAD_BYTES + need + 16;                    // (the head is the library's control area: never slab space)
@@ -1222,6 +1210,7 @@ static int render_mix_impl(const float *x, long x_stride, const float *H, int n_
                 "bas_render_mix_f32: subchunksize does not divide chunksize evenly (K=%d S=%d)", K, S);
     BAS_REQUIRE(T_in % K == 0, BAS_E_SHAPE, "bas_render_mix_f32: T_in (%ld) must be a multiple of K (%d)", T_in,
                 K);
+    BAS_REQUIRE_SIZES("bas_render_mix_f32", n_src, T_in, K, S, L);
     BAS_REQUIRE(n_src == 0 || T_in == 0 || (x && H), BAS_E_NULL, "bas_render_mix_f32: x or H is null");
     BAS_REQUIRE(n_src == 0 || x_stride >= T_in, BAS_E_SHAPE, "bas_render_mix_f32: x_stride < T_in");
     BAS_REQUIRE(T_in / K < (1L << 30), BAS_E_SHAPE, "bas_render_mix_f32: too many chunks");
@@ -1367,7 +1356,7 @@ extern "C" int bas_mix_finish_f32(const float *parts, int n_parts, long part_str
     T.ctl = reinterpret_cast<unsigned *>(ws);
     T.wgpeak = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + BAS_CTL_WORDS * 4);
     T.y = y; T.n = n; T.peak = peak; T.normalize = normalize ? 1 : 0;
-    const int grid = bas_grid_for((n + 3) / 4, 2048);
+    const int grid = bas_grid_for(n / 4 + (n % 4 != 0), 2048);
     T.n_wg = (unsigned)grid;
     hipLaunchKernelGGL(bas_mix_finish_kernel, dim3(grid), dim3(256), 0, st, parts, n_parts, part_stride, n, y, T);
     return bas_check_launch("bas_mix_finish_f32");

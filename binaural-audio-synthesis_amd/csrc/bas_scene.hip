@@ -71,22 +71,8 @@ __global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneAr
     }
 }
 
-// the written layout [G][rows][nb] with strides (sg, ss, 1) addresses no element twice: every dimension of more than one
-// element, in ascending stride order, steps over the whole extent of the ones before it
-static bool sc_one_to_one(long G, long rows, long nb, long sg, long ss) {
-    long st[3] = {1, ss, sg}, ex[3] = {nb, rows, G};
-    if (st[1] > st[2]) {
-        const long t = st[1], e = ex[1];
-        st[1] = st[2]; ex[1] = ex[2]; st[2] = t; ex[2] = e;
-    }
-    long span = 1;
-    for (int k = 0; k < 3; ++k) {
-        if (ex[k] == 1) continue;
-        if (st[k] < span) return false;
-        span = st[k] * ex[k];
-    }
-    return true;
-}
+// the written layout [G][rows][nb] with strides (sg, ss, 1) addresses no element twice (bas_internal.h)
+static bool sc_one_to_one(long G, long rows, long nb, long sg, long ss) { return bas_layout_one_to_one(G, rows, nb, sg, ss); }
 
 static bool sc_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 

@@ -131,12 +131,12 @@ static int sb_blocks_x(int n_sessions, long work) {
 // the checks both entry points share: sizes, then the strides against the layout's extent
 static int sb_check_layout(const char *what, int n_sessions, int n_src, long B, int K, int halo, long x_stride,
                            long ang_stride) {
-    BAS_REQUIRE(n_sessions > 0 && n_sessions <= 65535 && n_src > 0 && K > 0 && B > 0 && halo >= 0, BAS_E_SHAPE,
-                "%s: need 0 < n_sessions <= 65535, n_src > 0, K > 0, B > 0, halo >= 0 (G=%d n_src=%d K=%d B=%ld halo=%d)",
+    BAS_REQUIRE(n_sessions > 0 && n_sessions <= 65535 && n_src > 0 && K > 0 && B > 0 && B <= BAS_MAX_T_IN && halo >= 0, BAS_E_SHAPE,
+                "%s: need 0 < n_sessions <= 65535, n_src > 0, K > 0, 0 < B <= 2^41, halo >= 0 (G=%d n_src=%d K=%d B=%ld halo=%d)",
                 what, n_sessions, n_src, K, B, halo);
     BAS_REQUIRE(B % K == 0 && halo % K == 0, BAS_E_SHAPE, "%s: B (%ld) and halo (%d) must be multiples of K (%d)", what, B,
                 halo, K);
-    const long W = halo + B + K, nh = halo / K, nb = B / K + 1;
+    const long W = (long)halo + B + K, nh = halo / K, nb = B / K + 1;
     BAS_REQUIRE(x_stride >= n_sessions * W - K && ang_stride >= n_sessions * (nh + nb), BAS_E_SHAPE,
                 "%s: strides shorter than the layout (x_stride %ld < %ld or ang_stride %ld < %ld)", what, x_stride,
                 n_sessions * W - K, ang_stride, n_sessions * (nh + nb));
@@ -161,10 +161,10 @@ static int sb_pack(const char *what, const float *blocks, const double *elev, co
                     "%s: interp must be 0 (linear) or 1 (cubic)", what);
         BAS_REQUIRE(max_delay >= (interp == BAS_DELAY_CUBIC ? 2.0 : 1.0) && max_delay + 2.0 <= (double)H, BAS_E_SHAPE,
                     "%s: max_delay must lie in [d_min, H - 2]", what);
-        BAS_REQUIRE(raw_s >= H + B && raw_g >= (long)n_src * raw_s, BAS_E_SHAPE,
+        BAS_REQUIRE(raw_s >= H + B && raw_g / raw_s >= n_src, BAS_E_SHAPE,
                     "%s: raw strides shorter than [H | B] rows", what);
     }
-    const long W = halo + B + K;
+    const long W = (long)halo + B + K;
     const int nh = halo / K, nb = (int)(B / K + 1);
     const dim3 grid(sb_blocks_x(n_sessions, (long)n_src * (((B + 3) >> 2) + nb)), n_sessions);
     hipLaunchKernelGGL((bas_stream_batch_pack_kernel<HEAD, GAIN, DELAY>), grid, dim3(SB_THREADS), 0, bas_stream(stream),
@@ -225,7 +225,7 @@ static int sb_epilogue(const char *what, float *x, long x_stride, int n_sessions
                        bool need_gain, const float *y, long y_stride, float *peaks, bas_stream_t stream) {
     int rc = sb_check_layout(what, n_sessions, n_src, B, K, halo, x_stride, ang_stride);
     if (rc) return rc;
-    const long W = halo + B + K;
+    const long W = (long)halo + B + K;
     BAS_REQUIRE(y_stride >= n_sessions * W - K, BAS_E_SHAPE, "%s: y_stride %ld < T_in %ld", what, y_stride,
                 n_sessions * W - K);
     BAS_REQUIRE(x && elev && azim && last && y && peaks && (!need_gain || (gain && gain_last)), BAS_E_NULL,
@@ -261,7 +261,7 @@ static int stream_epilogue(const char *what, float *x, long x_stride, int n_src,
     BAS_REQUIRE(n_src >= 0 && halo >= 0 && B > 0 && nh >= 0 && nb >= 2, BAS_E_SHAPE,
                 "%s: need n_src>=0, halo>=0, B>0, nh>=0, nb>=2 (n_src=%d halo=%d B=%ld nh=%d nb=%d)", what, n_src, halo, B,
                 nh, nb);
-    BAS_REQUIRE(x_stride >= halo + B && ang_stride >= nh + nb && y_stride >= halo + B, BAS_E_SHAPE,
+    BAS_REQUIRE(B <= BAS_MAX_T_IN && x_stride >= halo + B && ang_stride >= (long)nh + nb && y_stride >= halo + B, BAS_E_SHAPE,
                 "%s: strides shorter than the window", what);
     BAS_REQUIRE(y && (n_src == 0 || (x && elev && azim && last && (!need_gain || (gain && gain_last)))), BAS_E_NULL,
                 "%s: null pointer", what);

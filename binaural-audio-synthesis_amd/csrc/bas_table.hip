@@ -141,7 +141,7 @@ extern "C" int bas_resample_up_f64(const double *x, int rows, int lx, const doub
     int rc = table_args("bas_resample_up_f64", x, rows, lx, h, Lh, p);
     if (rc) return rc;
     BAS_REQUIRE(y, BAS_E_NULL, "bas_resample_up_f64: y is null");
-    const size_t lds = sizeof(double) * (size_t)(2 * Lh + 1 + lx);
+    const size_t lds = sizeof(double) * ((size_t)2 * Lh + 1 + (size_t)lx);
     BAS_REQUIRE(lds <= 64 * 1024, BAS_E_SHAPE, "bas_resample_up_f64: filter + one row (%zu bytes) must fit 64 KB of LDS", lds);
     hipLaunchKernelGGL(bas_resample_up_kernel, dim3((unsigned)rows), dim3(256), lds, bas_stream(stream), x, lx, h, Lh, p, y);
     return bas_check_launch("bas_resample_up_f64");
@@ -154,7 +154,7 @@ extern "C" int bas_delaydiffs_f64(const double *irs, int n_dir, int n_taps, cons
     BAS_REQUIRE(diffs && status, BAS_E_NULL, "bas_delaydiffs_f64: diffs or status is null");
     BAS_REQUIRE(reinterpret_cast<uintptr_t>(status) % 8 == 0, BAS_E_ALIGN, "bas_delaydiffs_f64: status must be 8-byte aligned");
     BAS_REQUIRE(n_dir <= 65535, BAS_E_SHAPE, "bas_delaydiffs_f64: more than 65535 directions");
-    const size_t lds = sizeof(double) * (size_t)(2 * Lh + 1 + 2 * n_taps + 2 * n_taps - 1);
+    const size_t lds = sizeof(double) * ((size_t)2 * Lh + 1 + (size_t)2 * n_taps + (size_t)2 * n_taps - 1);
     BAS_REQUIRE(lds <= 64 * 1024, BAS_E_SHAPE,
                 "bas_delaydiffs_f64: filter, two signals and their correlation (%zu bytes) must fit 64 KB of LDS", lds);
     hipStream_t st = bas_stream(stream);

@@ -39,6 +39,28 @@ extern "C" {
 
 #define BAS_WS_CONTROL_BYTES 2048   /* head of every workspace: the library's control block (see bas_render_mix_fused_f32) */
 
+/* Ceilings of the render sizes (n_src, T_in, K, S, L).  Inside them every size and plan query is computed without
+ * overflow and in bounded time; beyond any of them bas_render_fused_supported answers 0 (kernel name "", workspace
+ * of the head alone), bas_render_kernel_name answers the generic kernel, bas_render_workspace_bytes the head alone,
+ * and the render entry points (bas_render_mix_f32, bas_render_mix_fused_f32, their _profiled, _fir_, _reduce_ and
+ * stream-block siblings) return BAS_E_SHAPE.  Each comes from what the kernels can address:
+ *   BAS_MAX_K      2^24: the crossfade weight of an input sample is (float)(m % K) / K (apply_hrtf.py:442-443 in
+ *                  binary32), and binary32 holds the integers up to 2^24 exactly;
+ *   BAS_MAX_L      2^18: the fused kernels read the packed table through 32-bit byte offsets, so
+ *                  2 ears x ndir x U x (L + 4) x 4 bytes < 2^31; with the table's 187 directions and the smallest
+ *                  planned factor U = 4 that is L < 358 836, and 2^18 is the power of two below;
+ *   BAS_MAX_N_SRC  2^30 - 1: the n_src x (T_in / K + 1) chunk-boundary queries of a render are counted in an int
+ *                  and every source has at least two boundaries;
+ *   BAS_MAX_T_IN   2^41: (tile, source) work units are int indices, and the smallest tile has 2048 outputs, so
+ *                  T_in + L - 1 < 2^31 x 2^11 = 2^42; 2^41 leaves room for any L.  (T_in / K < 2^30 still holds
+ *                  on top: the chunk index is an int.)
+ * A shape inside the ceilings whose (tile, source) units reach 2^31 - 65536 gets a workspace size of the head alone and
+ * BAS_E_SHAPE ("render in blocks") from the render entry points that would run a fast kernel. */
+#define BAS_MAX_K     (1 << 24)
+#define BAS_MAX_L     (1 << 18)
+#define BAS_MAX_N_SRC ((1 << 30) - 1)
+#define BAS_MAX_T_IN  (1L << 41)
+
 typedef void *bas_stream_t;    /* hipStream_t */
 
 /* Library / ABI version (BAS_ABI_VERSION). */
@@ -59,7 +81,8 @@ const char *bas_last_error(void);
  * shift followed by decimation (apply_hrtf.py:156-165) are contiguous across
  * lanes and neither "one sample earlier" nor "the next three taps" need a wrap test.  bas_table_packed_floats() gives
  * the size of `packed` in floats (0 for invalid shapes); the layout belongs to the library build that packed it
- * (a build with -DBAS_PLANE_DOUBLE=1 keeps every plane's samples twice). */
+ * (a build with -DBAS_PLANE_DOUBLE=1 keeps every plane's samples twice).  Every entry point that takes a table,
+ * bas_table_pack_f32 included, refuses one of 2^31 floats or more (BAS_E_SHAPE: the kernels use 32-bit offsets). */
 size_t bas_table_packed_floats(int ndir, int M, int U);
 int bas_table_pack_f32(const float *irs, int ndir, int M, int U, float *packed,
                        bas_stream_t stream);
@@ -127,7 +150,8 @@ int bas_traj_params_branch_f64(const double *elev, const double *azim, long n,
  *   w   [n][3] f64   = (top_alpha, bot_alpha, a)
  *   H   [n][2 ears][L] f32
  *   ws / ws_bytes: 16-byte aligned scratch of bas_interp2d_workspace_bytes(n) bytes
- *      (per-(query, ear) read plans handed from the plan kernel to the eval kernel). */
+ *      (per-(query, ear) read plans handed from the plan kernel to the eval kernel).  BAS_E_WORKSPACE when it is NULL,
+ *      too small or not 16-byte aligned - here and for the `plans` buffer of the bas_interp2d_plan_* entry points. */
 size_t bas_interp2d_workspace_bytes(int n);
 int bas_interp2d_f32(const float *packed, const double *diffs, const int32_t *idx,
                      const double *w, int n, int ndir, int L, int U, float *H, void *ws,
@@ -341,7 +365,8 @@ int bas_render_stream_block_profiled_f32(float *x, long x_stride, const float *p
  *   peaks[b] = m_b = max|y| over both ears of item b's window (:462, device float [B], overwritten); with normalize != 0
  *   the rule per item: if m_b > 1 the window is divided by m_b (:463-464).  out == NULL: in place; else out [B][2]
  *   [out_len_max] is written whole (the window, then zeros).  A memset and two launches (maxima, then scale or compact);
- *   bitwise deterministic (max is exact; atomicMax on the bits of non-negative floats); B <= 65535. */
+ *   bitwise deterministic (max is exact; atomicMax on the bits of non-negative floats); B <= 65535.
+ * Codes of the packs: x_stride < T_in, x_stride % 4 != 0 or T_in > BAS_MAX_T_IN: BAS_E_SHAPE; x not 16-byte aligned: BAS_E_ALIGN. */
 int bas_batch_pack_f32(const float *sig, int n_items, int n_src, long N, const long *lengths, const long *offsets,
                        const double *elev, const double *azim, long n_q_max, int K, long T_in, float *x,
                        long x_stride, double *elev_out, double *azim_out, bas_stream_t stream);
@@ -356,7 +381,7 @@ int bas_batch_finish_f32(float *y, long y_stride, int n_items, const long *offse
  * gap chunk's boundaries are both, and its input is zero.  The FIR needs no gap (an emitted sample, at >= halo >= L-1
  * into its window, reads only inputs of that window: apply_hrtf.py:444-453).  Angle rows: nh + nb boundaries per session
  * (nh = halo / K, nb = B / K + 1), session g's from g (nh + nb); T_in / K + 1 = G (nh + nb).  K divides B and halo;
- * x_stride >= T_in, ang_stride >= G (nh + nb); G <= 65535 (one row of workgroups per session).
+ * x_stride >= T_in, ang_stride >= G (nh + nb); G <= 65535 (one row of workgroups per session); B <= BAS_MAX_T_IN.
  *
  * bas_stream_batch_pack_f32: blocks [G][n_src][B] float32 -> x[s][g W + halo + j]; elev/azim [G][n_src][nb] float64 (the
  *   block's boundaries t0, t0 + K, .., t0 + B: :429, :435) -> elev_out/azim_out[s][g (nh + nb) + nh + c].  The halo
@@ -464,7 +489,8 @@ int bas_batch_pack_gain_f32(const float *sig, int n_items, int n_src, long N, co
  *     or 0 offline: the row's valid length + 4 (no output changes: every read past it lands before sample 0).  One launch;
  *     T < 2^30, n_groups n_src <= 65535.  y must not overlap x's readable range.
  *   bas_delay_carry_f32: the raw history of a stream block: row[0 .. H) = row[B .. B + H) for every (g, s) row (row =
- *     x + g x_stride_g + s x_stride_s at the history's start), B < H (overlapping) included.  One launch.
+ *     x + g x_stride_g + s x_stride_s at the history's start), B < H (overlapping) included.  One launch; n_groups n_src
+ *     < 2^31 (one workgroup per row).
  *   bas_batch_pack_delay_f32: bas_batch_pack_gain_f32 (gain NULL: bas_batch_pack_f32) with item b's DELAYED input in its
  *     segment: delay [B][n_src][n_q_max] is read where it is (no packed delay array), item b's reads are bounded by its
  *     own valid length (the offline rule above), the gaps stay zeros.  Still one launch.
