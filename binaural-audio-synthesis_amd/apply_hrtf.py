@@ -186,13 +186,14 @@ def check_gain(gain, shape):
     return arr
 
 
-def _is_device_gain(gain, shape):
-    """gain is a device tensor: checked for shape and dtype only (as device angles and heads are).  False for host data."""
+def is_device_arg(arg, shape, dtype, name):
+    """A per-boundary argument (gain, delay) is a device tensor: checked for shape and dtype only (as device angles and
+    heads are).  False for host data, which the argument's check_* function validates."""
     import torch
-    if not (isinstance(gain, torch.Tensor) and gain.is_cuda):
+    if not (isinstance(arg, torch.Tensor) and arg.is_cuda):
         return False
-    if tuple(gain.shape) != tuple(shape) or gain.dtype != torch.float64:
-        raise ValueError(f"gain must be a float64 tensor of shape {tuple(shape)}")
+    if tuple(arg.shape) != tuple(shape) or arg.dtype != dtype:
+        raise ValueError(f"{name} must be a {str(dtype).split('.')[-1]} tensor of shape {tuple(shape)}")
     return True
 
 
@@ -202,7 +203,7 @@ def gain_to_device(gain, shape, dev, buf=None):
     (allocated when None or of another shape).  Returns (tensor, buf)."""
     import torch
     shape = tuple(shape)
-    if _is_device_gain(gain, shape):
+    if is_device_arg(gain, shape, torch.float64, "gain"):
         if gain.device == dev and gain.is_contiguous():
             return gain, buf
         src = gain
@@ -212,17 +213,6 @@ def gain_to_device(gain, shape, dev, buf=None):
         buf = torch.empty(shape, dtype=torch.float64, device=dev)
     buf.copy_(src)
     return buf, buf
-
-
-def stage_gain(gain, view):
-    """Copy a gain argument into a renderer's gain view (a device tensor that is the view itself: nothing to do)."""
-    import torch
-    if _is_device_gain(gain, view.shape):
-        if gain.data_ptr() == view.data_ptr() and gain.stride() == view.stride():
-            return
-        view.copy_(gain)
-    else:
-        view.copy_(torch.from_numpy(check_gain(gain, view.shape)))
 
 
 def _flat_device_gain(gain, n_q):

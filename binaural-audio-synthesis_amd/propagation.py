@@ -66,34 +66,13 @@ def check_delay(delay, shape, interp, max_delay=None):
     return arr
 
 
-def is_device_delay(delay, shape):
-    """delay is a device tensor: checked for shape and dtype only (as device angles, heads and gains are).  False for
-    host data."""
-    import torch
-    if not (isinstance(delay, torch.Tensor) and delay.is_cuda):
-        return False
-    if tuple(delay.shape) != tuple(shape) or delay.dtype != torch.float64:
-        raise ValueError(f"delay must be a float64 tensor of shape {tuple(shape)}")
-    return True
-
-
 def delay_to_device(delay, shape, interp, dev, max_delay=None):
     """A delay argument as a contiguous float64 tensor of `shape` on `dev` (host data validated by check_delay first)."""
     import torch
-    if is_device_delay(delay, shape):
+    from .apply_hrtf import is_device_arg
+    if is_device_arg(delay, shape, torch.float64, "delay"):
         return delay.to(dev).contiguous()
     return torch.from_numpy(np.ascontiguousarray(check_delay(delay, shape, interp, max_delay))).to(dev)
-
-
-def stage_delay(delay, view, interp, max_delay):
-    """Copy a delay argument into a renderer's delay view (a device tensor that is the view itself: nothing to do)."""
-    import torch
-    if is_device_delay(delay, view.shape):
-        if delay.data_ptr() == view.data_ptr() and delay.stride() == view.stride():
-            return
-        view.copy_(delay)
-    else:
-        view.copy_(torch.from_numpy(check_delay(delay, view.shape, interp, max_delay)))
 
 
 def delayed_inputs(x, K, delay, interp="cubic", lengths=None, history=None, max_delay=None):
@@ -253,17 +232,6 @@ def color_to_device(color, rows, n_q, dev, taps=None):
         t = color.to(dev)
         return t if t.stride(-1) == 1 and all(s >= 0 for s in t.stride()) else t.contiguous()
     return torch.from_numpy(np.ascontiguousarray(check_color(color, rows, n_q, taps))).to(dev)
-
-
-def stage_color(color, view):
-    """Copy a colour argument (already checked) into a renderer's colour view (the view itself: nothing to do)."""
-    import torch
-    if isinstance(color, torch.Tensor) and color.is_cuda:
-        if color.data_ptr() == view.data_ptr() and color.stride() == view.stride():
-            return
-        view.copy_(color)
-    else:
-        view.copy_(torch.from_numpy(np.asarray(color.numpy() if hasattr(color, "numpy") else color, dtype=np.float32)))
 
 
 def colored_inputs(x, K, color, lengths=None, history=None):

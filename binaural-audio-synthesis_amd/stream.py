@@ -23,7 +23,9 @@ instead).  With graph=True those are replayed as ONE hipGraph launch.  `prepare(
 captures the graph BEFORE streaming starts (capture synchronises the device and must not
 race with allocations of other threads: keep it out of the real-time phase); without it the
 first block of a size runs as plain launches and the second one captures.  That life cycle, the render of a window
-and the workspaces it needs live in _BlockStream, which StreamRenderer and stream_batch.StreamBatchRenderer share.
+and the workspaces it needs live in _BlockStream, which StreamRenderer and stream_batch.StreamBatchRenderer share; so do
+the rules for process()'s per-boundary arguments, the live gains and the delay's state.  Samples carried from block to
+block (inputs, raw inputs of a delayed stream, pre-colour inputs of a coloured one) live in _CarriedRows.
 
 Why the halo is a whole number of CHUNKS (K) rather than L-1 rounded to 32: the kernels
 take windows whose first sample lies on a chunk boundary (the crossfade position of an input
@@ -32,8 +34,7 @@ tiles of 2048 samples anyway - a 512-sample block with a 512-sample halo is ONE 
 source, exactly as it would be with a 128-sample halo.
 """
 from . import _hip, sphere, propagation
-from .apply_hrtf import (as_device_table, plan_angles_device, render_angles_device, check_gain, stage_gain,
-                         _is_device_gain)
+from .apply_hrtf import as_device_table, plan_angles_device, render_angles_device, check_gain, is_device_arg
 
 
 def rotate_into_views(elev, azim, head, views):
@@ -64,6 +65,61 @@ def _is_buffer(t, view, dtype):
     return t.is_cuda and t.dtype == dtype and t.data_ptr() == view.data_ptr() and t.stride() == view.stride()
 
 
+def stage(arg, view, name=None, check=None):
+    """Copy one argument of a block (samples, angles, gains, delays, colour) into the renderer's own view of it; when it is
+    that view (a producer wrote there in place) there is nothing to copy.  check: None for an argument that has passed its
+    checks, else the host validator check(arg, shape) -> numpy array (check_gain, check_delay): host data goes through it,
+    a device tensor is checked for shape and dtype only (is_device_arg, which names the argument `name`)."""
+    import torch
+    if check is None or is_device_arg(arg, view.shape, view.dtype, name):
+        t = arg if isinstance(arg, torch.Tensor) else torch.as_tensor(arg)
+        if not _is_buffer(t, view, view.dtype):
+            view.copy_(t)                                 # (H2D for host arrays; float64 kept exactly)
+    else:
+        view.copy_(torch.from_numpy(check(arg, view.shape)))
+
+
+class _CarriedRows:
+    """float32 rows [..., rows, front + capacity], zero at first: columns [0, front) carry the last `front` samples of the
+    previous block, the new block lands behind them.  The row stride is a multiple of 4 samples whenever `front` is (a
+    16-byte aligned block behind an aligned front), and it decides whether the one-call path serves the window."""
+
+    def __init__(self, lead, front, device):
+        import torch
+        self.front, self.device = int(front), device
+        self._set(torch.zeros((*lead, self.front), dtype=torch.float32, device=device))
+
+    def _set(self, buf):
+        """The buffer and bas_delay_carry_f32's geometry of it (group stride, row stride, groups, rows; [rows, .] is one
+        group), fixed until it grows: reading it off the tensor costs every plain-launch block about 2 us per carry."""
+        self.buf = buf
+        groups, stride_g = (buf.shape[0], buf.stride(0)) if buf.dim() == 3 else (1, 0)
+        self._geometry = (stride_g, buf.stride(-2), groups, buf.shape[-2])
+
+    def reserve(self, B):
+        """Room for blocks of B samples; the front is kept.  True when the buffer was re-allocated (a graph that captured
+        its pointers is gone)."""
+        import torch
+        if self.buf.shape[-1] - self.front >= B:
+            return False
+        grown = torch.zeros((*self.buf.shape[:-1], (self.front + B + 3) // 4 * 4), dtype=torch.float32, device=self.buf.device)
+        grown[..., :self.front] = self.buf[..., :self.front]
+        self._set(grown)
+        return True
+
+    def block(self, B):
+        return self.buf[..., self.front:self.front + B]
+
+    def window(self, B):
+        return self.buf[..., :self.front + B]
+
+    def carry(self, B):
+        """One bas_delay_carry_f32 launch: the last `front` samples of [front | block of B] move to the front."""
+        with _hip.on_device(self.device):
+            _hip.call("bas_delay_carry_f32", _hip.ptr(self.buf), *self._geometry, self.front, B,
+                      _hip.current_stream(self.device))
+
+
 def tile_filling_block(about, chunksize, ir_length, tile=8192):
     """The largest block length <= `about` (a multiple of the chunk size) whose window - [halo | block] inputs, L - 1 more
     outputs - ends on a tile boundary of the big scenes' FIR kernel (8192 outputs per (tile, source) unit) or just before it.
@@ -81,11 +137,15 @@ def tile_filling_block(about, chunksize, ir_length, tile=8192):
 class _BlockStream:
     """What a block-wise renderer does the same way whatever its layout: the table, K, S and the halo; the block's hipGraph
     (the first block of a size runs plain, the second captures; prepare() captures before streaming starts); the render of
-    one window and its workspaces; process()'s fresh tensor or view.  A subclass lays out its buffers (_layout, which sets
-    _blocks_in_layout to 0 and drops _graph), stages the inputs, and provides _block_body (the stream-ordered work of one
-    block), input_view, _carried (the tensors prepare() must leave as they were) and _emitted (the samples a block emits)."""
+    one window and its workspaces; process()'s fresh tensor or view; the per-boundary arguments every renderer takes: the
+    rules process() checks them by, the live gains and the delay's bound, history length and carried
+    raw rows (§3.11).  `lead` is the shape in front of a per-boundary argument's boundaries and of a block's samples:
+    (n_src,) or (G, n_src).  A subclass lays out its buffers (_layout, which sets _blocks_in_layout to 0, drops _graph and
+    makes _elev_all, _azim_all and, with max_delay, _delay_all), stages the inputs, and provides _block_body (the
+    stream-ordered work of one block), input_view, _boundary_view (a block's part of an angle or gain buffer), _carried
+    (the tensors prepare() must leave as they were) and _emitted (the samples a block emits)."""
 
-    def __init__(self, tbl, chunksize, subchunksize, graph, copy_out):
+    def __init__(self, tbl, chunksize, subchunksize, graph, copy_out, lead, max_delay=None, interp="cubic"):
         assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
         self.tbl = as_device_table(tbl)
         self.K, self.S = int(chunksize), int(subchunksize)
@@ -95,6 +155,85 @@ class _BlockStream:
         self._graph = None
         self._blocks_in_layout = 0
         self._events = None                               # (begin, end) raw hipEvent_t around the FIR kernel of plain-launch blocks (bench.py)
+        self._lead = tuple(lead)
+        # per-source gains (DESIGN.md §3.10): None until the first gained block or gain_view() - until then the buffers,
+        # the launches and the graph are the gain-less ones.  Then rows beside the angles (the halo's part carried) and the
+        # gain at the END of the last block, for finish()
+        self._gain_all = None
+        self._gain_last = None
+        # propagation delay: raw input rows [*lead, H + capacity] - columns [0, H) carry the last H raw
+        # samples, a block's raw input lands behind them and its delayed input goes into the window - and the block's delays
+        propagation.interp_code(interp)
+        self.interp = interp
+        self.max_delay = None if max_delay is None else propagation.check_max_delay(max_delay, interp)
+        self.H = 0 if max_delay is None else propagation.history_samples(self.max_delay)
+        self._raw_rows = None if max_delay is None else _CarriedRows(self._lead, self.H, self.tbl.device)
+        self._delay_all = None
+
+    @property
+    def _raw(self):
+        """The carried raw rows' tensor (None without max_delay)."""
+        return None if self._raw_rows is None else self._raw_rows.buf
+
+    def _check_args(self, shape, elev, azim, gain, delay):
+        """process()'s rules for a block's per-boundary arguments of `shape`, checked before the renderer's state
+        changes (a refused call leaves its launches and graph): ValueError for a wrong shape, bad host values (device
+        tensors are checked for shape and dtype only), a delay the renderer was not built for or a missing one."""
+        import torch
+        for t in (elev, azim):
+            if tuple((t if isinstance(t, torch.Tensor) else torch.as_tensor(t)).shape) != shape:
+                raise ValueError(f"elev/azim must have shape {shape}")
+        if gain is not None and not is_device_arg(gain, shape, torch.float64, "gain"):
+            check_gain(gain, shape)
+        if (delay is None) != (self.max_delay is None):
+            raise ValueError("delay= is required by a renderer built with max_delay" if delay is None else
+                             "delay= needs a renderer built with max_delay")
+        if delay is not None and not is_device_arg(delay, shape, torch.float64, "delay"):
+            self._check_delay(delay, shape)
+
+    def _check_delay(self, delay, shape):
+        return propagation.check_delay(delay, shape, self.interp, self.max_delay)
+
+    def _enable_gain(self):
+        """Make the gain rows live (ones: the gain-less render's bits), once; the block's launches change, so does its graph."""
+        import torch
+        if self._gain_all is None:
+            self._gain_all = torch.ones_like(self._elev_all)
+            self._gain_last = torch.ones(self._lead, dtype=torch.float64, device=self.tbl.device)
+            self._graph, self._blocks_in_layout = None, 0
+
+    def _block_gain_view(self, gain):
+        """The gain view of the block laid out: with gain= the gains go live, and without it a gained renderer's block has
+        gains of one (None for a renderer never given a gain)."""
+        if gain is not None:
+            self._enable_gain()
+        elif self._gain_all is not None:
+            self._boundary_view(self._gain_all).fill_(1.0)
+        return None if self._gain_all is None else self._boundary_view(self._gain_all)
+
+    def trajectory_views(self, B):
+        """Device views (elev, azim), float64 [*lead, B/K + 1], of the renderer's own trajectory buffers for blocks of B
+        samples (strided: the slots behind the carried halo boundaries): a producer that fills them in place and passes
+        them to process() saves two copies."""
+        self._layout(B)
+        return self._boundary_view(self._elev_all), self._boundary_view(self._azim_all)
+
+    def gain_view(self, B):
+        """Device view, float64 [*lead, B/K + 1], of the renderer's own gain buffer for blocks of B samples (DESIGN.md
+        §3.10), beside trajectory_views(B): a producer that writes the gains there and passes the view to process(gain=)
+        saves the copy.  Makes the gains live (a renderer never given a gain keeps the gain-less launches)."""
+        self._layout(B)
+        self._enable_gain()
+        return self._boundary_view(self._gain_all)
+
+    def delay_view(self, B):
+        """Device view, float64 [*lead, B/K + 1], of the renderer's own delay buffer for blocks of B samples (DESIGN.md
+        §3.11), beside gain_view(B): a producer that writes the delays there and passes the view to process(delay=) saves
+        the copy.  Only for a renderer built with max_delay (ValueError otherwise)."""
+        if self.max_delay is None:
+            raise ValueError("delay_view: the renderer was built without max_delay")
+        self._layout(B)
+        return self._delay_all
 
     def _window_workspaces(self, n_src, T_in, n_q):
         """The render workspace of a window of n_src x T_in inputs (the larger of the stored-IR and the fused path's) and
@@ -173,12 +312,12 @@ class StreamRenderer(_BlockStream):
         import torch
         if color_taps is not None and not 1 <= int(color_taps) <= propagation.MAX_TAPS:
             raise ValueError(f"color_taps must be in 1..{propagation.MAX_TAPS}")
-        super().__init__(tbl, chunksize, subchunksize, graph, copy_out)
         self.n_src = int(n_src)
+        super().__init__(tbl, chunksize, subchunksize, graph, copy_out, (self.n_src,), max_delay, interp)
         dev = self.tbl.device
-        # input staging buffer [n_src, halo + capacity]: columns [0, halo) carry the previous inputs, a block
-        # is rendered in place behind them (input_view() lets a producer write there directly: no copy)
-        self._xbuf = torch.zeros((self.n_src, self.halo), dtype=torch.float32, device=dev)
+        # input rows [n_src, halo + capacity]: columns [0, halo) carry the previous inputs (moved there by the block's
+        # epilogue or reduce kernel), a block is rendered in place behind them
+        self._x_rows = _CarriedRows(self._lead, self.halo, dev)
         self._B = None                                    # block size the per-block buffers are laid out for
         self._halo_params = None                          # (elev, azim) [n_src, nh] of the halo's boundaries across a re-layout
         self._started = False                             # a block has been rendered
@@ -189,48 +328,26 @@ class StreamRenderer(_BlockStream):
         self.samples_in = 0
         self._finished = False
         self._head_buf = None                             # device staging of host head orientations (process(head=...))
-        # per-source gains (DESIGN.md §3.10): None until the first gained block or gain_view() - until then the buffers,
-        # the launches and the graph are the gain-less ones.  Then [n_src, nh + nb] beside the angles (halo part carried)
-        # and the gain at the END of the last block, for finish()
-        self._gain_all = None
-        self._gain_last = None
-        # propagation delay: raw input rows [n_src, H + capacity] - columns [0, H) carry the last H raw
-        # samples, a block's raw input lands behind them and its delayed input goes into _xbuf - and the block's delays
-        propagation.interp_code(interp)
-        self.interp = interp
-        self.max_delay = None if max_delay is None else propagation.check_max_delay(max_delay, interp)
-        self.H = 0 if max_delay is None else propagation.history_samples(self.max_delay)
-        self._raw = None if max_delay is None else torch.zeros((self.n_src, self.H), dtype=torch.float32, device=dev)
-        self._delay_all = None
         # colour: pre-colour rows [n_src, Tc + capacity] - columns [0, Tc) carry the last Tc pre-colour
         # samples; what would fill the FIR window (the block, or its delayed input) lands behind them and the colour launch
         # writes the window - the block's coefficient sets [n_src, nb, M], and the one set per row of the static form
         self.color_taps = None if color_taps is None else int(color_taps)
         self.Tc = 0 if color_taps is None else propagation.tail_samples(self.color_taps)
-        self._pre = None if color_taps is None else torch.zeros((self.n_src, self.Tc), dtype=torch.float32, device=dev)
+        self._pre_rows = None if color_taps is None else _CarriedRows(self._lead, self.Tc, dev)
         self._color_all = None
         self._color_static = None
         self._static_color = False                        # the block's colour launch reads _color_static
+        # a block's way in: raw -> (delay) -> pre-colour -> (colour) -> window.  input_view() is the first one's block
+        self._chain = [r for r in (self._raw_rows, self._pre_rows) if r is not None] + [self._x_rows]
+
+    _xbuf = property(lambda self: self._x_rows.buf, doc="The input rows' tensor.")
+    _pre = property(lambda self: None if self._pre_rows is None else self._pre_rows.buf, doc="The pre-colour rows' tensor.")
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _reserve(self, B):
-        import torch
-        cap = self._xbuf.shape[1] - self.halo
-        if cap < B:
-            grown = torch.zeros((self.n_src, (self.halo + B + 3) // 4 * 4), dtype=torch.float32, device=self._xbuf.device)
-            grown[:, :self.halo] = self._xbuf[:, :self.halo]
-            self._xbuf = grown
-            self._graph = None                            # the captured pointers are gone
-        if self._raw is not None and self._raw.shape[1] - self.H < B:
-            grown = torch.zeros((self.n_src, self.H + (B + 3) // 4 * 4), dtype=torch.float32, device=self._raw.device)
-            grown[:, :self.H] = self._raw[:, :self.H]     # the carried raw history survives the growth
-            self._raw = grown
-            self._graph = None
-        if self._pre is not None and self._pre.shape[1] - self.Tc < B:
-            grown = torch.zeros((self.n_src, self.Tc + (B + 3) // 4 * 4), dtype=torch.float32, device=self._pre.device)
-            grown[:, :self.Tc] = self._pre[:, :self.Tc]   # the carried pre-colour tail survives the growth
-            self._pre = grown
-            self._graph = None
+        for rows in self._chain:
+            if rows.reserve(B):
+                self._graph = None                        # the captured pointers are gone
 
     def _layout(self, B):
         """Per-block buffers for blocks of B samples (kept until another size arrives)."""
@@ -254,58 +371,24 @@ class StreamRenderer(_BlockStream):
             g = torch.ones((n, nh + nb), dtype=torch.float64, device=dev)
             g[:, :nh] = self._gain_all[:, :nh]
             self._gain_all = g
-        if self._raw is not None:                         # (not carried: each block brings its boundaries' delays)
+        if self._raw_rows is not None:                    # (not carried: each block brings its boundaries' delays)
             self._delay_all = torch.zeros((n, nb), dtype=torch.float64, device=dev)
-        if self._pre is not None:                         # (not carried either: each block brings its boundaries' sets)
+        if self._pre_rows is not None:                    # (not carried either: each block brings its boundaries' sets)
             self._color_all = torch.zeros((n, nb, self.color_taps), dtype=torch.float32, device=dev)
         self._y = torch.empty((2, self.halo + B + self.tbl.L - 1), dtype=torch.float32, device=dev)
         self._window_workspaces(n, self.halo + B, n * (nh + nb))
 
-    def _enable_gain(self):
-        """Make the gain rows live (ones: the gain-less render's bits), once; the block's launches change, so does its graph."""
-        import torch
-        if self._gain_all is None:
-            dev = self.tbl.device
-            self._gain_all = torch.ones((self.n_src, self.nh + self._nb), dtype=torch.float64, device=dev)
-            self._gain_last = torch.ones((self.n_src,), dtype=torch.float64, device=dev)
-            self._graph, self._blocks_in_layout = None, 0
+    def _boundary_view(self, buf):
+        return buf[:, self.nh:]
 
     def input_view(self, B):
         """Device view [n_src, B] of the renderer's own input buffer.  A producer (decoder, H2D copy,
         another kernel) that writes the next block here and passes this view to process() saves the
         staging copy of the block; the view is valid until the next input_view() call with a larger B.
         Growing the buffer allocates and drops the captured graph: size it once, before prepare().  With max_delay the
-        view holds the block's raw input (the renderer delays it)."""
+        view holds the block's raw input (the renderer delays it), with color_taps alone its pre-colour input."""
         self._reserve(B)
-        if self._raw is not None:
-            return self._raw[:, self.H:self.H + B]
-        if self._pre is not None:
-            return self._pre[:, self.Tc:self.Tc + B]
-        return self._xbuf[:, self.halo:self.halo + B]
-
-    def trajectory_views(self, B):
-        """Device views (elev, azim), float64 [n_src, B/K + 1], of the renderer's own trajectory buffers for
-        blocks of B samples (strided: they sit behind the carried halo boundaries): a producer that fills them in
-        place and passes them to process() saves two copies."""
-        self._layout(B)
-        return self._elev_all[:, self.nh:], self._azim_all[:, self.nh:]
-
-    def gain_view(self, B):
-        """Device view, float64 [n_src, B/K + 1], of the renderer's own gain buffer for blocks of B samples (DESIGN.md
-        §3.10), beside trajectory_views(B): a producer that writes the gains there and passes the view to process(gain=)
-        saves the copy.  Makes the gains live (a renderer never given a gain keeps the gain-less launches)."""
-        self._layout(B)
-        self._enable_gain()
-        return self._gain_all[:, self.nh:]
-
-    def delay_view(self, B):
-        """Device view, float64 [n_src, B/K + 1], of the renderer's own delay buffer for blocks of B samples (DESIGN.md
-        §3.11), beside gain_view(B): a producer that writes the delays there and passes the view to process(delay=) saves
-        the copy.  Only for a renderer built with max_delay (ValueError otherwise)."""
-        if self.max_delay is None:
-            raise ValueError("delay_view: the renderer was built without max_delay")
-        self._layout(B)
-        return self._delay_all
+        return self._chain[0].block(B)
 
     def _use_static_color(self, static):
         """Switch the block's colour launch between the per-boundary sets and the one set per row (its graph changes)."""
@@ -333,79 +416,51 @@ class StreamRenderer(_BlockStream):
     def _block_body(self):
         """The stream-ordered work of one block on the per-block buffers (captured into the hipGraph)."""
         B, nb, nh, halo = self._B, self._nb, self.nh, self.halo
-        dev = self.tbl.device
-        x = self._xbuf[:, :halo + B]
-        tbl, n = self.tbl, self.n_src
-        lib = _hip.lib()
-        if self._raw is not None:
-            # the block's delayed input into the window behind the halo (one launch), then the raw history moves behind
-            # the block (one launch): the last H raw samples go to the front for the next block
-            dst = self._xbuf[:, halo:halo + B] if self._pre is None else self._pre[:, self.Tc:self.Tc + B]
-            propagation.delay_rows_device(self._raw[:, self.H:self.H + B], self._delay_all, self.K, self.interp,
-                                          dst, H=self.H, max_delay=self.max_delay)
-            with _hip.on_device(dev):
-                _hip.call("bas_delay_carry_f32", _hip.ptr(self._raw), 0, self._raw.stride(0), 1, n, self.H, B,
-                          _hip.current_stream(dev))
-        if self._pre is not None:
-            # the block's coloured input into the window behind the halo (one launch), then the last Tc pre-colour samples
-            # move to the front for the next block (one launch; nothing to move at M = 1)
-            propagation.color_rows_device(self._pre[:, self.Tc:self.Tc + B],
-                                          self._color_static if self._static_color else self._color_all, self.K,
-                                          self._xbuf[:, halo:halo + B], Hc=self.Tc)
-            with _hip.on_device(dev):
-                _hip.call("bas_delay_carry_f32", _hip.ptr(self._pre), 0, self._pre.stride(0), 1, n, self.Tc, B,
-                          _hip.current_stream(dev))
-        with _hip.on_device(dev):
-            one_call = self.one_call and bool(lib.bas_render_fused_supported(n, halo + B, self.K, self.S, tbl.L)) and tbl.upsampling >= 4 \
-                and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-        g = self._gain_all
-        if one_call and g is not None:
-            # the same with the gains folded into the plans and carried beside the angles (DESIGN.md §3.10)
-            if self._events is not None:
-                raise ValueError("profiling events (bench.py) time gain-less blocks only: a gained block has no profiled "
-                                 "entry point")
-            plan_angles_device(tbl, self._elev_all, self._azim_all, self._ws_plans, gain=g)
-            with _hip.on_device(dev):
-                _hip.call("bas_render_stream_block_gain_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), _hip.ptr(tbl.packed),
-                          _hip.ptr(self._ws_plans), n, halo + B, self.K, self.S, tbl.L, tbl.upsampling, tbl.ndir,
-                          _hip.ptr(self._y), _hip.ptr(self._ws), self._ws.numel(), halo, _hip.ptr(self._elev_all),
-                          _hip.ptr(self._azim_all), _hip.ptr(g), self._elev_all.stride(0), nh, nb, _hip.ptr(self._last),
-                          _hip.ptr(self._gain_last), _hip.ptr(self._peak_dev), _hip.current_stream(dev))
-            return
-        if one_call:
-            # read plans (a3 inside), then ONE call: chunk IRs + FIR + mix, and behind the sums of its reduce kernel the
-            # running peak over the emitted samples + the carry of the last `halo` inputs and of the angles at their chunk
-            # boundaries (t0+B-halo .. t0+B-K) + the angles at t0+B for finish()
-            plan_angles_device(tbl, self._elev_all, self._azim_all, self._ws_plans)
-            args = (_hip.ptr(self._xbuf), self._xbuf.stride(0), _hip.ptr(tbl.packed), _hip.ptr(self._ws_plans), n, halo + B,
-                    self.K, self.S, tbl.L, tbl.upsampling, tbl.ndir, _hip.ptr(self._y), _hip.ptr(self._ws), self._ws.numel(),
-                    halo, _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0), nh, nb,
-                    _hip.ptr(self._last), _hip.ptr(self._peak_dev), _hip.current_stream(dev))
-            with _hip.on_device(dev):
-                if self._events is None:
-                    _hip.call("bas_render_stream_block_f32", *args)
-                else:
-                    _hip.call("bas_render_stream_block_profiled_f32", *args, self._events[0], self._events[1])
-            return
-        # other shapes: the render of the window, then the epilogue launch
-        self._render_window(x, self._elev_all, self._azim_all, gain=g)
-        with _hip.on_device(dev):
-            if g is None:
-                _hip.call("bas_stream_epilogue_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), self.n_src, halo, B,
-                          _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0), nh, nb,
-                          _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peak_dev),
-                          _hip.current_stream(dev))
+        tbl, n, dev = self.tbl, self.n_src, self.tbl.device
+        # the block's way into the window behind the halo: each step fills the next rows' block (one launch: the delayed
+        # input of the raw block, the coloured one of the pre-colour block), then its own last `front` samples move to the
+        # front for the next block (one launch; nothing to move at M = 1)
+        for src, dst in zip(self._chain, self._chain[1:]):
+            if src is self._raw_rows:
+                propagation.delay_rows_device(src.block(B), self._delay_all, self.K, self.interp, dst.block(B), H=self.H,
+                                              max_delay=self.max_delay)
             else:
-                _hip.call("bas_stream_epilogue_gain_f32", _hip.ptr(self._xbuf), self._xbuf.stride(0), self.n_src, halo, B,
-                          _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), _hip.ptr(g), self._elev_all.stride(0), nh, nb,
-                          _hip.ptr(self._last), _hip.ptr(self._gain_last), _hip.ptr(self._y), self._y.stride(0),
-                          _hip.ptr(self._peak_dev), _hip.current_stream(dev))
+                propagation.color_rows_device(src.block(B), self._color_static if self._static_color else self._color_all,
+                                              self.K, dst.block(B), Hc=self.Tc)
+            src.carry(B)
+        xbuf, x = self._x_rows.buf, self._x_rows.window(B)
+        with _hip.on_device(dev):
+            one_call = self.one_call and bool(_hip.lib().bas_render_fused_supported(n, halo + B, self.K, self.S, tbl.L)) \
+                and tbl.upsampling >= 4 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+        # live gains ride beside the angles and the end angles in every argument list (DESIGN.md §3.10)
+        g = self._gain_all
+        gain, gain_last = ((), ()) if g is None else ((_hip.ptr(g),), (_hip.ptr(self._gain_last),))
+        angles = (_hip.ptr(self._elev_all), _hip.ptr(self._azim_all), *gain, self._elev_all.stride(0), nh, nb,
+                  _hip.ptr(self._last), *gain_last)
+        if not one_call:                                  # other shapes: the render of the window, then the epilogue launch
+            self._render_window(x, self._elev_all, self._azim_all, gain=g)
+            with _hip.on_device(dev):
+                _hip.call("bas_stream_epilogue_f32" if g is None else "bas_stream_epilogue_gain_f32", _hip.ptr(xbuf), xbuf.stride(0), n, halo, B, *angles,
+                          _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peak_dev), _hip.current_stream(dev))
+            return
+        events = () if self._events is None else (self._events[0], self._events[1])
+        if events and g is not None:
+            raise ValueError("profiling events (bench.py) time gain-less blocks only: a gained block has no profiled "
+                             "entry point")
+        # read plans (a3 inside; the gains folded in), then ONE call: chunk IRs + FIR + mix, and behind the sums of its
+        # reduce kernel the running peak over the emitted samples + the carry of the last `halo` inputs and of the angles
+        # (and gains) at their chunk boundaries (t0+B-halo .. t0+B-K) + the angles (and gains) at t0+B for finish()
+        plan_angles_device(tbl, self._elev_all, self._azim_all, self._ws_plans, gain=g)
+        entry = "bas_render_stream_block_gain_f32" if g is not None else \
+            "bas_render_stream_block_profiled_f32" if events else "bas_render_stream_block_f32"
+        with _hip.on_device(dev):
+            _hip.call(entry, _hip.ptr(xbuf), xbuf.stride(0), _hip.ptr(tbl.packed), _hip.ptr(self._ws_plans), n, halo + B, self.K, self.S, tbl.L, tbl.upsampling,
+                      tbl.ndir, _hip.ptr(self._y), _hip.ptr(self._ws), self._ws.numel(), halo, *angles,
+                      _hip.ptr(self._peak_dev), _hip.current_stream(dev), *events)
 
     def _carried(self):
-        gains = () if self._gain_all is None else (self._gain_all, self._gain_last)
-        raw = () if self._raw is None else (self._raw[:, :self.H + self._B], self._delay_all)
-        pre = () if self._pre is None else (self._pre[:, :self.Tc + self._B], self._color_all)
-        return (self._xbuf[:, :self.halo + self._B], self._elev_all, self._azim_all, self._last, self._peak_dev) + gains + raw + pre
+        live = [t for t in (self._gain_all, self._gain_last, self._delay_all, self._color_all) if t is not None]
+        return [r.window(self._B) for r in self._chain] + [self._elev_all, self._azim_all, self._last, self._peak_dev] + live
 
     def _emitted(self):
         return self._y[:, self.halo:self.halo + self._B].t()
@@ -444,16 +499,7 @@ class StreamRenderer(_BlockStream):
         self._layout(B)
         nb = self._nb
         # every argument is checked before the renderer's state changes (a refused call leaves its launches and graph)
-        for t in (elev, azim):
-            if tuple(torch.as_tensor(t).shape) != (self.n_src, nb):
-                raise ValueError(f"elev/azim must have shape ({self.n_src}, {nb})")
-        if gain is not None and not _is_device_gain(gain, (self.n_src, nb)):
-            check_gain(gain, (self.n_src, nb))
-        if (delay is None) != (self.max_delay is None):
-            raise ValueError("delay= is required by a renderer built with max_delay" if delay is None else
-                             "delay= needs a renderer built with max_delay")
-        if delay is not None and not propagation.is_device_delay(delay, (self.n_src, nb)):
-            propagation.check_delay(delay, (self.n_src, nb), self.interp, self.max_delay)
+        self._check_args((self.n_src, nb), elev, azim, gain, delay)
         if (color is None) != (self.color_taps is None):
             raise ValueError("color= is required by a renderer built with color_taps" if color is None else
                              "color= needs a renderer built with color_taps")
@@ -461,26 +507,21 @@ class StreamRenderer(_BlockStream):
             color = propagation.check_color(color, self.n_src, nb, self.color_taps)
         if head is not None:
             q, self._head_buf = sphere.head_to_device(head, (nb, 4), self.tbl.device, self._head_buf)
+        gview = self._block_gain_view(gain)
         if gain is not None:
-            self._enable_gain()
-            stage_gain(gain, self._gain_all[:, self.nh:])
-        elif self._gain_all is not None:
-            self._gain_all[:, self.nh:].fill_(1.0)
+            stage(gain, gview, "gain", check_gain)
+        views = (self._boundary_view(self._elev_all), self._boundary_view(self._azim_all))
         if head is None:
-            for src, dst in ((elev, self._elev_all[:, self.nh:]), (azim, self._azim_all[:, self.nh:])):
-                t = torch.as_tensor(src)
-                if not _is_buffer(t, dst, torch.float64):
-                    dst.copy_(t)                          # (H2D for host arrays; float64 kept exactly)
+            for src, dst in zip((elev, azim), views):
+                stage(src, dst)
         else:
-            rotate_into_views(elev, azim, q, (self._elev_all[:, self.nh:], self._azim_all[:, self.nh:]))
+            rotate_into_views(elev, azim, q, views)
         if delay is not None:
-            propagation.stage_delay(delay, self._delay_all, self.interp, self.max_delay)
+            stage(delay, self._delay_all, "delay", self._check_delay)
         if color is not None:
             self._use_static_color(len(color.shape) == 2)
-            propagation.stage_color(color, self._color_static if self._static_color else self._color_all)
-        x_dst = self.input_view(B)
-        if not _is_buffer(blk, x_dst, torch.float32):
-            x_dst.copy_(blk)
+            stage(color, self._color_static if self._static_color else self._color_all)
+        stage(blk, self._chain[0].block(B))               # (input_view(B): _layout has made the room)
         out = self._run_block()
         self._started = True
         self.samples_in += B

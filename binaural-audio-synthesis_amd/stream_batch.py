@@ -18,6 +18,8 @@ unchanged render (read plans + fused FIR, or the stored-IR path; no peak, no pea
 bas_stream_batch_epilogue_f32 (per-session running peaks over the emitted samples and the moves of every session's carried
 state).  With graph=True everything after the pack is replayed as one hipGraph, captured by StreamRenderer's code
 (stream._BlockStream: `prepare(B)` before streaming; else the first block of a size runs plain and the second captures).
+The rules for process()'s arguments, the live gains, the delay's state and the views of the per-boundary buffers are
+_BlockStream's too; this module adds the layout of G sessions in one render and the pack.
 
 The planner (`plan_stream_layout`) is plain numpy and needs no GPU.
 """
@@ -27,8 +29,8 @@ import numpy as np
 
 from . import _hip, sphere, propagation
 from .batch import MAX_RENDER_SAMPLES, render_batch
-from .apply_hrtf import _is_device_gain, check_gain, gain_to_device, stage_gain
-from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views
+from .apply_hrtf import check_gain, gain_to_device
+from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views, stage
 
 MAX_SESSIONS = 65535             # the epilogue and pack kernels have one row of workgroups per session (gridDim.y)
 
@@ -129,26 +131,16 @@ class StreamBatchRenderer(_BlockStream):
         import torch
         self.G, self.n_src = int(n_sessions), int(n_src)
         plan_stream_layout(self.G, self.n_src, int(chunksize), 1, int(chunksize))   # (session and source counts: ValueError)
-        super().__init__(tbl, chunksize, subchunksize, graph, copy_out)
+        super().__init__(tbl, chunksize, subchunksize, graph, copy_out, (self.G, self.n_src), max_delay, interp)
         dev = self.tbl.device
         self._lay = None                                  # layout of the current block size
         # the angles at the END of every session's last block (finish()), in their own buffer: a change of block size
         # re-lays the per-block buffers out and cannot lose them
         self._last = torch.zeros((self.G, 2, self.n_src), dtype=torch.float64, device=dev)
         self._peaks = torch.zeros((self.G,), dtype=torch.float32, device=dev)
-        # per-source gains: None until the first gained block or gain_view(); then rows laid out as the
-        # angles [n_src, G (nh + nb)] and every session's gain at the end of its last block [G, n_src]
-        self._gain = None
-        self._gain_last = None
+        # (live gains, DESIGN.md §3.10: rows laid out as the angles [n_src, G (nh + nb)], end gains [G, n_src]; the raw
+        # rows of a delayed renderer, §3.11: [G, n_src, H + capacity], the block's delays [G, n_src, nb])
         self._gain_in = None                              # dense staging of host gains for the fused pack
-        # propagation delay: raw input [G, n_src, H + capacity] - [0, H) the session's last H raw samples,
-        # the block's raw input behind them - and the block's delays [G, n_src, nb]
-        propagation.interp_code(interp)
-        self.interp = interp
-        self.max_delay = None if max_delay is None else propagation.check_max_delay(max_delay, interp)
-        self.H = 0 if max_delay is None else propagation.history_samples(self.max_delay)
-        self._raw = None
-        self._delay = None
 
     # ---- buffers ---------------------------------------------------------------------------------------
     def _x3(self, x=None, lay=None):
@@ -172,19 +164,18 @@ class StreamBatchRenderer(_BlockStream):
         x = torch.zeros((n, (self.G * lay.W + 3) // 4 * 4), dtype=torch.float32, device=dev)
         elev = torch.zeros((n, lay.n_q), dtype=torch.float64, device=dev)
         azim = torch.zeros((n, lay.n_q), dtype=torch.float64, device=dev)
-        gain = None if self._gain is None else torch.ones((n, lay.n_q), dtype=torch.float64, device=dev)
+        gain = None if self._gain_all is None else torch.ones((n, lay.n_q), dtype=torch.float64, device=dev)
         if self._lay is not None:                         # carry every session's halo into the new layout
             self._x3(x, lay)[:, :, :halo] = self._x3()[:, :, :halo]
-            for new, old in ((elev, self._elev), (azim, self._azim), (gain, self._gain)):
+            for new, old in ((elev, self._elev_all), (azim, self._azim_all), (gain, self._gain_all)):
                 if new is not None:
                     self._a3(new, lay)[:, :, :nh] = self._a3(old)[:, :, :nh]
-        self._lay, self._x, self._elev, self._azim, self._gain = lay, x, elev, azim, gain
-        if self.max_delay is not None:                    # the raw histories survive the re-layout
-            raw = torch.zeros((self.G, n, self.H + (B + 3) // 4 * 4), dtype=torch.float32, device=dev)
-            if self._raw is not None:
-                raw[:, :, :self.H] = self._raw[:, :, :self.H]
-            self._raw = raw
-            self._delay = torch.zeros((self.G, n, lay.nb), dtype=torch.float64, device=dev)
+        self._lay, self._x, self._elev_all, self._azim_all, self._gain_all = lay, x, elev, azim, gain
+        # the raw rows only grow (the histories stay in front): after longer blocks their row stride is the longest
+        # block's, not this layout's, and samples of those blocks lie behind H + B, where no kernel reads
+        if self._raw_rows is not None:
+            self._raw_rows.reserve(B)
+            self._delay_all = torch.zeros((self.G, n, lay.nb), dtype=torch.float64, device=dev)
         self._gain_in = None
         self._graph, self._blocks_in_layout = None, 0
         self._y = torch.empty((2, lay.T_out), dtype=torch.float32, device=dev)
@@ -204,45 +195,15 @@ class StreamBatchRenderer(_BlockStream):
         import torch
         self._layout(B)
         lay = self._lay
-        if self._raw is not None:                         # with max_delay: the raw block behind the carried history
-            return self._raw[:, :, self.H:self.H + B]
+        if self._raw_rows is not None:                    # with max_delay: the raw block behind the carried history
+            return self._raw_rows.block(B)
         return torch.as_strided(self._x, (self.G, self.n_src, B), (lay.W, self._x.stride(0), 1), self.halo)
 
-    def trajectory_views(self, B):
-        """Device views (elev, azim), float64 [G, n_src, B/K + 1] (strided), of the renderer's own angle buffers for
-        blocks of B samples: the slots behind every session's carried halo boundaries."""
+    def _boundary_view(self, buf):
+        """[G, n_src, nb] (strided) of an angle or gain buffer: the slots behind every session's carried halo boundaries."""
         import torch
-        self._layout(B)
         lay = self._lay
-        shape, strides = (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1)
-        return (torch.as_strided(self._elev, shape, strides, lay.nh), torch.as_strided(self._azim, shape, strides, lay.nh))
-
-    def _enable_gain(self):
-        """Make the gain rows live (ones: the gain-less render's bits), once; the block's launches change, so does its graph."""
-        import torch
-        if self._gain is None:
-            dev = self.tbl.device
-            self._gain = torch.ones((self.n_src, self._lay.n_q), dtype=torch.float64, device=dev)
-            self._gain_last = torch.ones((self.G, self.n_src), dtype=torch.float64, device=dev)
-            self._graph, self._blocks_in_layout = None, 0
-
-    def gain_view(self, B):
-        """Device view, float64 [G, n_src, B/K + 1] (strided), of the renderer's own gain buffer for blocks of B samples,
-        beside trajectory_views(B): a producer that writes the gains there and passes the view to
-        process(gain=) saves the copy.  Makes the gains live."""
-        import torch
-        self._layout(B)
-        self._enable_gain()
-        lay = self._lay
-        return torch.as_strided(self._gain, (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1), lay.nh)
-
-    def delay_view(self, B):
-        """Device view, float64 [G, n_src, B/K + 1], of the renderer's own delay buffer for blocks of B samples (DESIGN.md
-        §3.11), beside gain_view(B).  Only for a renderer built with max_delay (ValueError otherwise)."""
-        if self.max_delay is None:
-            raise ValueError("delay_view: the renderer was built without max_delay")
-        self._layout(B)
-        return self._delay
+        return torch.as_strided(buf, (self.G, self.n_src, lay.nb), (lay.nh + lay.nb, lay.n_q, 1), lay.nh)
 
     def _emitted(self):
         """[G, B, 2] view of the render output: the samples this block completes for every session."""
@@ -254,27 +215,25 @@ class StreamBatchRenderer(_BlockStream):
     def _block_body(self):
         """The stream-ordered work of one block after the pack (captured into the hipGraph)."""
         lay, dev = self._lay, self.tbl.device
-        if self._raw is not None:                         # every session's last H raw samples to the front (DESIGN.md §3.11)
-            with _hip.on_device(dev):
-                _hip.call("bas_delay_carry_f32", _hip.ptr(self._raw), self._raw.stride(0), self._raw.stride(1), self.G,
-                          self.n_src, self.H, lay.B, _hip.current_stream(dev))
-        self._render_window(self._x[:, :lay.T_in], self._elev, self._azim, gain=self._gain)
+        if self._raw_rows is not None:                    # every session's last H raw samples to the front (DESIGN.md §3.11)
+            self._raw_rows.carry(lay.B)
+        self._render_window(self._x[:, :lay.T_in], self._elev_all, self._azim_all, gain=self._gain_all)
         with _hip.on_device(dev):
-            if self._gain is None:
+            if self._gain_all is None:
                 _hip.call("bas_stream_batch_epilogue_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src,
-                          self.halo, lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0),
+                          self.halo, lay.B, self.K, _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0),
                           _hip.ptr(self._last), _hip.ptr(self._y), self._y.stride(0), _hip.ptr(self._peaks),
                           _hip.current_stream(dev))
             else:
                 _hip.call("bas_stream_batch_epilogue_gain_f32", _hip.ptr(self._x), self._x.stride(0), self.G, self.n_src,
-                          self.halo, lay.B, self.K, _hip.ptr(self._elev), _hip.ptr(self._azim), _hip.ptr(self._gain),
-                          self._elev.stride(0), _hip.ptr(self._last), _hip.ptr(self._gain_last), _hip.ptr(self._y),
+                          self.halo, lay.B, self.K, _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), _hip.ptr(self._gain_all),
+                          self._elev_all.stride(0), _hip.ptr(self._last), _hip.ptr(self._gain_last), _hip.ptr(self._y),
                           self._y.stride(0), _hip.ptr(self._peaks), _hip.current_stream(dev))
 
     def _carried(self):
-        gains = () if self._gain is None else (self._gain, self._gain_last)
-        raw = () if self._raw is None else (self._raw, self._delay)
-        return (self._x, self._elev, self._azim, self._last, self._peaks) + gains + raw
+        gains = () if self._gain_all is None else (self._gain_all, self._gain_last)
+        raw = () if self._raw_rows is None else (self._raw_rows.buf, self._delay_all)
+        return (self._x, self._elev_all, self._azim_all, self._last, self._peaks) + gains + raw
 
     def process(self, blocks, elev, azim, head=None, gain=None, delay=None):
         """blocks: [G, n_src, B] (B a multiple of the chunk size); elev/azim: float64 [G, n_src, B/K + 1], every session's
@@ -301,33 +260,21 @@ class StreamBatchRenderer(_BlockStream):
         if B <= 0 or B % self.K:
             raise ValueError("block length must be a positive multiple of the chunk size")
         self._layout(B)
-        lay, dev = self._lay, self.tbl.device
+        lay = self._lay
+        angs = [torch.as_tensor(a) for a in (elev, azim)]
+        g_shape = (self.G, self.n_src, lay.nb)
+        self._check_args(g_shape, angs[0], angs[1], gain, delay)   # (before any device work)
+        dev = self.tbl.device
         x_view = self.input_view(B)
         views = self.trajectory_views(B)
-        angs = [torch.as_tensor(a) for a in (elev, azim)]
-        for t in angs:
-            if tuple(t.shape) != (self.G, self.n_src, lay.nb):
-                raise ValueError(f"elev/azim must have shape ({self.G}, {self.n_src}, {lay.nb})")
-        g_shape = (self.G, self.n_src, lay.nb)
-        if gain is not None and not _is_device_gain(gain, g_shape):
-            check_gain(gain, g_shape)                     # (host gains: validated before any device work)
-        if (delay is None) != (self.max_delay is None):
-            raise ValueError("delay= is required by a renderer built with max_delay" if delay is None else
-                             "delay= needs a renderer built with max_delay")
-        if delay is not None and not propagation.is_device_delay(delay, g_shape):
-            propagation.check_delay(delay, g_shape, self.interp, self.max_delay)
         x_in_place = _is_buffer(blk, x_view, torch.float32)
         a_in_place = all(_is_buffer(t, v, torch.float64) for t, v in zip(angs, views))
         if head is not None:                              # (the renderer's own head buffer is dense: the fused pack reads it)
             q, self._head_in = sphere.head_to_device(head, (self.G, lay.nb, 4), dev, self._head_in)
             if not (x_in_place or a_in_place):
                 q = q.contiguous()
-        gview, g_in_place = None, False
-        if gain is not None:                              # every argument is valid: the gains go live
-            gview = self.gain_view(B)
-            g_in_place = _is_buffer(gain, gview, torch.float64) if isinstance(gain, torch.Tensor) else False
-        elif self._gain is not None:                      # a gain-less block of a gained renderer: gains of one
-            self.gain_view(B).fill_(1.0)
+        gview = self._block_gain_view(gain)               # (every argument is valid: given gains go live)
+        g_in_place = isinstance(gain, torch.Tensor) and _is_buffer(gain, gview, torch.float64)
         if x_in_place or a_in_place:                      # the producer wrote part of the block in place: copy the rest
             if not x_in_place:
                 x_view.copy_(blk)
@@ -337,44 +284,47 @@ class StreamBatchRenderer(_BlockStream):
                 for t, v in zip(angs, views):
                     v.copy_(t)
             if gain is not None and not g_in_place:
-                stage_gain(gain, gview)
+                stage(gain, gview, "gain", check_gain)
             if delay is not None:                         # one launch: every session's delayed block into its window
-                propagation.stage_delay(delay, self._delay, self.interp, self.max_delay)
-                propagation.delay_rows_device(self._raw[0, :, self.H:self.H + B], self._delay[0], self.K, self.interp,
+                raw = self._raw_rows.buf
+                stage(delay, self._delay_all, "delay", self._check_delay)
+                propagation.delay_rows_device(raw[0, :, self.H:self.H + B], self._delay_all[0], self.K, self.interp,
                                               self._x[:, self.halo:self.halo + B], H=self.H, max_delay=self.max_delay,
-                                              groups=(self.G, self._raw.stride(0), self._delay.stride(0), lay.W))
+                                              groups=(self.G, raw.stride(0), self._delay_all.stride(0), lay.W))
         elif delay is not None:                           # one pack launch: delayed blocks, angles (head), gains
             blk, angs = self._dense_inputs(blk, angs, B)
-            propagation.stage_delay(delay, self._delay, self.interp, self.max_delay)
+            stage(delay, self._delay_all, "delay", self._check_delay)
+            raw = self._raw_rows.buf
             gq = None
             if gain is not None and not g_in_place:
                 gq, self._gain_in = gain_to_device(gain, g_shape, dev, self._gain_in)
             with _hip.on_device(dev):
                 _hip.call("bas_stream_batch_pack_delay_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
                           _hip.ptr(q) if head is not None else None, None if gq is None else _hip.ptr(gq),
-                          _hip.ptr(self._delay), propagation.interp_code(self.interp), self.max_delay, _hip.ptr(self._raw),
-                          self._raw.stride(0), self._raw.stride(1), self.H, self.G, self.n_src, B, self.K, self.halo,
-                          _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev), _hip.ptr(self._azim),
-                          None if gq is None else _hip.ptr(self._gain), self._elev.stride(0), _hip.current_stream(dev))
+                          _hip.ptr(self._delay_all), propagation.interp_code(self.interp), self.max_delay, _hip.ptr(raw),
+                          raw.stride(0), raw.stride(1), self.H, self.G, self.n_src, B, self.K, self.halo,
+                          _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev_all), _hip.ptr(self._azim_all),
+                          None if gq is None else _hip.ptr(self._gain_all), self._elev_all.stride(0),
+                          _hip.current_stream(dev))
         elif gain is not None and not g_in_place:         # one pack launch: blocks, angles (head) and gains
             blk, angs = self._dense_inputs(blk, angs, B)
             gq, self._gain_in = gain_to_device(gain, g_shape, dev, self._gain_in)
             with _hip.on_device(dev):
                 _hip.call("bas_stream_batch_pack_gain_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
                           _hip.ptr(q) if head is not None else None, _hip.ptr(gq), self.G, self.n_src, B, self.K, self.halo,
-                          _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev), _hip.ptr(self._azim),
-                          _hip.ptr(self._gain), self._elev.stride(0), _hip.current_stream(dev))
+                          _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev_all), _hip.ptr(self._azim_all),
+                          _hip.ptr(self._gain_all), self._elev_all.stride(0), _hip.current_stream(dev))
         else:                                             # one pack launch from dense device arrays
             blk, angs = self._dense_inputs(blk, angs, B)
             with _hip.on_device(dev):
                 if head is None:
                     _hip.call("bas_stream_batch_pack_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]), self.G,
-                              self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev),
-                              _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
+                              self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0), _hip.ptr(self._elev_all),
+                              _hip.ptr(self._azim_all), self._elev_all.stride(0), _hip.current_stream(dev))
                 else:
                     _hip.call("bas_stream_batch_pack_head_f32", _hip.ptr(blk), _hip.ptr(angs[0]), _hip.ptr(angs[1]),
                               _hip.ptr(q), self.G, self.n_src, B, self.K, self.halo, _hip.ptr(self._x), self._x.stride(0),
-                              _hip.ptr(self._elev), _hip.ptr(self._azim), self._elev.stride(0), _hip.current_stream(dev))
+                              _hip.ptr(self._elev_all), _hip.ptr(self._azim_all), self._elev_all.stride(0), _hip.current_stream(dev))
         return self._run_block()
 
     def _dense_inputs(self, blk, angs, B):
@@ -420,14 +370,14 @@ class StreamBatchRenderer(_BlockStream):
         for g0, g1 in _session_runs(self._sessions(sessions)):
             if self._lay is not None:
                 self._x3()[:, g0:g1, :self.halo].zero_()
-                self._a3(self._elev)[:, g0:g1, :self.nh].zero_()
-                self._a3(self._azim)[:, g0:g1, :self.nh].zero_()
+                self._a3(self._elev_all)[:, g0:g1, :self.nh].zero_()
+                self._a3(self._azim_all)[:, g0:g1, :self.nh].zero_()
             self._last[g0:g1].zero_()
             self._peaks[g0:g1].zero_()
-            if self._raw is not None:                     # the raw histories too: the next block starts from silence
-                self._raw[g0:g1, :, :self.H].zero_()
-            if self._gain is not None:                    # carried gains back to one
-                self._a3(self._gain)[:, g0:g1, :self.nh].fill_(1.0)
+            if self._raw_rows is not None:                # the raw histories too: the next block starts from silence
+                self._raw_rows.buf[g0:g1, :, :self.H].zero_()
+            if self._gain_all is not None:                # carried gains back to one
+                self._a3(self._gain_all)[:, g0:g1, :self.nh].fill_(1.0)
                 self._gain_last[g0:g1].fill_(1.0)
 
     def finish(self, sessions, return_peaks=False):
@@ -447,13 +397,13 @@ class StreamBatchRenderer(_BlockStream):
             sig = torch.zeros((n, self.n_src, halo + K), dtype=torch.float32, device=dev)
             sig[:, :, :halo] = self._x3()[:, :, :halo].index_select(1, sel).transpose(0, 1)
             ang = []
-            for k, a in enumerate((self._elev, self._azim)):
+            for k, a in enumerate((self._elev_all, self._azim_all)):
                 end = self._last.index_select(0, sel)[:, k, :, None]                     # [n, n_src, 1]
                 ang.append(torch.cat([self._a3(a)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2))
             gain = None
-            if self._gain is not None:                    # the halo's carried gains, then the end gain twice
+            if self._gain_all is not None:                # the halo's carried gains, then the end gain twice
                 end = self._gain_last.index_select(0, sel)[:, :, None]
-                gain = torch.cat([self._a3(self._gain)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2)
+                gain = torch.cat([self._a3(self._gain_all)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2)
             out, _, _ = render_batch(sig, K, self.S, ang[0], ang[1], self.tbl, normalize="none", gain=gain)
             tails.copy_(out[:, halo:halo + L - 1])
             self._peaks.index_copy_(0, sel, torch.maximum(self._peaks.index_select(0, sel), tails.abs().amax(dim=(1, 2))))

@@ -40,10 +40,10 @@ def test_host_gain_validation():
     t2, buf2 = ah.gain_to_device(ok * 2, (3, 4), dev, buf)
     assert buf2 is buf and np.array_equal(buf.numpy(), ok * 2)
     view = torch.zeros((3, 6), dtype=torch.float64)[:, 1:5]
-    ah.stage_gain(ok, view)
+    bas.stream.stage(ok, view, "gain", ah.check_gain)
     assert np.array_equal(view.numpy(), ok)
     with pytest.raises(ValueError):
-        ah.stage_gain(ok[:, :3], view)
+        bas.stream.stage(ok[:, :3], view, "gain", ah.check_gain)
 
 
 def test_device_call_gains_must_be_contiguous_float64_device_tensors():
