@@ -132,6 +132,15 @@ SIGNATURES = {
                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_int, _c_int,
                                       _c_int, _c_void_p, _c_void_p, _c_void_p, _c_long, _c_long, _c_void_p, _c_long,
                                       _c_long, _c_void_p]),
+    # late reverberation
+    "bas_bus_mix_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_int, _c_long,
+                                 _c_int, _c_void_p, _c_long, _c_void_p]),
+    "bas_long_fir_tail_floats": (_c_size_t, [_c_int, _c_int]),
+    "bas_long_fir_tail_f32": (_c_int, [_c_void_p, _c_long, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "bas_long_fir_workspace_bytes": (_c_size_t, [_c_int, _c_long, _c_int, _c_int]),
+    "bas_long_fir_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p,
+                                  _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_void_p,
+                                  _c_size_t, _c_void_p]),
 }
 
 _lib = None

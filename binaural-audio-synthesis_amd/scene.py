@@ -33,7 +33,7 @@ rigid or nearly rigid walls.
 """
 import numpy as np
 
-from . import _hip, sphere, propagation
+from . import _hip, sphere, propagation, reverb
 
 MAX_ORDER = 3
 SPEED_OF_SOUND = 343.0
@@ -365,7 +365,7 @@ def _table_L(tbl):
 
 
 def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=None, head=None, room=None, src_gain=None,
-                 normalize="mix", interp="cubic", c=SPEED_OF_SOUND, r_ref=1.0, fused=None):
+                 normalize="mix", interp="cubic", c=SPEED_OF_SOUND, r_ref=1.0, fused=None, late=None):
     """Render and mix moving sources given by their positions (render_sources with the geometry done on the device).
 
     signals: [n_src, N] (numpy or tensor); pos: [n_src, n_chunks + 1, 3], the sources' positions in metres at t = 0, K, ..,
@@ -376,7 +376,11 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     0: nothing is replicated); render_angles_device with the gains.  Returns what render_sources returns: a device tensor
     (out_length, 2), peak-normalised ("mix") or not ("none").
     A room with bands adds one step: the delay launch writes a staging buffer, and one bas_color_rows_f32 launch (groups =
-    sources, the n_img filters of room.image_filters(fs) shared by all of them, static) writes the rows the render reads."""
+    sources, the n_img filters of room.image_filters(fs) shared by all of them, static) writes the rows the render reads.
+    late: None, or a reverb.LateTail: the raw source signals, weighted by src_gain, are mixed into one bus
+    (bas_bus_mix_f32), the dry render runs un-normalised, and bas_long_fir_f32 writes dry + bus * tail into a new buffer of
+    in_length + max(L, lag + Lr) - 1 samples, on which the peak rule then runs (bas_peak_normalize_f32).  The chunk size
+    must be a multiple of 32 (reverb.partition: ValueError).  late=None: the launches and the bits of a call without it."""
     import torch
     from .apply_hrtf import as_device_table, padded_rows, render_lengths, render_angles_device
     K, S = int(chunksize), int(subchunksize)
@@ -387,6 +391,7 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     assert sig.dim() == 2, 'signals must be [n_src, N]'
     n_src, n = sig.shape
     n_img = _n_img(room)
+    Np = None if reverb.check_late(late) is None else reverb.partition(K)
     if n_src < 1 or n_src * n_img > 65535:
         raise ValueError("render_scene renders 1..65535 rows (n_src n_img) in one call")
     in_length, _ = render_lengths(n, K, _table_L(tbl))
@@ -411,8 +416,20 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
         if banded:                                                     # every source's images read the one bank
             propagation.color_rows_device(pre[:n_img], room.device_filters(fs, dev), K, x[:n_img], lengths=lens,
                                           groups=(n_src, n_img * pre.stride(0), 0, n_img * x.stride(0)))
-    y, _ = render_angles_device(x, K, S, tbl, el, az, normalize, fused=fused, gain=g)
-    return y.t()
+    if late is None:
+        y, _ = render_angles_device(x, K, S, tbl, el, az, normalize, fused=fused, gain=g)
+        return y.t()
+    y, _ = render_angles_device(x, K, S, tbl, el, az, "none", fused=fused, gain=g)
+    bus = padded_rows(1, n, dev)
+    if n:
+        reverb.bus_mix_device(src, _unit_last(reverb.send_to_device(args[3], n_src, n_q, dev)), K, bus)
+    out = torch.empty((2, in_length + reverb.wet_length(late, tbl.L)), dtype=torch.float32, device=dev)
+    reverb.long_fir_device(bus, late, Np, out, y_in=y)
+    if normalize == "mix":
+        peak = torch.empty((1,), dtype=torch.float32, device=dev)
+        with _hip.on_device(dev):
+            _hip.call("bas_peak_normalize_f32", _hip.ptr(out), out.numel(), _hip.ptr(peak), 1, _hip.current_stream(dev))
+    return out.t()
 
 
 class SceneStreamRenderer:
@@ -420,11 +437,15 @@ class SceneStreamRenderer:
     into the inner renderer's own buffers (one launch in front of the block's graph, where §3.9's head launch sits)."""
 
     def __init__(self, tbl, n_src, chunksize, subchunksize, fs, max_distance, room=None, interp="cubic", c=SPEED_OF_SOUND,
-                 r_ref=1.0, graph=True, copy_out=True):
+                 r_ref=1.0, graph=True, copy_out=True, late=None):
         """n_src sources (each rendered as room.n_img image sources: the inner StreamRenderer has n_src n_img rows);
         max_distance: the largest source-to-listener path in metres, images included (a longer one is heard at
         max_distance's delay: the clamp of §3.11); the stream carries max_distance / c * fs samples of history per row.
-        graph, copy_out: as for StreamRenderer."""
+        graph, copy_out: as for StreamRenderer.
+        late: None, or a reverb.LateTail: behind every block's render (and its graph) one bus-mix launch
+        - the block's raw signals weighted by src_gain - and bas_long_fir_f32, which adds the wet signal to the block's
+        output, then the carry of the bus's history (reverb.LateStream); `peak` is then the running maximum over the sums
+        and finish() returns max(L, lag + Lr) - 1 samples.  The chunk size must be a multiple of 32 (ValueError)."""
         from .stream import StreamRenderer
         self.n_src, self.n_img = int(n_src), _n_img(room)
         if self.n_src < 1:
@@ -440,6 +461,10 @@ class SceneStreamRenderer:
         assert self.K % int(subchunksize) == 0, 'subchunksize does not divide chunksize evenly'
         self._prev = None                                 # the sources' positions one chunk before the next block (device)
         banded = room is not None and room.bands is not None
+        self.copy_out = bool(copy_out)
+        if reverb.check_late(late) is not None:           # (the sums are this class's to hand out: the inner renderer's
+            reverb.partition(self.K)                      # blocks stay views of its own output buffer)
+            copy_out = False
         self.inner = StreamRenderer(tbl, self.n_src * self.n_img, chunksize, subchunksize, graph=graph, copy_out=copy_out,
                                     max_delay=self.max_delay, interp=interp, color_taps=room.taps if banded else None)
         self._bank = None
@@ -447,12 +472,16 @@ class SceneStreamRenderer:
             dev = self.inner.tbl.device                   # the inner renderer's own static colour buffer, passed every block
             self._bank = self.inner.color_view(None, static=True)
             self._bank.view(self.n_src, self.n_img, room.taps).copy_(room.device_filters(fs, dev).unsqueeze(0))
+        self._late = None if late is None else reverb.LateStream(late, 1, self.K, self.inner.tbl.device)
+        self._send_ones = None                            # the static send of a block without src_gain (device, made once)
 
     def prepare(self, B):
         """StreamRenderer.prepare for blocks of B samples, with the gains live (so that the captured graph is the one
         process() replays)."""
         self.inner.gain_view(B)
         self.inner.prepare(B)
+        if self._late is not None:
+            self._late.prepare(B)
 
     def check_block(self, block_shape, pos, listener_pos, head, src_gain):
         """The arguments of process() against a block of `block_shape`, before any device work (ValueError); returns
@@ -481,13 +510,34 @@ class SceneStreamRenderer:
         self._prev = p[:, -2].clone()                     # (the velocity at the next block's first boundary)
         x = st.input_view(B)                                           # [n_src n_img, B]: every image's copy of the block
         x.view(self.n_src, self.n_img, B).copy_(blk.to(dev).unsqueeze(1))   # (one broadcast copy, converts to float32)
-        return st.process(x, el, az, gain=g, delay=d, color=self._bank)
+        dry = st.process(x, el, az, gain=g, delay=d, color=self._bank)
+        if self._late is None:
+            return dry
+        # the bus from the block's raw signals (every source's first image row holds its float32 copy) and src_gain, then
+        # dry + wet: in place in the inner renderer's output view, or into a fresh tensor (copy_out); then the bus's carry
+        if args[3] is None and self._send_ones is None:
+            self._send_ones = torch.ones((self.n_src,), dtype=torch.float64, device=dev)
+        send = self._send_ones if args[3] is None else \
+            _unit_last(reverb.send_to_device(args[3], self.n_src, B // self.K + 1, dev))
+        reverb.bus_mix_device(x.view(self.n_src, self.n_img, B)[:, 0], send, self.K, self._late.bus_block(B))
+        dry = dry.t()
+        out = torch.empty((2, B), dtype=torch.float32, device=dev) if self.copy_out else dry
+        self._late.process(B, out, y_in=dry)
+        return out.t()
 
     def finish(self):
-        """The last L - 1 samples (StreamRenderer.finish)."""
-        return self.inner.finish()
+        """The last L - 1 samples (StreamRenderer.finish); with late, the last max(L, lag + Lr) - 1: the dry tail plus
+        what the bus's history still rings."""
+        dry = self.inner.finish()
+        if self._late is None:
+            return dry
+        import torch
+        n = reverb.wet_length(self._late.tail, self.inner.tbl.L)
+        out = torch.empty((2, n), dtype=torch.float32, device=self.inner.tbl.device)
+        self._late.finish(n, out, y_in=dry.t())
+        return out.t()
 
     @property
     def peak(self):
-        """max |sample| emitted so far."""
-        return self.inner.peak
+        """max |sample| emitted so far (with late: over the sums of dry and wet)."""
+        return self.inner.peak if self._late is None else float(self._late.peak_dev[0])

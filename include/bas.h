@@ -580,6 +580,49 @@ int bas_scene_params_f64(const double *pos, long pos_stride_g, long pos_stride_s
                          int nb, double *elev, double *azim, double *gain, long a_stride_g, long a_stride_s,
                          double *delay, long d_stride_g, long d_stride_s, bas_stream_t stream);
 
+/* ---- late reverberation (no reference counterpart) ---------------------------------------------------
+ * One send bus per group - a weighted mono mix of the group's source rows - through one long static stereo tail, added to
+ * the binaural mix.  All entries: one stream, no allocation, no synchronisation (capturable); every argument check runs
+ * before any launch.
+ *   bas_bus_mix_f32: bus[g][t] = sum_s w_s(t) x_{g,s}(t), t < T, for the rows x + g x_stride_g + s x_stride_s and the
+ *     weights send + g s_stride_g + s s_stride_s + k s_stride_k (float64, one per chunk boundary k <= (T-1)/K + 1):
+ *     for t = kK + j, w_s(t) = g_k + (j / K)(g_{k+1} - g_k), formed in binary64 without contraction (j / K one division)
+ *     and rounded ONCE to binary32; acc = fmaf(w, x, acc) from acc = +0 with s ascending.  s_stride_k == 0 is the static
+ *     form, w = (float)g_0: the bits of the per-boundary form fed repeated weights.  The bits do not depend on tiling.
+ *     Output bus + g bus_stride.  16-byte loads and stores where a row is 16-byte aligned.  One launch.  T < 2^30,
+ *     n_groups <= 65535, strides >= 0, bus_stride >= T with more than one group, K > 0 (BAS_E_SHAPE); x, send, bus
+ *     required (BAS_E_NULL); x, bus 4-byte aligned, send 8-byte (BAS_E_ALIGN).
+ *   bas_long_fir_tail_floats / bas_long_fir_tail_f32: h [2][Lr] (ear e at h + e h_stride) -> `tail`, an opaque array of
+ *     bas_long_fir_tail_floats(Lr, Np) floats (0 for sizes out of range), 16-byte aligned: the twiddle table of the
+ *     transforms of size 2 Np (binary32 roundings of binary64 sincospi values) and the spectra of the P = ceil(Lr / Np)
+ *     partitions [h_p | Np zeros] under a DFT of size 2 Np, bins 0 .. Np.  Once per tail and Np.  One launch.
+ *   bas_long_fir_workspace_bytes / bas_long_fir_f32: r[g][e][n] = sum_{k < Lr} h[e][k] b_g(n - lag - k), n < T_out, by
+ *     uniformly partitioned overlap-save.  Bus g is bus + g bus_stride: samples [-Hb, T_bus) are readable (Hb: a stream's
+ *     carried history, may be 0), everything else reads as zero.  Output frame f covers outputs [f Np, (f + 1) Np); X_f is
+ *     the DFT of size 2 Np of b[(f - 1) Np - lag, (f + 1) Np - lag) (lag only shifts the window: exact, free);
+ *     Y_e[k] = sum_{p < P} X_{f - p}[k] H_{e,p}[k], accumulated by ONE thread per bin from +0 with p ascending, the four
+ *     fused multiply-adds of a complex product in a fixed order; both ears go through one complex inverse transform, whose
+ *     second half is r.  out[g][e][n] = y_in[g][e][n] + r (one binary32 add; y_in is zero at n >= T_y; NULL: zero
+ *     everywhere; out may be y_in with the same strides: in place) at out + g out_stride_g + e out_stride_e + n;
+ *     peak[g] = max(peak[g], max|out|) (float; an atomic max on the bits of non-negative floats, as
+ *     bas_batch_finish_f32 takes it; NULL: not taken).  An output's bits depend on the bus, h, lag and Np only - not on
+ *     T_out or T_bus, not on how frames and bins are dealt to workgroups, not on whether the call is a whole signal or a
+ *     stream block with its history in front.  A zero bus or a zero h adds +0.  Three launches (frame spectra, the sums
+ *     over partitions, inverse + add + peak).  ws: bas_long_fir_workspace_bytes(n_bus, T_out, Lr, Np) bytes, 16-byte
+ *     aligned, uninitialised (BAS_E_WORKSPACE when smaller).  Np in {32, 64, 128, 256, 512}, 1 <= Lr <= 2^17,
+ *     0 <= lag <= 2^20, T_bus, T_out, T_y, Hb < 2^30, n_bus <= 65535, strides >= 0, out_stride_e >= T_out and, with more
+ *     than one bus, out_stride_g >= out_stride_e + T_out (BAS_E_SHAPE); tail, out, ws and (with anything to read) bus
+ *     required (BAS_E_NULL); bus, y_in, out, peak 4-byte aligned, tail and ws 16-byte (BAS_E_ALIGN). */
+int bas_bus_mix_f32(const float *x, long x_stride_g, long x_stride_s, const double *send, long s_stride_g,
+                    long s_stride_s, long s_stride_k, int n_groups, int n_src, long T, int K, float *bus, long bus_stride,
+                    bas_stream_t stream);
+size_t bas_long_fir_tail_floats(int Lr, int Np);
+int bas_long_fir_tail_f32(const float *h, long h_stride, int Lr, int Np, float *tail, bas_stream_t stream);
+size_t bas_long_fir_workspace_bytes(int n_bus, long T_out, int Lr, int Np);
+int bas_long_fir_f32(const float *bus, long bus_stride, long Hb, long T_bus, int n_bus, const float *tail, int Lr, int Np,
+                     int lag, const float *y_in, long y_stride_g, long y_stride_e, long T_y, float *out, long out_stride_g,
+                     long out_stride_e, long T_out, float *peak, void *ws, size_t ws_bytes, bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's
