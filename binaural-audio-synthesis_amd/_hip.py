@@ -141,6 +141,11 @@ SIGNATURES = {
     "bas_long_fir_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p,
                                   _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_void_p,
                                   _c_size_t, _c_void_p]),
+    # look-ahead limiter
+    "bas_limit_state_floats": (_c_size_t, [_c_int, _c_int]),
+    "bas_limit_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_long,
+                               _c_long, ctypes.c_double, _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p,
+                               _c_void_p]),
 }
 
 _lib = None

@@ -623,6 +623,51 @@ int bas_long_fir_f32(const float *bus, long bus_stride, long Hb, long T_bus, int
                      int lag, const float *y_in, long y_stride_g, long y_stride_e, long T_y, float *out, long out_stride_g,
                      long out_stride_e, long T_out, float *peak, void *ws, size_t ws_bytes, bas_stream_t stream);
 
+/* ---- look-ahead limiter -----------------------------------------------------------------------------
+ * The reference ends a render with its peak rule (apply_hrtf.py:462-464: if max|y| > 1, divide the whole signal by it).  A
+ * stream cannot apply that rule - the maximum is known when the stream is over - so the streamed paths hand out raw sums.
+ * This stage makes them safe to play: a peak limiter with look-ahead, ONE gain for both ears (the interaural level
+ * difference is kept), no recursion.  For a ceiling c > 0 (a normal binary32 value, carried in a double), a look-ahead of
+ * A samples and a hold of Hd samples, with zeros before the start and after the end of a signal:
+ *   1. m[n] = max(|yL[n]|, |yR[n]|);
+ *   2. r[n] = m[n] > c ? c / m[n] : 1                          (one binary32 division);
+ *   3. e[k] = min r[j] over j in [k - Hd, k + A]               (exact);
+ *   4. s[n] = (e[n - A] + ... + e[n]) / (A + 1): binary64 adds from +0 with k ascending, one binary64 division, rounded
+ *      ONCE to binary32;
+ *   5. g[n] = min(s[n], r[n]);
+ *   6. out[n] = min(max(y[n] g[n], -c), c) per ear             (one binary32 multiplication; the sign is kept).
+ * The gain falls linearly over the A samples before a peak, meets the required gain at the peak, stays for Hd samples and
+ * returns linearly over A samples; |out| <= c always; a signal whose peak is at most c keeps its bits.  Inputs must be
+ * finite; the bits are specified for |y| <= 2^20 c (no r subnormal).
+ *   y at y + g y_stride_g + t y_stride_t + e y_stride_e, out likewise: any strides >= 0 (the stream renderers' [B, 2]
+ *   views of planar buffers, interleaved frames); the output's strides must address every element once, and input, output
+ *   and state must not overlap (BAS_E_SHAPE: the limiter does not run in place).
+ *   state == NULL: a whole signal.  T_in == T_out; out[n] belongs to y[n].
+ *   state != NULL: a block of a stream.  state + g state_stride holds bas_limit_state_floats(A, Hd) floats per session
+ *     (0 for parameters out of range), zeroed before a stream's first block: two ring positions and the session's last
+ *     2 A + Hd input samples - samples only, r is recomputed.  out[j] is the limited sample of time t0 + j - A for a block
+ *     that starts at t0: the stream is delayed by A samples and begins with A zeros.  T_in == T_out: a block, whose last
+ *     min(T_in, 2 A + Hd) samples then go into the ring - by the session's own workgroup where the block is one tile (1024
+ *     samples) or less, by a second launch where it is longer.  T_in == 0: the stream's end - T_out (usually A) more
+ *     samples with zeros behind the history; the state is left as it is, y is not read.
+ *     Any block length >= 1.  An output's bits depend on the samples at times [n - A - Hd, n + A] alone: not on the block
+ *     boundaries, not on how samples are dealt to workgroups.
+ *   reduction[g] = min(reduction[g], min g) over the outputs written (the gain-reduction meter; set to 1 by the caller
+ *   before a stream), peak[g] = max(peak[g], max|out|): atomics on the bits of positive floats, sent only when they would
+ *   change the value; each may be NULL.
+ * One stream, no allocation, no synchronisation (capturable); one launch, two for a stream block of more than 1024 samples.
+ * Every argument check runs before any launch: 0 <= lookahead <= 1024, 0 <= hold <= 4096, ceiling a normal binary32 value
+ * > 0, n_sessions <= 65535, T_in, T_out < 2^30, strides >= 0, state_stride a multiple of 4 and >= the state's size
+ * (BAS_E_SHAPE); out, and y with T_in > 0, required (BAS_E_NULL); y, out, reduction, peak 4-byte aligned, state 16-byte
+ * (BAS_E_ALIGN). */
+#define BAS_LIMIT_MAX_LOOKAHEAD 1024
+#define BAS_LIMIT_MAX_HOLD 4096
+size_t bas_limit_state_floats(int lookahead, int hold);
+int bas_limit_f32(const float *y, long y_stride_g, long y_stride_t, long y_stride_e, float *out, long out_stride_g,
+                  long out_stride_t, long out_stride_e, int n_sessions, long T_in, long T_out, double ceiling,
+                  int lookahead, int hold, float *state, long state_stride, float *reduction, float *peak,
+                  bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's
