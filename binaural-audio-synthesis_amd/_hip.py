@@ -146,6 +146,11 @@ SIGNATURES = {
     "bas_limit_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_long,
                                _c_long, ctypes.c_double, _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p,
                                _c_void_p]),
+    # ambisonic beds
+    "bas_ambi_matrices_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int,
+                                       _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),
+    "bas_matrix_mix_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_int, _c_int, _c_int, _c_long,
+                                    _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),
 }
 
 _lib = None

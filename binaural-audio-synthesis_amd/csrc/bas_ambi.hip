@@ -1,0 +1,261 @@
+// Ambisonic beds (include/bas.h "ambisonic beds"):
+//   bas_ambi_matrices_f32 - head orientations at chunk boundaries -> mixing matrices M = D Rot(q), one launch;
+//   bas_matrix_mix_f32    - the hot path: y_v(t) = sum_c M(t)[v][c] x_c(t) with M interpolated between chunk boundaries,
+//                           strided rows in and out (a renderer's input rows are written in place), one launch.
+#include "bas_internal.h"
+#include "bas_ambi.h"
+
+// One workgroup per (group, boundary); Q is staged in LDS.  Thread j < J evaluates Y at R^T s_j into LDS; the 84 (order 3)
+// entries of the order blocks of Rot are sums over j ascending from +0; the V C entries of M are sums over b ascending over c's order block.  All
+// binary64 without contraction, one rounding to binary32.  The identity (bas_ambi_unit_head) stores (float)D.
+__global__ __launch_bounds__(AMBI_THREADS) void bas_ambi_matrices_kernel(
+    const double *__restrict__ head, long hs_g, long hs_c, const double *__restrict__ D, const double *__restrict__ Q,
+    const double *__restrict__ S, int J, int order, int V, int nb, float *__restrict__ m, long ms_g, long ms_k) {
+#pragma clang fp contract(off)
+    __shared__ double Ys[AMBI_MAX_J][AMBI_MAX_C + 1];
+    __shared__ double Rot[AMBI_MAX_C][AMBI_MAX_C];
+    __shared__ double Qs[AMBI_MAX_J * AMBI_MAX_C];
+    const int C = (order + 1) * (order + 1);
+    const long gk = blockIdx.x;
+    const long g = gk / nb, k = gk - g * nb;
+    const double *q = head + g * hs_g + k * hs_c;
+    float *out = m + g * ms_g + k * ms_k;
+    double w = q[0], x = q[1], y = q[2], z = q[3];
+    if (bas_ambi_unit_head(w, x, y, z)) {
+        for (int i = threadIdx.x; i < V * C; i += AMBI_THREADS) out[i] = (float)D[i];
+        return;
+    }
+    for (int i = threadIdx.x; i < J * C; i += AMBI_THREADS) Qs[i] = Q[i];
+    if ((int)threadIdx.x < J) {
+        const int j = threadIdx.x;
+        double hx, hy, hz, Y[AMBI_MAX_C];
+        bas_ambi_rotate_t(w, x, y, z, S[3 * j], S[3 * j + 1], S[3 * j + 2], hx, hy, hz);
+        bas_sh_n3d(hx, hy, hz, order, Y);
+#pragma unroll
+        for (int a = 0; a < AMBI_MAX_C; ++a)
+            if (a < C) Ys[j][a] = Y[a];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < C * C; i += AMBI_THREADS) {
+        const int a = i / C, b = i - a * C;
+        const int la = a >= 9 ? 3 : a >= 4 ? 2 : a >= 1 ? 1 : 0, lb = b >= 9 ? 3 : b >= 4 ? 2 : b >= 1 ? 1 : 0;
+        double acc = 0.0;
+        if (la == lb)
+            for (int j = 0; j < J; ++j) acc = acc + Ys[j][a] * Qs[j * C + b];
+        Rot[a][b] = acc;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < V * C; i += AMBI_THREADS) {
+        const int v = i / C, c = i - v * C;
+        const int l = c >= 9 ? 3 : c >= 4 ? 2 : c >= 1 ? 1 : 0;
+        double acc = 0.0;
+        for (int b = l * l; b < (l + 1) * (l + 1); ++b) acc = acc + D[v * C + b] * Rot[b][c];
+        out[i] = (float)acc;
+    }
+}
+
+// One workgroup per (tile, group, slice of speaker rows): blockIdx.y is the group, blockIdx.x strides over the tiles,
+// blockIdx.z takes the rows [z v_per, (z + 1) v_per) - one slice for long signals, where the inputs are then read once, more
+// where tiles and groups alone would leave most of the chip idle (a stream block).  LDS holds the slice's rows of the matrices
+// of the boundaries the tile touches, each row padded with zeros to CP = C rounded up to 4 columns (a zero column adds an exact
+// zero to a sum that is never -0).  A lane makes outputs t .. t + 3: it holds the C x 4 inputs in registers and walks the
+// V rows, per row one quad of each matrix per four columns - the same address for every lane of a chunk, a broadcast -
+// and 4 C (STATIC) or 8 C fused multiply-adds, c ascending, then one 16-byte store.  Lanes whose four outputs straddle a chunk
+// boundary (K not a multiple of 4) do theirs one by one, the same operations in the same order.  Nothing depends on t0: an
+// output's bits are a function of (j, K, M_k, M_{k+1}) and its C inputs alone.
+template <int CP, bool STATIC>
+__global__ __launch_bounds__(MM_THREADS) void bas_matrix_mix_kernel(
+    const float *__restrict__ x, long xs_g, long xs_c, const float *__restrict__ m, long ms_g, long ms_k, int C, int V, int T,
+    int K, int tile, int v_per, float *__restrict__ y, long ys_g, long ys_v) {
+    __shared__ __attribute__((aligned(16))) float ms[MM_LDS_FLOATS];
+    const int g = blockIdx.y;
+    const int v0 = blockIdx.z * v_per, v1 = min(v0 + v_per, V);      // the slice's rows
+    const float *xg = x + g * xs_g;
+    const float *mg = m + g * ms_g;
+    float *yg = y + g * ys_g;
+    const int set_floats = (v1 - v0) * CP;
+    const float inv_K = 1.0f / (float)K;
+    const int n_tiles = (T + tile - 1) / tile;
+    for (int it = blockIdx.x; it < n_tiles; it += gridDim.x) {
+        const int t0 = it * tile;
+        const int t1 = min(t0 + tile, T);                                // the tile's outputs are [t0, t1)
+        // ---- matrices: the boundaries k0 .. k1 + 1 (STATIC: the one matrix)
+        const int k0 = t0 / K;
+        const int n_sets = STATIC ? 1 : (t1 - 1) / K - k0 + 2;
+        for (int i = threadIdx.x; i < n_sets * set_floats; i += MM_THREADS) {
+            const int set = i / set_floats, r = i - set * set_floats;
+            const int v = r / CP, c = r - v * CP;
+            ms[i] = c < C ? mg[(long)(k0 + set) * ms_k + (v0 + v) * C + c] : 0.f;
+        }
+        __syncthreads();
+        const int tl = t0 + (threadIdx.x << 2);
+        if (tl < t1) {
+            // ---- inputs: C rows of four samples, zeros past T and in the padding columns
+            float xr[CP][4];
+#pragma unroll
+            for (int c = 0; c < CP; ++c) {
+                xr[c][0] = xr[c][1] = xr[c][2] = xr[c][3] = 0.f;
+                if (c < C) {
+                    const float *row = xg + c * xs_c;
+                    if ((reinterpret_cast<uintptr_t>(row) & 15) == 0 && tl + 3 < T) {
+                        const f32x4 q = *reinterpret_cast<const f32x4 *>(row + tl);
+                        xr[c][0] = q.x; xr[c][1] = q.y; xr[c][2] = q.z; xr[c][3] = q.w;
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (tl + i < T) xr[c][i] = row[tl + i];
+                    }
+                }
+            }
+            const int k = tl / K, j = tl - k * K;
+            const bool one_chunk = STATIC || j + 3 < K;                   // the lane's four outputs share a chunk
+            for (int v = 0; v < v1 - v0; ++v) {
+                float o[4];
+                if (one_chunk) {
+                    const f32x4 *ma = reinterpret_cast<const f32x4 *>(ms + (STATIC ? 0 : (k - k0) * set_floats) + v * CP);
+                    const f32x4 *mb = reinterpret_cast<const f32x4 *>(ms + (STATIC ? 0 : (k - k0 + 1) * set_floats) + v * CP);
+                    float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int cq = 0; cq < CP / 4; ++cq) {
+                        const f32x4 qa = ma[cq];
+                        const float ta[4] = {qa.x, qa.y, qa.z, qa.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) a[i] = fmaf(ta[e], xr[4 * cq + e][i], a[i]);
+                        if (!STATIC) {
+                            const f32x4 qb = mb[cq];
+                            const float tb[4] = {qb.x, qb.y, qb.z, qb.w};
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) b[i] = fmaf(tb[e], xr[4 * cq + e][i], b[i]);
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        o[i] = STATIC ? a[i] : fmaf((float)(j + i) * inv_K, b[i] - a[i], a[i]);
+                } else {                                                  // a chunk boundary inside the quad: one by one
+                    int ki = k, ji = j;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int last = tl + i < t1 ? ki : k;            // (past the tile's end: any matrix the tile holds)
+                        const float *ma = ms + (last - k0) * set_floats + v * CP;
+                        const float *mb = ma + set_floats;
+                        float a = 0.f, b = 0.f;
+#pragma unroll
+                        for (int c = 0; c < CP; ++c) {
+                            a = fmaf(ma[c], xr[c][i], a);
+                            b = fmaf(mb[c], xr[c][i], b);
+                        }
+                        o[i] = fmaf((float)ji * inv_K, b - a, a);
+                        if (++ji == K) { ji = 0; ++ki; }
+                    }
+                }
+                float *out = yg + (v0 + v) * ys_v;
+                if ((reinterpret_cast<uintptr_t>(out) & 15) == 0 && tl + 3 < T) {
+                    f32x4 q;
+                    q.x = o[0]; q.y = o[1]; q.z = o[2]; q.w = o[3];
+                    *reinterpret_cast<f32x4 *>(out + tl) = q;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (tl + i < T) out[tl + i] = o[i];
+                }
+            }
+        }
+        __syncthreads();                                                  // (the next tile overwrites ms)
+    }
+}
+
+static inline bool ambi_ranges_meet(const void *a, long na, const void *b, long nb, int bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + (uintptr_t)nb * bytes && b0 < a0 + (uintptr_t)na * bytes;
+}
+
+extern "C" int bas_ambi_matrices_f32(const double *head, long hs_g, long hs_c, const double *D, const double *Q,
+                                     const double *S, int J, int order, int V, int n_groups, int nb, float *m, long ms_g,
+                                     long ms_k, bas_stream_t stream) {
+    BAS_REQUIRE(order >= 1 && order <= AMBI_MAX_ORDER, BAS_E_SHAPE, "bas_ambi_matrices_f32: order (%d) must be in 1..%d",
+                order, AMBI_MAX_ORDER);
+    BAS_REQUIRE(V >= 1 && V <= AMBI_MAX_V, BAS_E_SHAPE, "bas_ambi_matrices_f32: V (%d) must be in 1..%d", V, AMBI_MAX_V);
+    BAS_REQUIRE(J >= 1 && J <= AMBI_MAX_J, BAS_E_SHAPE, "bas_ambi_matrices_f32: J (%d) must be in 1..%d", J, AMBI_MAX_J);
+    BAS_REQUIRE(n_groups >= 0 && nb >= 0 && (long)n_groups * nb <= (1L << 30), BAS_E_SHAPE,
+                "bas_ambi_matrices_f32: need n_groups, nb >= 0 and n_groups nb <= 2^30");
+    BAS_REQUIRE(hs_g >= 0 && hs_c >= 4 && ms_g >= 0 && ms_k >= 0, BAS_E_SHAPE,
+                "bas_ambi_matrices_f32: strides must be >= 0 and hs_c >= 4");
+    if ((long)n_groups * nb == 0) return 0;
+    const int C = (order + 1) * (order + 1);
+    BAS_REQUIRE(bas_layout_one_to_one(n_groups, nb, (long)V * C, ms_g, ms_k), BAS_E_SHAPE,
+                "bas_ambi_matrices_f32: the output's strides address an element twice");
+    BAS_REQUIRE(head && D && Q && S && m, BAS_E_NULL, "bas_ambi_matrices_f32: null pointer");
+    BAS_REQUIRE((reinterpret_cast<uintptr_t>(head) & 7) == 0 && (reinterpret_cast<uintptr_t>(D) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(Q) & 7) == 0 && (reinterpret_cast<uintptr_t>(S) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(m) & 3) == 0,
+                BAS_E_ALIGN, "bas_ambi_matrices_f32: head, D, Q, S must be 8-byte aligned, m 4-byte");
+    hipLaunchKernelGGL(bas_ambi_matrices_kernel, dim3((unsigned)((long)n_groups * nb)), dim3(AMBI_THREADS), 0,
+                       bas_stream(stream), head, hs_g, hs_c, D, Q, S, J, order, V, nb, m, ms_g, ms_k);
+    return bas_check_launch("bas_ambi_matrices_f32");
+}
+
+template <int CP>
+static void ambi_launch_mix(bool is_static, dim3 grid, hipStream_t st, const float *x, long xs_g, long xs_c, const float *m,
+                            long ms_g, long ms_k, int C, int V, int T, int K, int tile, int v_per, float *y, long ys_g,
+                            long ys_v) {
+    if (is_static)
+        hipLaunchKernelGGL((bas_matrix_mix_kernel<CP, true>), grid, dim3(MM_THREADS), 0, st, x, xs_g, xs_c, m, ms_g, ms_k, C,
+                           V, T, K, tile, v_per, y, ys_g, ys_v);
+    else
+        hipLaunchKernelGGL((bas_matrix_mix_kernel<CP, false>), grid, dim3(MM_THREADS), 0, st, x, xs_g, xs_c, m, ms_g, ms_k, C,
+                           V, T, K, tile, v_per, y, ys_g, ys_v);
+}
+
+extern "C" int bas_matrix_mix_f32(const float *x, long xs_g, long xs_c, const float *m, long ms_g, long ms_k, int C, int V,
+                                  int n_groups, long T, int K, float *y, long ys_g, long ys_v, bas_stream_t stream) {
+    BAS_REQUIRE(C >= 1 && C <= AMBI_MAX_C, BAS_E_SHAPE, "bas_matrix_mix_f32: C (%d) must be in 1..%d", C, AMBI_MAX_C);
+    BAS_REQUIRE(V >= 1 && V <= AMBI_MAX_V, BAS_E_SHAPE, "bas_matrix_mix_f32: V (%d) must be in 1..%d", V, AMBI_MAX_V);
+    BAS_REQUIRE(n_groups >= 0 && n_groups <= 65535 && T >= 0 && K > 0, BAS_E_SHAPE,
+                "bas_matrix_mix_f32: need 0 <= n_groups <= 65535, T >= 0 and K > 0");
+    BAS_REQUIRE(T < (1L << 30), BAS_E_SHAPE, "bas_matrix_mix_f32: T (%ld) must be below 2^30", T);
+    BAS_REQUIRE(xs_g >= 0 && xs_c >= 0 && ms_g >= 0 && ms_k >= 0 && ys_g >= 0 && ys_v >= 0, BAS_E_SHAPE,
+                "bas_matrix_mix_f32: strides must be >= 0");
+    BAS_REQUIRE(xs_g < (1L << 40) && xs_c < (1L << 40) && ms_g < (1L << 40) && ms_k < (1L << 40) && ys_g < (1L << 40) &&
+                    ys_v < (1L << 40),
+                BAS_E_SHAPE, "bas_matrix_mix_f32: strides must be below 2^40");
+    BAS_REQUIRE(ms_k == 0 || ms_k >= (long)V * C, BAS_E_SHAPE,
+                "bas_matrix_mix_f32: ms_k must be 0 (static) or >= V C (the matrices of two boundaries overlap)");
+    if (n_groups == 0 || T == 0) return 0;
+    BAS_REQUIRE(bas_layout_one_to_one(n_groups, V, T, ys_g, ys_v), BAS_E_SHAPE,
+                "bas_matrix_mix_f32: the output's strides address an element twice");
+    BAS_REQUIRE(x && m && y, BAS_E_NULL, "bas_matrix_mix_f32: null pointer");
+    BAS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 3) == 0 &&
+                    (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+                BAS_E_ALIGN, "bas_matrix_mix_f32: x, m, y must be 4-byte aligned");
+    const long x_n = (n_groups - 1) * xs_g + (C - 1) * xs_c + T, y_n = (n_groups - 1) * ys_g + (V - 1) * ys_v + T;
+    BAS_REQUIRE(!ambi_ranges_meet(x, x_n, y, y_n, 4), BAS_E_SHAPE,
+                "bas_matrix_mix_f32: input and output overlap (the mix does not run in place)");
+    const long n_k = ms_k == 0 ? 1 : (T - 1) / K + 2;
+    const long m_n = (n_groups - 1) * ms_g + (n_k - 1) * ms_k + (long)V * C;
+    BAS_REQUIRE(!ambi_ranges_meet(m, m_n, y, y_n, 4), BAS_E_SHAPE, "bas_matrix_mix_f32: matrices and output overlap");
+    // a tile touches (tile - 1) / K + 3 boundaries at most, and LDS holds MM_LDS_FLOATS / (V CP) matrices (>= 8): whole
+    // tiles where the chunks are long enough, shorter ones (a multiple of 4 samples) below
+    const int CP = (C + 3) & ~3;
+    const long fit = ((long)(MM_LDS_FLOATS / (V * CP)) - 2) * K;
+    const int tile = fit >= MM_TILE ? MM_TILE : (int)(fit & ~3L);
+    const long n_tiles = (T + tile - 1) / tile;
+    // slices of speaker rows where tiles x groups are fewer workgroups than the chip has CUs: MM_FILL workgroups then (every
+    // slice reads the inputs again, which a long signal must not: it is bound by those bytes)
+    const long n_wg = (n_tiles < 65535 ? n_tiles : 65535) * n_groups;
+    const long want = 2 * n_wg >= MM_FILL ? 1 : (MM_FILL + n_wg - 1) / n_wg;
+    const int v_per = (int)((V + want - 1) / want) > 0 ? (int)((V + want - 1) / want) : 1;
+    const dim3 grid((unsigned)(n_tiles < 65535 ? n_tiles : 65535), (unsigned)n_groups, (unsigned)((V + v_per - 1) / v_per));
+    const hipStream_t st = bas_stream(stream);
+    const bool is_static = ms_k == 0;
+    switch (CP) {
+    case 4: ambi_launch_mix<4>(is_static, grid, st, x, xs_g, xs_c, m, ms_g, ms_k, C, V, (int)T, K, tile, v_per, y, ys_g, ys_v); break;
+    case 8: ambi_launch_mix<8>(is_static, grid, st, x, xs_g, xs_c, m, ms_g, ms_k, C, V, (int)T, K, tile, v_per, y, ys_g, ys_v); break;
+    case 12: ambi_launch_mix<12>(is_static, grid, st, x, xs_g, xs_c, m, ms_g, ms_k, C, V, (int)T, K, tile, v_per, y, ys_g, ys_v); break;
+    default: ambi_launch_mix<16>(is_static, grid, st, x, xs_g, xs_c, m, ms_g, ms_k, C, V, (int)T, K, tile, v_per, y, ys_g, ys_v); break;
+    }
+    return bas_check_launch("bas_matrix_mix_f32");
+}

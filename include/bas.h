@@ -668,6 +668,49 @@ int bas_limit_f32(const float *y, long y_stride_g, long y_stride_t, long y_strid
                   int lookahead, int hold, float *state, long state_stride, float *reduction, float *peak,
                   bas_stream_t stream);
 
+/* ---- ambisonic beds (no reference counterpart) --------------------------------------------------------
+ * A bed is a sound field in real spherical harmonics: orders N = 1..3, C = (N + 1)^2 channels in ACN order, N3D inside
+ * ((1 / 4 pi) int Y_a Y_b = delta_ab; no Condon-Shortley phase; SN3D input is a diagonal folded into the decoder by the
+ * host).  In the frame of "head tracking" (d = (-sin az cos el, cos az cos el, sin el)) and (x, y, z) = (d_y, -d_x, d_z):
+ *   Y_0 = 1;  Y_1..3 = r3 y, r3 z, r3 x;  Y_4..8 = r15 xy, r15 yz, (r5/2)(3 z^2 - 1), r15 xz, (r15/2)(x^2 - y^2);
+ *   Y_9..15 = r(35/8) y (3 x^2 - y^2), r105 xyz, r(21/8) y (5 z^2 - 1), (r7/2) z (5 z^2 - 3), r(21/8) x (5 z^2 - 1),
+ *   (r105/2) z (x^2 - y^2), r(35/8) x (x^2 - 3 y^2)        (r: the correctly rounded binary64 square root).
+ * The bed is decoded to V <= 64 virtual loudspeakers fixed to the head; the FIELD is turned by the head orientation:
+ * feeds = M bed with M = D Rot(q), D [V][C] the static decoder and Rot the C x C matrix, block diagonal per order, with
+ * Y(R(q)^T s) = Rot Y(s) for every direction s (R(q): the matrix of "head tracking").  The feeds are V more source rows of a
+ * render.  Both entries: one stream, no allocation, no synchronisation (capturable), one launch; every argument check runs
+ * before the launch; all strides in elements, >= 0.
+ *   bas_ambi_matrices_f32: head [n_groups][nb][4] (float64 (w, x, y, z) at head + g hs_g + k hs_c, hs_c >= 4) -> M
+ *     (float32 at m + g ms_g + k ms_k + v C + c).  Rot is defined by sample points: S [J][3] unit vectors and Q [J][C]
+ *     whose columns of order l are pinv(Y_l(S)^T) (the host makes both once; J <= 64);
+ *       q is negated when w < 0; x == y == z == 0 after that (a zero quaternion included) is the identity: M = (float)D,
+ *         exactly; otherwise q is normalised and h_j = R(q)^T s_j by the expressions of "head tracking";
+ *       Rot[a][b] = sum_{j < J} Y_a(h_j) Q[j][b] for a, b of the same order, from +0 with j ascending, 0 elsewhere;
+ *       M[v][c] = sum_b D[v][b] Rot[b][c], from +0 with b ascending over c's order block;
+ *     all in binary64 without contraction, rounded to binary32 once.  Nothing is validated on the device (a non-finite
+ *     head gives non-finite matrices).  order in 1..3, V in 1..64, J in 1..64, n_groups nb <= 2^30, hs_c >= 4, and the
+ *     output's strides must address every element once (BAS_E_SHAPE); all pointers required (BAS_E_NULL); float64
+ *     pointers 8-byte aligned, m 4-byte (BAS_E_ALIGN).
+ *   bas_matrix_mix_f32: the hot path.  Input rows x + g xs_g + c xs_c (C <= 16 rows of T samples), matrices
+ *     m + g ms_g + k ms_k + v C + c for the (T - 1) / K + 2 chunk boundaries, output rows y + g ys_g + v ys_v (V <= 64).
+ *     For t = k K + j:  A = fmaf(M_k[v][c], x_c(t), A) from +0 with c ascending, B likewise with M_{k+1},
+ *     w = (float)j * (1.0f / (float)K),  y_v(t) = fmaf(w, B - A, A) - the form of bas_color_rows_f32: an output's bits
+ *     depend on (j, K, M_k, M_{k+1}) and the C inputs at t alone, not on tiles, block boundaries or alignment.
+ *     ms_k == 0 is the static form, y = A (B skipped): the bits of the per-boundary form fed repeated matrices.
+ *     ms_g == 0 shares one matrix bank, xs_g == 0 one bed over all groups.  16-byte loads and stores where a row is
+ *     16-byte aligned, 4-byte ones elsewhere.  C in 1..16, V in 1..64, T < 2^30, n_groups <= 65535, K > 0, ms_k == 0 or
+ *     >= V C, the output's strides must address every element once, and the output must overlap neither x nor the
+ *     matrices (BAS_E_SHAPE); x, m, y required (BAS_E_NULL) and 4-byte aligned (BAS_E_ALIGN). */
+#define BAS_AMBI_MAX_ORDER 3
+#define BAS_AMBI_MAX_CHANNELS 16
+#define BAS_AMBI_MAX_SPEAKERS 64
+#define BAS_AMBI_MAX_POINTS 64
+int bas_ambi_matrices_f32(const double *head, long hs_g, long hs_c, const double *D, const double *Q, const double *S,
+                          int J, int order, int V, int n_groups, int nb, float *m, long ms_g, long ms_k,
+                          bas_stream_t stream);
+int bas_matrix_mix_f32(const float *x, long xs_g, long xs_c, const float *m, long ms_g, long ms_k, int C, int V,
+                       int n_groups, long T, int K, float *y, long ys_g, long ys_v, bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's
