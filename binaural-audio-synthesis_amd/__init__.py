@@ -11,7 +11,7 @@ from .stream_batch import StreamBatchRenderer  # noqa: F401
 from .scene import render_scene, SceneStreamRenderer  # noqa: F401
 from .reverb import LateTail, late_tail  # noqa: F401
 from .limiter import limit, StreamLimiter  # noqa: F401
-from .ambisonics import render_bed, BedStream  # noqa: F401
+from .ambisonics import render_bed, BedStream, encode_bed, BedEncoder  # noqa: F401
 from .apply_hrtf import (  # noqa: F401
     load_irs_and_delaydiffs, irs_and_delaydiffs, interpolate_2d, interpolate_2d_deg, interpolate_2d_batch,
     interpolate_2d_params, make_signal_move_2d, render_sources, delay_signal_float,

@@ -151,6 +151,11 @@ SIGNATURES = {
                                        _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),
     "bas_matrix_mix_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_int, _c_int, _c_int, _c_long,
                                     _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),
+    # ambisonic encoder
+    "bas_ambi_encode_gains_f32": (_c_int, [_c_void_p, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_void_p,
+                                           _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),
+    "bas_ambi_encode_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_int, _c_int, _c_int,
+                                     _c_long, _c_int, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_void_p]),
 }
 
 _lib = None

@@ -7,6 +7,10 @@ points of csrc/bas_ambi.hip (bas_ambi_matrices_f32: head -> mixing matrices; bas
 path), bed_sources / render_bed are the offline forms and BedStream puts a bed beside the objects of a StreamRenderer or a
 StreamBatchRenderer through the views those publish.
 
+The stage in front is the encoder: encoding_gains and encode are its float64 definition,
+encoding_gains_device and encode_device wrap bas_ambi_encode_gains_f32 and bas_ambi_encode_f32 (the hot path: many source
+rows summed into one bed), encode_bed is the offline form and BedEncoder the stream stage that fills a BedStream's bed.
+
 Conventions.  Orders 1..3 (4, 9, 16 channels), ACN channel order, real spherical harmonics without the Condon-Shortley
 phase (ambiX).  Inside, everything is N3D: (1 / 4 pi) int Y_a Y_b = delta_ab; SN3D input is taken by folding
 diag(sqrt(2 l + 1)) into the decoder.  Directions are the project's (bas_head.h): d = (-sin az cos el, cos az cos el,
@@ -249,6 +253,111 @@ def decode(bed, K, M):
         Mt = M[k] + w[:, None, None] * (M[k + 1] - M[k])                    # every sample's own matrix [n, V, C]
         out[:, t] = np.einsum("nvc,cn->vn", Mt, bed[:, t])
     return out
+
+
+# ---- the encoder: the definition ----------------------------------------------------------------------
+ENCODE_BLOCK = 32                                  # BAS_AMBI_ENCODE_BLOCK: sources of one first-level chain of the device sum
+ENCODE_MAX_SOURCES = 65536                         # BAS_AMBI_ENCODE_MAX_SOURCES
+ENCODE_TILE = 1024                                 # ENC_TILE of csrc/bas_ambi.h
+ENCODE_FILL = 512                                  # ENC_FILL
+ENCODE_LDS_FLOATS = 8192                           # ENC_LDS_FLOATS
+ENCODE_MAX_SLAB = 512                              # ENC_MAX_SLAB
+ENCODE_STATIC_SLICE, ENCODE_BOUNDARY_SLICE = 16, 8  # ENC_STATIC_SLICE, ENC_BOUNDARY_SLICE
+
+
+def encode_plan(C, K, T, static=False, n_groups=1):
+    """(channels per workgroup, tile, slab) of one bas_ambi_encode_f32 launch - the launcher's rule.  A lane accumulates a
+    slice of at most 16 (static) or 8 (per-boundary) channels; a per-boundary launch of more than 8 channels gives a
+    workgroup two slices of 8 and a tile of ENCODE_TILE / 2 (its halves share the tile's signals); where tiles x slices
+    x groups would be fewer than ENCODE_FILL / 2 workgroups, the slices are of 4 channels.  The tile is the largest where
+    one block of sources of the (tile - 1) / K + 3 boundaries a tile can touch fits LDS, a shorter multiple of 4 where the
+    chunks are short; the slab is the multiple of ENCODE_BLOCK sources whose banks fill LDS, ENCODE_MAX_SLAB at most."""
+    C, K, T, G = int(C), int(K), int(T), int(n_groups)
+    CP, cap = (C + 3) & ~3, ENCODE_STATIC_SLICE if static else ENCODE_BOUNDARY_SLICE
+    s, split = min(CP, cap), 2 if CP > cap else 1
+    for last in (False, True):
+        cw, tile_max = s * split, ENCODE_TILE // split
+        fit = tile_max if static else (ENCODE_LDS_FLOATS // (ENCODE_BLOCK * cw) - 2) * K
+        tile = tile_max if fit >= tile_max else fit & ~3
+        n_wg = -(-T // tile) * -(-C // cw) * G
+        if last or (s == 4 and split == 1) or 2 * n_wg >= ENCODE_FILL:
+            break
+        s, split = 4, 1
+    n_sets = 1 if static else (tile - 1) // K + 3
+    return s * split, tile, min(ENCODE_MAX_SLAB, (ENCODE_LDS_FLOATS // (n_sets * s * split)) & ~(ENCODE_BLOCK - 1))
+
+
+def encode_tile(C, K, T, static=False, n_groups=1):
+    """The outputs of one workgroup pass of bas_ambi_encode_f32 (encode_plan)."""
+    return encode_plan(C, K, T, static, n_groups)[1]
+
+
+def encode_slab(C, K, T, static=False, n_groups=1):
+    """The sources whose banks one LDS stage of bas_ambi_encode_f32 holds (encode_plan): a multiple of ENCODE_BLOCK."""
+    return encode_plan(C, K, T, static, n_groups)[2]
+
+
+def encoding_scale(order, norm="sn3d"):
+    """scale[l], l = 0..order: 1 for "n3d", 1.0 / sqrt(2 l + 1) for "sn3d" (float64)."""
+    channels(order)
+    if norm not in ("sn3d", "n3d"):
+        raise ValueError("norm must be 'sn3d' or 'n3d'")
+    l = np.arange(int(order) + 1, dtype=np.float64)
+    return np.ones(int(order) + 1) if norm == "n3d" else 1.0 / np.sqrt(2.0 * l + 1.0)
+
+
+def _check_angles(elev, azim, gain):
+    e, a = np.asarray(elev, dtype=np.float64), np.asarray(azim, dtype=np.float64)
+    if e.ndim < 2 or e.shape != a.shape:
+        raise ValueError("elev and azim must share a shape [..., n_src, nb]")
+    if not (np.isfinite(e).all() and np.isfinite(a).all()):
+        raise ValueError("angles must be finite")
+    g = np.ones(e.shape) if gain is None else np.asarray(gain, dtype=np.float64)
+    if g.shape != e.shape:
+        raise ValueError(f"gain must have shape {e.shape}, got {g.shape}")
+    if not np.isfinite(g).all():
+        raise ValueError("gains must be finite")
+    return e, a, g
+
+
+def encoding_gains(elev, azim, order, norm="sn3d", gain=None):
+    """E [..., nb, n_src, C] float64 of world-frame angles [..., n_src, nb] in radians (gain None or of their shape):
+    E[k][s][c] = (gain[s][k] * scale[l(c)]) * Y_c(d(elev[s][k], azim[s][k])), scale = encoding_scale(order, norm).
+    ValueError for non-finite input."""
+    scale = encoding_scale(order, norm)
+    e, a, g = _check_angles(elev, azim, gain)
+    Y = sh_n3d(directions(e, a), order)                                     # [..., n_src, nb, C]
+    E = (g[..., None] * scale[order_of_channel(Y.shape[-1])]) * Y
+    return np.ascontiguousarray(np.swapaxes(E, -3, -2))
+
+
+def encode(signals, K, E, base=None):
+    """The bed [C, T] float64 of signals [n_src, T]: for t = k K + j,
+    bed_c(t) = base_c(t) + sum_s (E_k[s][c] + (j / K)(E_{k+1}[s][c] - E_k[s][c])) x_s(t).  E [nb, n_src, C] with
+    nb >= (T - 1) // K + 2 boundaries, or [n_src, C]: static.  base: None or an existing bed [C, T] to add to.  This is
+    decode with rows and columns swapped: the coefficients, not the directions, are interpolated between boundaries."""
+    x, E, K = np.asarray(signals, dtype=np.float64), np.asarray(E, dtype=np.float64), int(K)
+    if x.ndim != 2 or E.ndim not in (2, 3) or E.shape[-2] != x.shape[0] or K <= 0:
+        raise ValueError("signals must be [n_src, T], E [nb, n_src, C] or [n_src, C], K > 0")
+    T, C = x.shape[1], E.shape[-1]
+    if base is not None:
+        base = np.asarray(base, dtype=np.float64)
+        if base.shape != (C, T):
+            raise ValueError(f"base must be [{C}, {T}]")
+    if E.ndim == 2:
+        out = E.T @ x
+    else:
+        if T and E.shape[0] < (T - 1) // K + 2:
+            raise ValueError(f"E must hold >= {(T - 1) // K + 2} boundaries")
+        out = np.zeros((C, T))
+        span = max(1, (1 << 22) // (E.shape[1] * C))                        # samples per pass (memory, not arithmetic)
+        for t0 in range(0, T, span):
+            t = np.arange(t0, min(t0 + span, T))
+            k, w = t // K, (t % K) / K
+            Et = E[k] + w[:, None, None] * (E[k + 1] - E[k])                # every sample's own bank [n, n_src, C]
+            Et *= x[:, t].T[:, :, None]
+            out[:, t] = Et.sum(axis=1).T                                    # s ascending, whatever the span: blocks == whole
+    return out if base is None else base + out
 
 
 # ---- the device side ------------------------------------------------------------------------------------------------------
@@ -494,3 +603,283 @@ class BedStream:
             M = mixing_matrices_device(d, q, out=self._M)
         decode_device(x, self.renderer.K, M, out)
         return out
+
+
+# ---- the encoder: the device side -------------------------------------------------------------------------
+def _angles_to_device(elev, azim, gain, dev=None):
+    """(elev, azim, gain or None) as float64 device tensors [G, n_src, nb] sharing elev's strides (gain its own), unit
+    stride over the boundaries, and whether the caller's form had the group axis.  Device tensors are checked for shape
+    and dtype only; host data is validated (finite) and uploaded."""
+    import torch
+    on_dev = [isinstance(t, torch.Tensor) and t.is_cuda for t in (elev, azim)]
+    if all(on_dev):
+        if elev.dtype != torch.float64 or azim.dtype != torch.float64 or elev.dim() not in (2, 3) or elev.shape != azim.shape:
+            raise ValueError("elev and azim must be float64 tensors of one shape [n_src, nb] or [G, n_src, nb]")
+        dev = elev.device
+        e, a = elev, azim
+        if e.stride(-1) != 1 or e.stride() != a.stride() or min(e.stride()) < 0:
+            e, a = e.contiguous(), a.contiguous()
+        g = None
+        if gain is not None:
+            if isinstance(gain, torch.Tensor) and gain.is_cuda:
+                if gain.dtype != torch.float64 or gain.shape != e.shape:
+                    raise ValueError(f"gain must be a float64 tensor of shape {tuple(e.shape)}")
+                g = gain if gain.stride(-1) == 1 and min(gain.stride()) >= 0 else gain.contiguous()
+            else:
+                from .apply_hrtf import check_gain
+                g = torch.from_numpy(np.ascontiguousarray(check_gain(gain, tuple(e.shape)))).to(dev)
+    elif any(on_dev):
+        raise ValueError("elev and azim must both be device tensors or both host data")
+    else:
+        he, ha, hg = _check_angles(*(t.numpy() if isinstance(t, torch.Tensor) else t for t in (elev, azim)),
+                                   None if gain is None else (gain.cpu().numpy() if isinstance(gain, torch.Tensor) else gain))
+        if he.ndim not in (2, 3):
+            raise ValueError("elev and azim must be [n_src, nb] or [G, n_src, nb]")
+        dev = dev if dev is not None else _hip.require_gpu()
+        e, a = (torch.from_numpy(np.ascontiguousarray(t)).to(dev) for t in (he, ha))
+        g = None if gain is None else torch.from_numpy(np.ascontiguousarray(hg)).to(dev)
+    grouped = e.dim() == 3
+    if not grouped:
+        e, a, g = e[None], a[None], None if g is None else g[None]
+    return e, a, g, grouped, dev
+
+
+def encoding_gains_device(elev, azim, order, norm="sn3d", gain=None, out=None):
+    """One bas_ambi_encode_gains_f32 launch: world-frame angles [n_src, nb] or [G, n_src, nb] (float64 device tensors with
+    unit stride over the boundaries and shared strides, such as a renderer's trajectory_views, are read where they are and
+    checked for shape and dtype only; host data goes through the checks of encoding_gains and is uploaded) and gain (None,
+    or of the same shape with strides of its own) -> E float32 [.., nb, n_src, C] on the device.  out: a float32 device
+    tensor of that shape, any strides >= 0 over the leading axes that address every element once, [n_src, C] dense."""
+    import torch
+    scale = encoding_scale(order, norm)
+    C = channels(order)
+    e, a, g, grouped, dev = _angles_to_device(elev, azim, gain, None if out is None else out.device)
+    G, n_src, nb = (int(v) for v in e.shape)
+    shape = ((G,) if grouped else ()) + (nb, n_src, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+              and out.device == dev):
+        raise ValueError(f"out must be a float32 tensor of shape {shape} on {dev}")
+    if not 1 <= n_src <= ENCODE_MAX_SOURCES:
+        raise ValueError(f"n_src must be in 1..{ENCODE_MAX_SOURCES}")
+    if G * nb == 0:
+        return out
+    if out.stride(-1) != 1 or out.stride(-2) != C:
+        raise ValueError("out: the [n_src, C] banks must be dense")
+    try:
+        with _hip.on_device(dev):
+            _hip.call("bas_ambi_encode_gains_f32", _hip.ptr(e), _hip.ptr(a), e.stride(0) if grouped else 0, e.stride(1),
+                      _hip.ptr(g), 0 if g is None or not grouped else g.stride(0), 0 if g is None else g.stride(1),
+                      scale.ctypes.data, int(order), G, n_src, nb, _hip.ptr(out), out.stride(0) if grouped else 0,
+                      out.stride(-3), _hip.current_stream(dev))
+    except _hip.BasError as err:
+        _shape_error(err)
+    return out
+
+
+def encode_device(x, K, E, out, base=None):
+    """One bas_ambi_encode_f32 launch.  out: float32 device view [C, T] or [G, C, T] (unit sample stride, any row and
+    group strides that address every element once: a BedStream's bed_view serves); x: float32 device tensor [n_src, T]
+    (shared by all groups) or [G, n_src, T], unit sample stride (a renderer's input_view rows serve); E: float32 device
+    tensor [n_src, C] (static, shared), [nb, n_src, C] (shared) or [G, nb, n_src, C] with nb >= (T - 1) // K + 2, or
+    nb == 1: static.  [n_src, C] dense.  base: None, or a float32 device tensor of out's shape that is added - out itself
+    (in place) or a tensor that does not overlap it.  Returns out."""
+    import torch
+    for t, name in ((x, "x"), (E, "E"), (out, "out")) + (() if base is None else ((base, "base"),)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            raise ValueError(f"{name} must be a float32 device tensor")
+    if out.dim() not in (2, 3) or x.dim() not in (2, 3) or E.dim() not in (2, 3, 4):
+        raise ValueError("out must be [C, T] or [G, C, T], x [n_src, T] or [G, n_src, T], E [n_src, C], [nb, n_src, C] or "
+                         "[G, nb, n_src, C]")
+    C, T = int(out.shape[-2]), int(out.shape[-1])
+    G = int(out.shape[0]) if out.dim() == 3 else 1
+    n_src, K = int(x.shape[-2]), int(K)
+    if K <= 0:
+        raise ValueError("K must be positive")
+    if tuple(E.shape[-2:]) != (n_src, C) or int(x.shape[-1]) != T:
+        raise ValueError(f"E must end in [{n_src}, {C}] and x hold {T} samples")
+    if (x.dim() == 3 and x.shape[0] != G) or (E.dim() == 4 and E.shape[0] != G):
+        raise ValueError(f"x and E must have out's {G} groups")
+    if base is not None and tuple(base.shape) != tuple(out.shape):
+        raise ValueError(f"base must have out's shape {tuple(out.shape)}")
+    nb = 1 if E.dim() == 2 else int(E.shape[-3])
+    if nb != 1 and T and nb < (T - 1) // K + 2:
+        raise ValueError(f"E must hold >= {(T - 1) // K + 2} boundaries (or one: static)")
+    if T and (out.stride(-1) != 1 or x.stride(-1) != 1 or (base is not None and base.stride(-1) != 1)):
+        raise ValueError("x, base and out need unit sample stride")
+    if E.stride(-1) != 1 or E.stride(-2) != C:
+        raise ValueError("E: the [n_src, C] banks must be dense")
+    dev = out.device
+    xs_g = x.stride(0) if x.dim() == 3 else 0
+    es_g = E.stride(0) if E.dim() == 4 else 0
+    es_k = 0 if nb == 1 else E.stride(-3)
+    ys_g = out.stride(0) if out.dim() == 3 else 0
+    bs_g, bs_c = (0, 0) if base is None else (base.stride(0) if base.dim() == 3 else 0, base.stride(-2))
+    try:
+        with _hip.on_device(dev):
+            _hip.call("bas_ambi_encode_f32", _hip.ptr(x), xs_g, x.stride(-2), _hip.ptr(E), es_g, es_k, n_src, C, G, T, K,
+                      _hip.ptr(base), bs_g, bs_c, _hip.ptr(out), ys_g, out.stride(-2), _hip.current_stream(dev))
+    except _hip.BasError as err:
+        _shape_error(err)
+    return out
+
+
+def encode_bed(signals, chunksize, elev, azim, order, norm="sn3d", gain=None, delay=None, interp="cubic", base=None):
+    """n_src point sources as one bed: a float32 device tensor [C, T] (rows 16-byte aligned).  signals [n_src, T] (host
+    array or device tensor); elev, azim (world frame, radians) and gain [n_src, n_q] at the n_q = ceil(T / K) + 1 chunk
+    boundaries - host data or float64 device tensors, e.g. what scene.scene_params_device(pos, fs, listener_pos=lp,
+    head=None, room=room) returns; delay [n_src, n_q] in samples: the rows go through propagation.delayed_inputs_device
+    first; base: a bed [C, T] to add to (recorded ambience).  render_bed(encode_bed(..), K, S, tbl, dec, head=q) is the
+    whole path: the field is in world coordinates and the decoder turns it."""
+    import torch
+    from .apply_hrtf import padded_rows
+    C, K = channels(order), int(chunksize)
+    if K <= 0:
+        raise ValueError("chunksize must be positive")
+    x = signals if isinstance(signals, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(signals, np.float32)))
+    if x.dim() != 2 or not 1 <= x.shape[0] <= ENCODE_MAX_SOURCES:
+        raise ValueError(f"signals must be [n_src, T] with 1 <= n_src <= {ENCODE_MAX_SOURCES}")
+    n_src, T = int(x.shape[0]), int(x.shape[1])
+    n_q = -(-T // K) + 1
+    for name, arg in (("elev", elev), ("azim", azim), ("gain", gain), ("delay", delay)):
+        if arg is not None and tuple(np.shape(arg)) != (n_src, n_q):
+            raise ValueError(f"{name} must have shape ({n_src}, {n_q})")
+    dev = x.device if x.is_cuda else _hip.require_gpu()
+    with _hip.on_device(dev):
+        if delay is not None:
+            from . import propagation
+            x = propagation.delayed_inputs_device(x.to(dev), K, delay, interp)
+        else:
+            x = x.to(device=dev, dtype=torch.float32)
+            if x.stride(-1) != 1:
+                x = x.contiguous()
+        if base is not None:
+            base = _bed_to_device(base, C, dev)
+            if tuple(base.shape) != (C, T):
+                raise ValueError(f"base must be [{C}, {T}]")
+        out = padded_rows(C, T, dev)
+        E = encoding_gains_device(*(t.to(dev) if isinstance(t, torch.Tensor) and t.is_cuda else t for t in (elev, azim)),
+                                  order, norm, gain.to(dev) if isinstance(gain, torch.Tensor) and gain.is_cuda else gain)
+        if T:
+            encode_device(x, K, E, out, base)
+    return out
+
+
+class BedEncoder:
+    """The encoder as a stream stage: n_src sources into one bed per block.
+
+        enc = BedEncoder(3, n_src, K)                   # n_groups=G: G independent encoders in the same two launches
+        enc.prepare(B)
+        for ...:
+            enc.input_view(B)[...] = block              # float32 [n_src, B]; the world-frame angles (float64 [n_src, nb])
+            el, az = enc.trajectory_views(B)            # and gains go into trajectory_views(B) and gain_view(B) - the
+            ...                                         # layout scene.scene_params_device(out=) writes
+            enc.encode(stage.bed_view(B))               # stage: a BedStream; then stage.write(stage.bed_view(B), q_b)
+
+    encode() is two launches (the banks, then the mix): no allocation after prepare(B), no synchronisation - capturable.
+    There is no carried state: a block's bits depend on its own nb = B / K + 1 boundaries, and consecutive blocks repeat
+    their shared boundary's angles and gains, as with gains and heads.  One encoded bed serves any number of listeners:
+    the field is in world coordinates (a StreamBatchRenderer's BedStream takes it as the shared [C, B] bed)."""
+
+    def __init__(self, order, n_src, chunksize, norm="sn3d", n_groups=None, device=None):
+        self.order, self.C = int(order), channels(order)
+        self.scale = encoding_scale(order, norm)
+        self.norm = norm
+        self.n_src, self.K = int(n_src), int(chunksize)
+        if not 1 <= self.n_src <= ENCODE_MAX_SOURCES:
+            raise ValueError(f"n_src must be in 1..{ENCODE_MAX_SOURCES}")
+        if self.K <= 0:
+            raise ValueError("chunksize must be positive")
+        if n_groups is not None and not 1 <= int(n_groups) <= 65535:
+            raise ValueError("n_groups must be None or in 1..65535")
+        self.G = None if n_groups is None else int(n_groups)
+        self.device = _hip.require_gpu(device)
+        self._B = None
+
+    def prepare(self, B):
+        """The stage's buffers for blocks of B samples: signals [n_src, B], angles and gains [n_src, nb] (gains one), the
+        banks [nb, n_src, C]; with n_groups each with a leading G.  Captures nothing."""
+        import torch
+        B = int(B)
+        if B <= 0 or B % self.K:
+            raise ValueError("block length must be a positive multiple of the chunk size")
+        if self._B != B:
+            nb, lead = B // self.K + 1, (() if self.G is None else (self.G,))
+            self._x = torch.zeros(lead + (self.n_src, (B + 3) // 4 * 4), dtype=torch.float32, device=self.device)[..., :B]
+            self._elev = torch.zeros(lead + (self.n_src, nb), dtype=torch.float64, device=self.device)
+            self._azim = torch.zeros_like(self._elev)
+            self._gain = torch.ones_like(self._elev)
+            self._E = torch.zeros(lead + (nb, self.n_src, self.C), dtype=torch.float32, device=self.device)
+            self._B = B
+
+    def _ready(self, B):
+        if self._B != int(B):
+            self.prepare(B)
+
+    def input_view(self, B):
+        """The stage's own signal rows, float32 [n_src, B] or [G, n_src, B]."""
+        self._ready(B)
+        return self._x
+
+    def trajectory_views(self, B):
+        """(elev, azim): the stage's own world-frame angles, float64 [n_src, nb] or [G, n_src, nb]."""
+        self._ready(B)
+        return self._elev, self._azim
+
+    def gain_view(self, B):
+        """The stage's own gains, float64 [n_src, nb] or [G, n_src, nb]: one until written."""
+        self._ready(B)
+        return self._gain
+
+    def _take(self, arg, buf, name, check):
+        """A per-boundary argument: None -> the stage's buffer as the caller left it; a float64 device tensor of the
+        buffer's shape is read where it is; host data is validated and copied into the buffer."""
+        import torch
+        if arg is None:
+            return buf
+        if isinstance(arg, torch.Tensor) and arg.is_cuda:
+            if arg.dtype != torch.float64 or tuple(arg.shape) != tuple(buf.shape) or arg.device != self.device:
+                raise ValueError(f"{name} must be a float64 tensor of shape {tuple(buf.shape)} on {self.device}")
+            return arg
+        arr = np.asarray(arg.numpy() if isinstance(arg, torch.Tensor) else arg, dtype=np.float64)
+        if arr.shape != tuple(buf.shape):
+            raise ValueError(f"{name} must have shape {tuple(buf.shape)}")
+        if not np.isfinite(arr).all():
+            raise ValueError(f"{check} must be finite")
+        buf.copy_(torch.from_numpy(np.ascontiguousarray(arr)))
+        return buf
+
+    def encode(self, out, block=None, elev=None, azim=None, gain=None, base=None):
+        """out: a float32 device view [C, B] or [G, C, B] (a BedStream's bed_view).  block: None (input_view as the caller
+        filled it), a float32 device tensor [(G,) n_src, B] read where it is, or host data staged in input_view.  elev,
+        azim, gain: None (the stage's views) or as encoding_gains_device takes them.  base: as encode_device.  Returns
+        out."""
+        import torch
+        lead = () if self.G is None else (self.G,)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
+                and out.dim() == len(lead) + 2 and tuple(out.shape[:-1]) == lead + (self.C,)):
+            raise ValueError(f"out must be a float32 device tensor {list(lead + (self.C,))} x B")
+        B = int(out.shape[-1])
+        if B <= 0 or B % self.K:
+            raise ValueError("block length must be a positive multiple of the chunk size")
+        self._ready(B)
+        if block is None:
+            x = self._x
+        elif isinstance(block, torch.Tensor) and block.is_cuda:              # read where it is: refused unless it can be
+            if block.dtype != torch.float32 or block.device != self.device or tuple(block.shape) != tuple(self._x.shape) \
+                    or block.stride(-1) != 1:
+                raise ValueError(f"a device block must be float32 {list(self._x.shape)} on {self.device} with unit sample "
+                                 "stride")
+            x = block
+        else:                                                                # host data: staged in input_view
+            arr = np.asarray(block.numpy() if isinstance(block, torch.Tensor) else block, dtype=np.float32)
+            if arr.shape != tuple(self._x.shape):
+                raise ValueError(f"block must be {list(self._x.shape)}")
+            x = self._x
+            x.copy_(torch.from_numpy(np.ascontiguousarray(arr)))
+        e = self._take(elev, self._elev, "elev", "angles")
+        a = self._take(azim, self._azim, "azim", "angles")
+        g = self._take(gain, self._gain, "gain", "gains")
+        encoding_gains_device(e, a, self.order, self.norm, g, out=self._E)
+        return encode_device(x, self.K, self._E, out, base)

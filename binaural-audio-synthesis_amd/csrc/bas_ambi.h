@@ -16,6 +16,17 @@
 #define MM_FILL 512                     // workgroups the speaker rows are dealt to (blockIdx.z) where tiles x groups < 256
 #define MM_LDS_FLOATS 8192              // matrices a tile can hold in LDS: MM_LDS_FLOATS / (V CP) boundaries (>= 8)
 
+// The encoder (include/bas.h "ambisonic encoder")
+#define ENCODE_BLOCK 32                 // sources of one first-level chain of bas_ambi_encode_f32 (part of the definition)
+#define ENC_MAX_SRC 65536
+#define ENC_THREADS 256
+#define ENC_TILE 1024                   // outputs of one workgroup pass: four per lane
+#define ENC_FILL 512                    // below ENC_FILL / 2 workgroups the channels are dealt in slices of four
+#define ENC_LDS_FLOATS 8192             // the banks of one slab of sources: n_sets x slab x (channels of the slice)
+#define ENC_MAX_SLAB 512                // sources of one LDS stage at most (a longer stage saves nothing)
+#define ENC_STATIC_SLICE 16             // channels one workgroup accumulates: 16 x 4 block sums + 16 x 4 totals = 128 registers
+#define ENC_BOUNDARY_SLICE 8            // .. with two banks: 8 x 4 x 2 + 8 x 4 x 2
+
 // Y_0 .. Y_{C-1} of the unit vector d (project frame: +y front, +x right, +z up) in (x, y, z) = (d_y, -d_x, d_z).  The
 // constants are the correctly rounded binary64 square roots.
 __device__ __forceinline__ void bas_sh_n3d(double dx, double dy, double dz, int order, double *Y) {

@@ -711,6 +711,45 @@ int bas_ambi_matrices_f32(const double *head, long hs_g, long hs_c, const double
 int bas_matrix_mix_f32(const float *x, long xs_g, long xs_c, const float *m, long ms_g, long ms_k, int C, int V,
                        int n_groups, long T, int K, float *y, long ys_g, long ys_v, bas_stream_t stream);
 
+/* ---- ambisonic encoder (no reference counterpart) -------------------------------------------------------
+ * The stage in front of a bed: n_src point sources with directions (and gains) at chunk boundaries are summed into one bed
+ * of order N = 1..3 in world coordinates, conventions as above.  Both entries: one stream, no allocation, no synchronisation
+ * (capturable), one launch; every argument check runs before the launch; all strides in elements, >= 0 and below 2^40.
+ *   bas_ambi_encode_gains_f32: angles (float64 radians, world frame) at elev + g as_g + s as_s + k and azim likewise (the
+ *     layout of a renderer's trajectory views), gain likewise with its own strides (NULL: 1) -> banks E (float32 at
+ *     e + g es_g + k es_k + s C + c, the [n_src][C] banks dense):
+ *       d = (-sin az cos el, cos az cos el, sin el);  E[s][c] = (gain * scale[l(c)]) * Y_c(d),  l(c) the order of channel c;
+ *     scale: order + 1 doubles in HOST memory, read before the launch (1 for N3D output, 1 / sqrt(2 l + 1) for SN3D: the
+ *     host's choice).  Binary64 without contraction, the product order as written, rounded to binary32 once.  Nothing is
+ *     validated on the device.  order in 1..3, n_src in 1..65536, n_groups nb n_src <= 2^30, and the output's strides must
+ *     address every element once (BAS_E_SHAPE); elev, azim, scale, e required (BAS_E_NULL); float64 pointers 8-byte
+ *     aligned, e 4-byte (BAS_E_ALIGN).  n_groups == 0 or nb == 0: nothing to do.
+ *   bas_ambi_encode_f32: the hot path.  Signals x + g xs_g + s xs_s (n_src rows of T samples), banks
+ *     e + g es_g + k es_k + s C + c for the (T - 1) / K + 2 chunk boundaries, output rows y + g ys_g + c ys_c (C <= 16, any
+ *     value).  The reduction over the sources has two levels; sources form blocks of BAS_AMBI_ENCODE_BLOCK = 32
+ *     consecutive rows.  For t = k K + j:
+ *       per block b:   A_b = fmaf(E_k[s][c], x_s(t), A_b) from +0 with s ascending inside the block, B_b likewise with E_{k+1};
+ *       across blocks: A = A_0, then A = A + A_b for b = 1, 2, .. ascending (binary32 additions), B likewise;
+ *       w = (float)j * (1.0f / (float)K),  y = fmaf(w, B - A, A);   with base:  y = base_c(t) + y  (one addition).
+ *     es_k == 0 is the static form, y = A (B skipped): the bits of the per-boundary form fed repeated banks.  An output's
+ *     bits depend on (j, K, n_src, E_k[:, c], E_{k+1}[:, c]), the n_src inputs at t and base_c(t) alone - not on tiles, T,
+ *     block boundaries of a stream, alignment, grid, slab sizes or groups.  With n_src <= 32 this is the chain of
+ *     bas_matrix_mix_f32 fed the transposed bank.  xs_g == 0 shares the signals, es_g == 0 the banks over all groups.
+ *     base: NULL, or rows base + g bs_g + c bs_c; base may be y itself with y's strides (in place: every output is read and
+ *     written by the one lane that owns it), otherwise it must not overlap y.  16-byte loads and stores where a row is
+ *     16-byte aligned, 4-byte ones elsewhere.  C in 1..16, n_src in 1..65536, T < 2^30, n_groups <= 65535, K > 0,
+ *     es_k == 0 or >= n_src C with ((T - 1) / K + 2) es_k <= 2^62, the output's strides must address every element once,
+ *     and the output must overlap neither x nor the banks (BAS_E_SHAPE); x, e, y required (BAS_E_NULL); x, e, base, y 4-byte aligned (BAS_E_ALIGN).
+ *     n_groups == 0 or T == 0: nothing to do. */
+#define BAS_AMBI_ENCODE_BLOCK 32
+#define BAS_AMBI_ENCODE_MAX_SOURCES 65536
+int bas_ambi_encode_gains_f32(const double *elev, const double *azim, long as_g, long as_s, const double *gain, long gs_g,
+                              long gs_s, const double *scale, int order, int n_groups, int n_src, int nb, float *e,
+                              long es_g, long es_k, bas_stream_t stream);
+int bas_ambi_encode_f32(const float *x, long xs_g, long xs_s, const float *e, long es_g, long es_k, int n_src, int C,
+                        int n_groups, long T, int K, const float *base, long bs_g, long bs_c, float *y, long ys_g,
+                        long ys_c, bas_stream_t stream);
+
 /* ---- table builder: the heavy parts of upsample_irs.m ---------
  * PARITY UNPINNED (no Octave, no IRCAM data in the build: upsample_irs.py's header).  All
  * arrays float64 on the device; h = the 2 Lh + 1 taps of the resampling filter Octave's

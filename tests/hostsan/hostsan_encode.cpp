@@ -1,0 +1,200 @@
+// The host half of the ambisonic encoder's two entry points (include/bas.h "ambisonic encoder") under AddressSanitizer and
+// UndefinedBehaviorSanitizer, stand-alone: `make -C binaural-audio-synthesis_amd/csrc hostsan_encode` links this file with
+// the library's objects (host code sanitized, device code as shipped).  For bas_ambi_encode_gains_f32 and
+// bas_ambi_encode_f32: one valid argument list, which with no device to run on returns a positive hipError_t, and its
+// violations, each of which returns the code bas.h documents and leaves a text naming the entry point.  The pointers are
+// never dereferenced by the host code (scale is: it is host memory by contract).  Exits 77 where a GPU is visible.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "../../include/bas.h"
+
+static int g_fail = 0, g_checks = 0;
+
+static void expect(int line, const char *what, int rc, int want, const char *entry) {
+    ++g_checks;
+    const char *text = bas_last_error();
+    bool ok = want > 0 ? rc > 0 : rc == want;
+    if (ok && want != 0) ok = text && strstr(text, entry) != nullptr;      // every failure leaves a text naming the entry
+    if (!ok && ++g_fail <= 40)
+        fprintf(stderr, "hostsan_encode: FAIL line %d: %s: returned %d, want %s%d, text \"%s\"\n", line, what, rc,
+                want > 0 ? "> " : "", want > 0 ? 0 : want, text ? text : "(null)");
+}
+#define EXPECT(what, call, want, entry) expect(__LINE__, what, (call), (want), entry)
+
+static const int E_NULL = -1, E_SHAPE = -2, E_ALIGN = -3, NO_DEVICE = 1;
+
+struct Gains {
+    const double *elev, *azim;
+    long as_g, as_s;
+    const double *gain;
+    long gs_g, gs_s;
+    const double *scale;
+    int order, G, n_src, nb;
+    float *e;
+    long es_g, es_k;
+    int call() const {
+        return bas_ambi_encode_gains_f32(elev, azim, as_g, as_s, gain, gs_g, gs_s, scale, order, G, n_src, nb, e, es_g, es_k,
+                                         nullptr);
+    }
+};
+
+struct Mix {
+    const float *x;
+    long xs_g, xs_s;
+    const float *e;
+    long es_g, es_k;
+    int n_src, C, G;
+    long T;
+    int K;
+    const float *base;
+    long bs_g, bs_c;
+    float *y;
+    long ys_g, ys_c;
+    int call() const {
+        return bas_ambi_encode_f32(x, xs_g, xs_s, e, es_g, es_k, n_src, C, G, T, K, base, bs_g, bs_c, y, ys_g, ys_c, nullptr);
+    }
+};
+
+template <class T>
+static T *at(uintptr_t base, long bytes) {
+    return reinterpret_cast<T *>(base + bytes);
+}
+
+static void gains_section() {
+    static const char *N = "bas_ambi_encode_gains_f32";
+    static double scale[4] = {1.0, 0.5773502691896258, 0.4472135954999579, 0.3779644730092272};
+    const uintptr_t p = uintptr_t(1) << 32;                                  // made-up device addresses, 64-byte aligned
+    const int order = 3, C = 16, G = 3, n_src = 40, nb = 5;
+    const Gains ok = {at<const double>(p, 0), at<const double>(p, 1 << 20), (long)n_src * nb, nb, at<const double>(p, 2 << 20),
+                      (long)n_src * nb, nb, scale, order, G, n_src, nb, at<float>(p, 4 << 20), (long)nb * n_src * C,
+                      (long)n_src * C};
+    Gains a;
+    EXPECT("valid arguments, no device", ok.call(), NO_DEVICE, N);
+    a = ok; a.gain = nullptr; a.gs_g = a.gs_s = 0;
+    EXPECT("valid arguments without gain, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.G = 0; a.e = nullptr;
+    EXPECT("no groups: nothing to do", a.call(), 0, N);
+    a = ok; a.nb = 0; a.elev = nullptr;
+    EXPECT("no boundaries: nothing to do", a.call(), 0, N);
+    // ---- null pointers
+    a = ok; a.elev = nullptr; EXPECT("elev null", a.call(), E_NULL, N);
+    a = ok; a.azim = nullptr; EXPECT("azim null", a.call(), E_NULL, N);
+    a = ok; a.scale = nullptr; EXPECT("scale null", a.call(), E_NULL, N);
+    a = ok; a.e = nullptr; EXPECT("e null", a.call(), E_NULL, N);
+    // ---- zero and over-limit counts
+    for (int o : {0, 4, -1}) { a = ok; a.order = o; EXPECT("order", a.call(), E_SHAPE, N); }
+    for (int n : {0, -1, 65537}) { a = ok; a.n_src = n; EXPECT("n_src", a.call(), E_SHAPE, N); }
+    a = ok; a.G = -1; EXPECT("n_groups < 0", a.call(), E_SHAPE, N);
+    a = ok; a.nb = -1; EXPECT("nb < 0", a.call(), E_SHAPE, N);
+    a = ok; a.G = 1 << 16; a.nb = 1 << 10; a.n_src = 17; a.es_g = (long)a.nb * a.n_src * C; a.es_k = (long)a.n_src * C;
+    EXPECT("n_groups nb n_src > 2^30", a.call(), E_SHAPE, N);
+    // ---- negative strides and strides of 2^40
+    for (int i = 0; i < 6; ++i)
+        for (long v : {-1L, 1L << 40}) {
+            a = ok;
+            long *f[6] = {&a.as_g, &a.as_s, &a.gs_g, &a.gs_s, &a.es_g, &a.es_k};
+            *f[i] = v;
+            EXPECT("stride", a.call(), E_SHAPE, N);
+        }
+    // ---- a doubly addressed output
+    a = ok; a.es_k = (long)n_src * C - 1; EXPECT("two boundaries' banks overlap", a.call(), E_SHAPE, N);
+    a = ok; a.es_g = 0; EXPECT("groups alias", a.call(), E_SHAPE, N);
+    a = ok; a.es_k = 0; EXPECT("boundaries alias", a.call(), E_SHAPE, N);
+    a = ok; a.es_g = a.es_k; EXPECT("groups meet boundaries", a.call(), E_SHAPE, N);
+    a = ok; a.es_g = (long)nb * n_src * C - 1; EXPECT("groups overlap by one", a.call(), E_SHAPE, N);
+    // ---- misaligned pointers
+    a = ok; a.elev = at<const double>(p, 4); EXPECT("elev misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.azim = at<const double>(p, (1 << 20) + 2); EXPECT("azim misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.gain = at<const double>(p, (2 << 20) + 1); EXPECT("gain misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.scale = reinterpret_cast<const double *>(reinterpret_cast<const char *>(scale) + 4);
+    EXPECT("scale misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.e = at<float>(p, (4 << 20) + 2); EXPECT("e misaligned", a.call(), E_ALIGN, N);
+}
+
+static void mix_section() {
+    static const char *N = "bas_ambi_encode_f32";
+    const uintptr_t p = uintptr_t(1) << 33;
+    const int n_src = 100, C = 16, G = 2, K = 128;
+    const long T = 1000, row = 1024, n_k = (T - 1) / K + 2;
+    const uintptr_t x0 = p, e0 = p + (uintptr_t(8) << 20), b0 = p + (uintptr_t(16) << 20), y0 = p + (uintptr_t(24) << 20);
+    const Mix ok = {at<const float>(x0, 0), n_src * row, row, at<const float>(e0, 0), n_k * n_src * C, (long)n_src * C, n_src,
+                    C, G, T, K, at<const float>(b0, 0), C * row, row, at<float>(y0, 0), C * row, row};
+    const long x_n = (G - 1) * ok.xs_g + (n_src - 1) * row + T, y_n = (G - 1) * ok.ys_g + (C - 1) * row + T;
+    const long e_n = (G - 1) * ok.es_g + (n_k - 1) * ok.es_k + (long)n_src * C;
+    Mix a;
+    EXPECT("valid arguments, no device", ok.call(), NO_DEVICE, N);
+    a = ok; a.base = nullptr; a.bs_g = a.bs_c = 0;
+    EXPECT("valid arguments without base, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.base = a.y;
+    EXPECT("base == y with y's strides (in place), no device", a.call(), NO_DEVICE, N);
+    a = ok; a.xs_g = 0; a.es_g = 0; a.es_k = 0;
+    EXPECT("shared signals, one static bank, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.G = 0; a.y = nullptr; EXPECT("no groups: nothing to do", a.call(), 0, N);
+    a = ok; a.T = 0; a.x = nullptr; a.y = nullptr; EXPECT("no samples: nothing to do", a.call(), 0, N);
+    // ---- null pointers
+    a = ok; a.x = nullptr; EXPECT("x null", a.call(), E_NULL, N);
+    a = ok; a.e = nullptr; EXPECT("e null", a.call(), E_NULL, N);
+    a = ok; a.y = nullptr; EXPECT("y null", a.call(), E_NULL, N);
+    // ---- zero and over-limit counts
+    for (int c : {0, 17, -1}) { a = ok; a.C = c; EXPECT("C", a.call(), E_SHAPE, N); }
+    for (int n : {0, -1, 65537}) { a = ok; a.n_src = n; EXPECT("n_src", a.call(), E_SHAPE, N); }
+    for (int g : {-1, 65536}) { a = ok; a.G = g; EXPECT("n_groups", a.call(), E_SHAPE, N); }
+    for (long t : {-1L, 1L << 30}) { a = ok; a.T = t; EXPECT("T", a.call(), E_SHAPE, N); }
+    for (int k : {0, -3}) { a = ok; a.K = k; EXPECT("K", a.call(), E_SHAPE, N); }
+    // ---- negative strides and strides of 2^40
+    for (int i = 0; i < 8; ++i)
+        for (long v : {-1L, 1L << 40}) {
+            a = ok;
+            long *f[8] = {&a.xs_g, &a.xs_s, &a.es_g, &a.es_k, &a.bs_g, &a.bs_c, &a.ys_g, &a.ys_c};
+            *f[i] = v;
+            EXPECT("stride", a.call(), E_SHAPE, N);
+        }
+    // ---- es_k between 1 and n_src C - 1
+    for (long v : {1L, (long)n_src * C - 1}) { a = ok; a.es_k = v; EXPECT("es_k inside a bank", a.call(), E_SHAPE, N); }
+    // ---- banks whose extent (n_k - 1) es_k would leave a signed long: T = 2^30 - 1 at K = 1 is 2^30 boundaries
+    a = ok; a.T = (1L << 30) - 1; a.K = 1; a.es_k = (1L << 40) - 1; a.es_g = 0; a.xs_s = a.bs_c = a.ys_c = 1L << 30;
+    a.xs_g = 100L << 30; a.bs_g = a.ys_g = 16L << 30;
+    EXPECT("2^30 boundaries at es_k = 2^40 - 1", a.call(), E_SHAPE, N);
+    // ---- a doubly addressed output
+    a = ok; a.ys_c = T - 1; EXPECT("rows overlap", a.call(), E_SHAPE, N);
+    a = ok; a.ys_c = 0; EXPECT("rows alias", a.call(), E_SHAPE, N);
+    a = ok; a.ys_g = 0; EXPECT("groups alias", a.call(), E_SHAPE, N);
+    a = ok; a.ys_g = row; EXPECT("groups meet rows", a.call(), E_SHAPE, N);
+    // ---- overlaps: y with x, e and base, by one float at either end
+    a = ok; a.y = at<float>(x0, 0); EXPECT("y == x", a.call(), E_SHAPE, N);
+    a = ok; a.y = at<float>(x0, 4 * (x_n - 1)); EXPECT("y meets x's last float", a.call(), E_SHAPE, N);
+    a = ok; a.y = at<float>(x0, -4 * (y_n - 1)); EXPECT("y's last float meets x", a.call(), E_SHAPE, N);
+    a = ok; a.y = at<float>(e0, 0); EXPECT("y == e", a.call(), E_SHAPE, N);
+    a = ok; a.y = at<float>(e0, 4 * (e_n - 1)); EXPECT("y meets e's last float", a.call(), E_SHAPE, N);
+    a = ok; a.y = at<float>(e0, -4 * (y_n - 1)); EXPECT("y's last float meets e", a.call(), E_SHAPE, N);
+    a = ok; a.base = at<const float>(y0, 4); EXPECT("base overlaps y, shifted", a.call(), E_SHAPE, N);
+    a = ok; a.base = a.y; a.bs_c = row + 4; a.bs_g = C * (row + 4); EXPECT("base == y with other strides", a.call(), E_SHAPE, N);
+    a = ok; a.base = at<const float>(y0, 4 * (y_n - 1)); EXPECT("base meets y's last float", a.call(), E_SHAPE, N);
+    // ---- misaligned pointers
+    a = ok; a.x = at<const float>(x0, 2); EXPECT("x misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.e = at<const float>(e0, 1); EXPECT("e misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.base = at<const float>(b0, 3); EXPECT("base misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.y = at<float>(y0, 2); EXPECT("y misaligned", a.call(), E_ALIGN, N);
+}
+
+int main() {
+    int n_dev = 0;
+    const hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e == hipSuccess && n_dev > 0) {
+        printf("hostsan_encode: refused: %d GPU device(s) visible - sanitized host code never drives a GPU; hide them "
+               "(HIP_VISIBLE_DEVICES=-1)\n", n_dev);
+        return 77;
+    }
+    (void)hipGetLastError();
+    gains_section();
+    const int after_gains = g_checks;
+    mix_section();
+    printf("hostsan_encode: bas_ambi_encode_gains_f32 %d checks, bas_ambi_encode_f32 %d checks, %d failed\n", after_gains,
+           g_checks - after_gains, g_fail);
+    printf("hostsan_encode: %s\n", g_fail ? "FAILED" : "ok");
+    return g_fail ? 1 : 0;
+}
