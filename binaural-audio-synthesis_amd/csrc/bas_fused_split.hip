@@ -16,6 +16,7 @@
 // plans, one workgroup per CU; and a wave alone on its SIMD pays ~6 clocks for every LDS read and wait.
 // No MFMA: this is a 1-D FIR (BASELINE.json north_star).
 #include "bas_fused.h"
+#include <stdlib.h>
 
 #ifndef FZ_NT_LOADS
 #define FZ_NT_LOADS 1
@@ -24,6 +25,9 @@
 #ifndef FS_PSPLIT
 #define FS_PSPLIT 1             // unit blocks of subchunks >= 32: the half-rate product P split once more (0: round 4's first form)
 #endif
+#ifndef FS_TAPS_ONCE
+#define FS_TAPS_ONCE 1          // ... and every tap of a unit read once and formed for both x rows that meet it (ffa_unitp1_asm;
+#endif                          // 0: ffa_unitp_asm.  The diagnostic build holds both: BAS_FS_TAPS_ONCE=0|1)
 #ifndef FS_STAGER_PRIO
 #define FS_STAGER_PRIO 3        // wave priority of the stagers (latency bound: their few instructions go first) ...
 #endif
@@ -50,6 +54,9 @@ __device__ unsigned long long bas_fs_stamps[1024 * 8 * 8];
 // of 32 inputs meets two / four crossfaded tap sets; unit blocks only (ffa_unit2_asm, ffa_unit4_asm).
 // PSPLIT (NSUB = 1, unit blocks only): the half-rate product P of the fast FIR is split once more (ffa_unitp_asm: 116
 // accumulator registers, 3.3 % fewer vector instructions per unit; DESIGN.md 4.0, profiles/r04_ubench_fast_fir_level2.txt).
+// PSPLIT = 2: the same arithmetic with every tap read ONCE (ffa_unitp1_asm, bas_fir_once_asm.inc): taps 32 b .. 32 b + 31
+// meet x row R - b in octets 4-7 of step b and x row R - b - 1 in octets 0-3 of step b + 1; one read at the older row's
+// slot serves both, formed with either row's weight (128 tap reads per unit instead of 256).
 template <int UNITLEN, int NSUB = 1, int PSPLIT = 0>
 __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
     FzArgs A, const float *__restrict__ x,                   // [n_src] rows of T_in floats, stride A.x_stride
@@ -212,6 +219,7 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
         int addr_buf = 0;                                    // the LDS buffer the addresses below point into
         unsigned tapv[5] = {0u, 0u, 0u, 0u, 0u}, xrow4 = 0u;
         float alv[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, blv[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        float wnv[4] = {0.f, 0.f, 0.f, 0.f};                 // PSPLIT = 2: the newer row's weight of merged group b
         const unsigned buf_bytes = 16u * (unsigned)buf4;
         for (long pid = 0; pid < n_pass; ++pid) {
             // the thread index is made opaque once per unit: what derives from it is recomputed per unit instead of being
@@ -263,6 +271,9 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                         tapv[r] = tap;
                         m_in -= 32;
                         const bool wrap = m_in < 0;                          // the next row up lies in the chunk before: one slot down
+                        // taps once: group r reads the older row's slot.  Where the pair crosses a chunk boundary this row opens
+                        // its chunk (weight 0) and its taps are h0_c = h0_{c-1} + d_{c-1}: the older slot's record at weight K / K
+                        if constexpr (PSPLIT == 2) { if (r < 4) wnv[r] = wrap ? 1.f : alv[r]; }
                         m_in += wrap ? A.K : 0;
                         tap += 32u * 16u - (wrap ? 4u * (unsigned)HD_SLOT : 0u);
                     }
@@ -282,7 +293,11 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
             const unsigned long long c0 = __builtin_amdgcn_s_memtime();
 #endif
             if constexpr (UNITLEN != 0) {                    // a whole segment of UNITLEN taps: its five row steps in one block
-                if constexpr (PSPLIT)
+                if constexpr (PSPLIT == 2) {                 // (tap row and weight of the older row of group b: those of step b + 1)
+                    const unsigned tapo[4] = {tapv[1], tapv[2], tapv[3], tapv[4]};
+                    const float wov[4] = {alv[1], alv[2], alv[3], alv[4]};
+                    ffa_unitp1_asm<XR, UNITLEN>(accA, accB, accPA, accPB, accPB8, accPP, accB16, xrow4, tapo, wnv, wov);
+                } else if constexpr (PSPLIT)
                     ffa_unitp_asm<XR, UNITLEN>(accA, accB, accPA, accPB, accPB8, accPP, accB16, xrow4, tapv, alv);
                 else if constexpr (NSUB == 4)                // (the weights of a row's subchunks: al + u S / K, formed in the block)
                     ffa_unit4_asm<XR, UNITLEN>(accA, accB, accB16, accP, xrow4, tapv, alv, (float)A.S * A.invK);
@@ -559,7 +574,15 @@ hipError_t bas_fs_launch(const FzArgs &A, const float *x, float *slab, const flo
 #if FZ_ASM
     typedef void (*fs_fn)(FzArgs, const float *, float *, const float *, const unsigned *, float *, unsigned int *);
     const int ul = bas_fs_unit_len(A.Lp);
-#if FS_PSPLIT
+#if FS_PSPLIT && FS_TAPS_ONCE
+    fs_fn fn = ul == 128 ? bas_render_fs_kernel<128, 1, 2> : ul == 104 ? bas_render_fs_kernel<104, 1, 2> : bas_render_fs_kernel<0>;
+#ifdef BAS_DIAG
+    {                                                        // diagnostic build only: the block that reads every tap twice (A/B, tests)
+        const char *once = getenv("BAS_FS_TAPS_ONCE");
+        if (once && atoi(once) == 0 && ul != 0) fn = ul == 128 ? bas_render_fs_kernel<128, 1, 1> : bas_render_fs_kernel<104, 1, 1>;
+    }
+#endif
+#elif FS_PSPLIT
     fs_fn fn = ul == 128 ? bas_render_fs_kernel<128, 1, 1> : ul == 104 ? bas_render_fs_kernel<104, 1, 1> : bas_render_fs_kernel<0>;
 #else
     fs_fn fn = ul == 128 ? bas_render_fs_kernel<128> : ul == 104 ? bas_render_fs_kernel<104> : bas_render_fs_kernel<0>;

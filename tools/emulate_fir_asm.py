@@ -26,8 +26,46 @@ def sel_bits(line, name, default):
     return [int(m.group(i)) for i in (1, 2, 3)] if m else list(default)
 
 
-def run(lines, xr_stride, lseg, nsub=1, psplit=False, seed=0):
-    """Returns (y_block [32, 2], y_direct [32, 2])."""
+def count_lds_reads(lines):
+    """(tap reads, x-row reads) a lane issues in the block"""
+    reads = [ln for ln in lines if ln.startswith("ds_read")]
+    return sum("%[tap" in ln for ln in reads), sum("%[xrow]" in ln for ln in reads)
+
+
+def once_scene(lseg, cross=None, weights=None, x_rows=None, seed=0):
+    """Data of one lane for the block that reads every tap once (gen_fir_asm.py: gen_unit_once): the chunk slots of a real
+    tile instead of independent rows.  The rows of steps 0 .. cross lie in chunk c, the older ones in chunk c - 1 (cross = None:
+    all in one chunk); slot c - 1 holds (h0, d), slot c holds h0 + d and a d of its own: the chunk IRs are continuous across
+    the boundary, as the stagers write them.  Step r reads tap k at row [r, k - 32 r + 32] of its slot.  weights: al per step
+    (default: rising with the row's age inside a chunk, 0 for the row that opens chunk c).  Returns the `scene` of run()."""
+    rng = np.random.default_rng(seed)
+    halo = (lseg + 31) >> 5
+    n_steps = halo + 1
+    x = rng.standard_normal((n_steps, 32)) if x_rows is None else np.asarray(x_rows, dtype=np.float64)
+    h_old, d_old, d_new = (rng.standard_normal((lseg + 64, 2)) for _ in range(3))
+    h_new = h_old + d_old
+    h0, d = np.zeros((n_steps, 64, 2)), np.zeros((n_steps, 64, 2))
+    newer = [cross is not None and r <= cross for r in range(n_steps)]
+    for r in range(n_steps):
+        for t in range(64):
+            k = 32 * r - 32 + t
+            if 0 <= k < lseg:
+                h0[r, t], d[r, t] = (h_new[k], d_new[k]) if newer[r] else (h_old[k], d_old[k])
+    if weights is None:
+        weights = [(cross - r) / 16.0 if newer[r] else 1.0 - (r - (-1 if cross is None else cross)) / 16.0 for r in range(n_steps)]
+    al = np.asarray(weights, dtype=np.float64)
+    operands = {}
+    for b in range(halo):                                      # merged group b: steps b (newer row) and b + 1 (older row)
+        crossing = newer[b] and not newer[b + 1]
+        assert not crossing or al[b] == 0.0                    # the row that opens a chunk has weight 0
+        operands[f"wn{b}"] = 1.0 if crossing else al[b]
+        operands[f"wo{b}"] = al[b + 1]
+    return dict(x=x, h0=h0, d=d, al=al, operands=operands)
+
+
+def run(lines, xr_stride, lseg, nsub=1, psplit=False, seed=0, scene=None):
+    """Returns (y_block [32, 2], y_direct [32, 2]).  scene: x rows, taps, weights and further operands (once_scene) instead of
+    random independent ones."""
     rng = np.random.default_rng(seed)
     halo = (lseg + 31) >> 5
     n_steps = halo + 1
@@ -35,6 +73,8 @@ def run(lines, xr_stride, lseg, nsub=1, psplit=False, seed=0):
     h0 = rng.standard_normal((n_steps, 64, 2))                 # tap t of step r: (h0_L, h0_R), (d_L, d_R); tap k = 32 r - 32 + t
     d = rng.standard_normal((n_steps, 64, 2))
     al = rng.uniform(0, 1, size=n_steps)
+    if scene is not None:
+        x, h0, d, al = scene["x"], scene["h0"], scene["d"], scene["al"]
     dl = 1.0 / 64.0
     bl = al + dl
     v = np.full(256, np.nan)
@@ -44,6 +84,8 @@ def run(lines, xr_stride, lseg, nsub=1, psplit=False, seed=0):
     operands = {f"al{r}": al[r] for r in range(n_steps)}
     operands.update({f"bl{r}": bl[r] for r in range(n_steps)})
     operands["dl"] = dl
+    if scene is not None:
+        operands.update(scene["operands"])
 
     def read(reg, count, at):
         for k in range(reg, reg + count):

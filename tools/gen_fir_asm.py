@@ -212,6 +212,7 @@ def unit_steps(lseg):
 NOFORM = False
 ROLL = 3                        # unit block: rolling x row with this many half-octet tap buffers (0: round 3's two x buffers)
 FMA_KEEP = 8
+TAPS_ONCE_PROBE = False
 SPREAD = 0                      # unit block: LDS reads dealt one by one over the first SPREAD/8 of the FMA run behind them (0: in a burst)
 
 
@@ -471,6 +472,9 @@ def gen_unit_roll(xr_stride, lseg, nsub=1, nbuf=2, psplit=False):
     def tap_reads(n):
         r, i, h = halves[n]
         b = R_T0 + 16 * (n % nbuf)
+        if TAPS_ONCE_PROBE and psplit and r >= 1 and i < 4:     # (probe: this half forms whatever its buffer holds)
+            landed.add(f"t{n}")
+            return []
         return [(f"t{n}", f"ds_read_b128 {quad(b + 4 * j)}, %[tap{r}] offset:{(8 * i + 4 * h + j) * 16}") for j in range(4)]
 
     def form(n, sets):
@@ -553,6 +557,226 @@ def gen_unit_roll(xr_stride, lseg, nsub=1, nbuf=2, psplit=False):
             issue(*t)
     assert not queue, queue
     return L, last
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The P-split unit block with every tap read ONCE (ffa_unitp1_asm, bas_fir_once_asm.inc).  Tap T in [32 b, 32 b + 31] of a
+# segment is met twice by a lane: in octets 4-7 of row step b (x row R - b, the NEWER one) and in octets 0-3 of step b + 1
+# (x row R - b - 1, the OLDER one).  gen_unit_roll reads and forms it in both places.  Both reads fetch the same record
+# (h0, d) while the two rows lie in one chunk; where the pair crosses a chunk boundary the newer row opens chunk c with
+# weight 0 and h0_c = h0_{c-1} + d_{c-1}: the older row's record at weight K / K.  So the block walks MERGED half octets
+# (b, i, h), b = 0 .. halo - 1, i = 0 .. 3: one read of four taps at the older row's slot (operand tap{b+1}: the tap row of
+# step b + 1), two formed sets - N with the weight wn{b} (the newer row's own, or 1.0 in a lane whose pair crosses), O with
+# wo{b} (the older row's own) - and the FMAs of (step b, octet 4 + i, h) on N and of (step b + 1, octet i, h) on O.
+#   * The rolling x row holds both rows at once: merged half m = 2 i + h of a group uses quads 0 .. 7 - m of the newer row
+#     and 7 - m .. 7 of the older.  Quad c = 7 - m is the only one both need: the newer row's FMAs on it go first (right
+#     behind the forming of N), the older row's quad c is read into the same registers behind them, the other ~77 FMAs of
+#     the half run under that read, and the older row's five FMAs on quad c close the half.  No second x buffer, 8 x-quad
+#     reads per group as before.
+#   * ONE half-octet tap buffer: it is free once both sets are formed, the next half's reads go out right there - in one
+#     burst with the x quad - and land under ~77 FMAs.  One wait per half covers all five.
+# Registers: accumulators v[0:115] as gen_unit_roll(psplit), x 32 + sums 16 + 8, taps 16, formed 2 x (12 + 2), weights 2:
+# v[116:217].  Same FMAs per accumulator as ffa_unitp_asm; their order inside an accumulator interleaves the two steps.
+O_X, O_XS, O_XSS, O_T = 116, 148, 164, 172
+O_GN, O_GSSN, O_GO, O_GSSO, O_W = 188, 200, 202, 214, 216
+O_LAST = 217
+
+
+def once_halves(lseg):
+    """merged half octets (b, i, h) of a segment of lseg taps; both partners of a merged octet hold the same taps, so they
+    are live or dead together, and together they are all the live octets of the unit"""
+    steps = unit_steps(lseg)
+    out = []
+    for b in range(len(steps) - 1):
+        for i in range(4):
+            newer, older = steps[b][0] <= 4 + i < steps[b][1], steps[b + 1][0] <= i < steps[b + 1][1]
+            assert newer == older
+            if newer:
+                out += [(b, i, 0), (b, i, 1)]
+    assert len(out) == sum(hi - lo for lo, hi in steps)        # (two half octets per merged octet = one per live octet)
+    assert steps[0][0] >= 4 and steps[-1][1] <= 4              # nothing in front of the first group or behind the last
+    return out
+
+
+def gen_unit_once(xr_stride, lseg):
+    steps = unit_steps(lseg)
+    halo = len(steps) - 1
+    halves = once_halves(lseg)
+    b16 = 114
+    PA0, PB0, PP0 = 64, 80, 98
+    L = []
+
+    def emit(ln):                                               # (sensitivity variants, wrong results: tools/build_fir_variants.sh)
+        if NOWAIT and ln.startswith("s_waitcnt") and L:
+            return
+        if NOTAPS and ln.startswith("ds_read") and "%[tap" in ln:
+            return
+        if NOALIGN and ln.startswith(".p2align"):
+            return
+        L.append(ln)
+    queue, landed = [], set()
+
+    def issue(tag, line):
+        emit(line)
+        queue.append(tag)
+
+    def wait_for(tags):
+        if not any(t in tags for t in queue):
+            return
+        last_ = max(k for k, t in enumerate(queue) if t in tags)
+        n = len(queue) - 1 - last_
+        assert n <= 15, n
+        emit(f"s_waitcnt lgkmcnt({n})")
+        landed.update(queue[:last_ + 1])
+        del queue[:last_ + 1]
+        emit(".p2align 3")
+
+    def fma_list(i, h, g, gss):
+        """[(line, x quad it reads)] of half octet (i, h) of a row step on the formed set g (ge[2], go[2], gs[2]; gss)"""
+        out = []
+        for k in range(2):
+            dk = 4 * i + 2 * h + k - 16
+            for p in range(-1, 16):
+                q = p - dk
+                if not (0 <= q < 16):
+                    continue
+                xp = pr(O_X + 2 * q)
+                if p >= 0:
+                    out.append((f"v_pk_fma_f32 {pr(A0 + 2 * p)}, {pr(g + 2 * k)}, {xp}, {pr(A0 + 2 * p)} op_sel_hi:[1,0,1]", q >> 1))
+                breg = b16 if p + 1 == 16 else B0 + 2 * (p + 1)
+                out.append((f"v_pk_fma_f32 {pr(breg)}, {pr(g + 4 + 2 * k)}, {xp}, {pr(breg)} op_sel:[0,1,0]", q >> 1))
+        j = 2 * i + h - 8                                       # the quarter-rate tap of this half octet (gen_unit_roll: psplit)
+        for r_ in range(-1, 8):
+            t = r_ - j
+            if not (0 <= t < 8):
+                continue
+            xs_pair = pr(O_XS + 2 * t)
+            xss_pair, xss_hi = pr(O_XSS + 2 * (t >> 1)), t & 1
+            if r_ >= 0:
+                out.append((f"v_pk_fma_f32 {pr(PA0 + 2 * r_)}, {pr(g + 8)}, {xs_pair}, {pr(PA0 + 2 * r_)} op_sel_hi:[1,0,1]", t))
+                sel = "op_sel:[0,1,0]" if xss_hi else "op_sel_hi:[1,0,1]"
+                out.append((f"v_pk_fma_f32 {pr(PP0 + 2 * r_)}, {pr(gss)}, {xss_pair}, {pr(PP0 + 2 * r_)} {sel}", t))
+            out.append((f"v_pk_fma_f32 {pr(PB0 + 2 * (r_ + 1))}, {pr(g + 10)}, {xs_pair}, {pr(PB0 + 2 * (r_ + 1))} op_sel:[0,1,0]", t))
+        return out
+
+    def form(g, gss, wsel):
+        for k in range(2):
+            te, to = O_T + 4 * (2 * k), O_T + 4 * (2 * k + 1)
+            emit(f"v_pk_fma_f32 {pr(g + 2 * k)}, {pr(te + 2)}, {pr(O_W)}, {pr(te)} {wsel}")
+            emit(f"v_pk_fma_f32 {pr(g + 4 + 2 * k)}, {pr(to + 2)}, {pr(O_W)}, {pr(to)} {wsel}")
+        for k in range(2):
+            emit(f"v_pk_add_f32 {pr(g + 8 + 2 * k)}, {pr(g + 2 * k)}, {pr(g + 4 + 2 * k)}")
+        emit(f"v_pk_add_f32 {pr(gss)}, {pr(g + 8)}, {pr(g + 10)}")
+
+    def x_read(r, c):
+        return (f"x{r}.{c}", f"ds_read_b128 {quad(O_X + 4 * c)}, %[xrow] offset:{(halo - r) * 16 + c * xr_stride * 16}")
+
+    def tap_reads(n):
+        b, i, h = halves[n]
+        return [(f"t{n}", f"ds_read_b128 {quad(O_T + 4 * j)}, %[tap{b + 1}] offset:{(8 * i + 4 * h + j) * 16}") for j in range(4)]
+
+    def sums(c):
+        for q in (2 * c, 2 * c + 1):
+            emit(f"v_add_f32_e64 v{O_XS + q}, v{O_X + 2 * q}, v{O_X + 2 * q + 1}")
+        emit(f"v_add_f32_e64 v{O_XSS + c}, v{O_XS + 2 * c}, v{O_XS + 2 * c + 1}")
+
+    row_in = {}                                                 # x quad -> the row step whose row it holds (sums formed)
+
+    def lines_on(lst, r):
+        for ln, c in lst:
+            assert row_in.get(c) == r, (ln, c, r, row_in)       # the quad holds this step's row, landed and summed
+            emit(ln)
+
+    emit("s_waitcnt lgkmcnt(0)")                               # (scalar loads of the code around the block return out of order)
+    emit(".p2align 3")
+    first = sorted({c for n, (b, i, h) in enumerate(halves) if b == 0 for _, c in fma_list(4 + i, h, O_GN, O_GSSN)})
+    for c in first:
+        issue(*x_read(0, c))
+    for t in tap_reads(0):
+        issue(*t)
+    wait_for([f"x0.{c}" for c in first] + ["t0"])
+    for c in first:
+        sums(c)
+        row_in[c] = 0
+    for n, (b, i, h) in enumerate(halves):
+        newer, older = fma_list(4 + i, h, O_GN, O_GSSN), fma_list(i, h, O_GO, O_GSSO)
+        both = {c for _, c in newer} & {c for _, c in older}
+        assert len(both) == 1, both                             # the one quad the two rows share in this half
+        cx = both.pop()
+        assert f"t{n}" in landed
+        if n == 0 or halves[n - 1][0] != b:                    # first half of a group: its two weights, (newer, older)
+            emit(f"v_mov_b32_e64 v{O_W}, %[wn{b}]")
+            emit(f"v_mov_b32_e64 v{O_W + 1}, %[wo{b}]")
+        form(O_GN, O_GSSN, "op_sel_hi:[1,0,1]")
+        lines_on([(ln, c) for ln, c in newer if c == cx], b)
+        form(O_GO, O_GSSO, "op_sel:[0,1,0] op_sel_hi:[1,1,1]")
+        # ONE burst of reads per half (reads behind each other pipeline, a lone read between FMAs costs the next FMA its slot:
+        # DESIGN.md 4.0): the next half's taps - the tap buffer is free, both sets are formed - and the older row's quad cx,
+        # behind the newer row's last use of it
+        if n + 1 < len(halves):
+            for t in tap_reads(n + 1):
+                issue(*t)
+        issue(*x_read(b + 1, cx))
+        del row_in[cx]
+        lines_on([(ln, c) for ln, c in newer if c != cx], b)
+        lines_on([(ln, c) for ln, c in older if c != cx], b + 1)
+        wait_for([f"t{n + 1}", f"x{b + 1}.{cx}"])
+        assert f"x{b + 1}.{cx}" in landed
+        sums(cx)
+        row_in[cx] = b + 1
+        lines_on([(ln, c) for ln, c in older if c == cx], b + 1)
+    assert not queue, queue
+    return L, O_LAST
+
+
+UNITP1_HEAD = """// GENERATED by tools/gen_fir_asm.py - do not edit (see that file: gen_unit_once).
+// The split-role kernel's unit block with every tap read once and formed for both x rows that meet it.
+#pragma once
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+template <int XR, int LSEG>
+__device__ __forceinline__ void ffa_unitp1_asm(f32x32 &accA, f32x32 &accB, f32x16 &accPA, f32x16 &accPB, f32x2 &accPB8, f32x16 &accPP,
+                                                f32x2 &accB16, unsigned xrow4, const unsigned (&tapo)[4], const float (&wn)[4],
+                                                const float (&wo)[4]);
+"""
+
+UNITP1_FUNC = """
+// One (tile, source) unit of a {lseg}-tap segment, P split as in ffa_unitp_asm, taps read once: {n_fma} v_pk_fma_f32, {n_ds} ds_read_b128
+// ({n_tap} of them taps), {n_wait} waits.  Merged group b = octets 4-7 of row step b and octets 0-3 of step b + 1: tapo[b] = tap row
+// address of step b + 1 (the older row's slot), wn[b] = weight of step b (1.0 where the two rows lie in different chunks),
+// wo[b] = weight of step b + 1.  xrow4 as in ffa_unit_asm.
+template <>
+__device__ __forceinline__ void ffa_unitp1_asm<{xr}, {lseg}>(f32x32 &accA, f32x32 &accB, f32x16 &accPA, f32x16 &accPB, f32x2 &accPB8,
+                                                f32x16 &accPP, f32x2 &accB16, unsigned xrow4, const unsigned (&tapo)[4],
+                                                const float (&wn)[4], const float (&wo)[4]) {{
+    asm volatile(
+{body}
+        : "+{{v[0:31]}}"(accA), "+{{v[32:63]}}"(accB), "+{{v[64:79]}}"(accPA), "+{{v[80:95]}}"(accPB), "+{{v[96:97]}}"(accPB8),
+          "+{{v[98:113]}}"(accPP), "+{{v[114:115]}}"(accB16)
+        : [xrow] "v"(xrow4), [tap1] "v"(tapo[0]), [tap2] "v"(tapo[1]), [tap3] "v"(tapo[2]), [tap4] "v"(tapo[3]),
+          [wn0] "v"(wn[0]), [wn1] "v"(wn[1]), [wn2] "v"(wn[2]), [wn3] "v"(wn[3]),
+          [wo0] "v"(wo[0]), [wo1] "v"(wo[1]), [wo2] "v"(wo[2]), [wo3] "v"(wo[3])
+        : "memory", {clob});
+}}
+"""
+
+
+def once_text():
+    text = UNITP1_HEAD
+    for lseg in U_LSEGS:
+        ul, u_last = gen_unit_once(261, lseg)
+        text += UNITP1_FUNC.format(xr=261, lseg=lseg, body="\n".join(f'        "{ln}\\n\\t"' for ln in ul),
+                                   clob=", ".join(f'"v{r}"' for r in range(O_X, u_last + 1)),
+                                   n_fma=sum(1 for ln in ul if ln.startswith("v_pk_fma")),
+                                   n_ds=sum(1 for ln in ul if ln.startswith("ds_read")),
+                                   n_tap=sum(1 for ln in ul if ln.startswith("ds_read") and "%[tap" in ln),
+                                   n_wait=sum(1 for ln in ul if ln.startswith("s_waitcnt")))
+    return text
+
+
+def once_path(out):
+    """the second generated file lies beside the first: bas_fir_asm.inc -> bas_fir_once_asm.inc, ab_NAME.inc -> ab_NAME_once.inc"""
+    d, f = os.path.split(out)
+    return os.path.join(d, "bas_fir_once_asm.inc" if f == "bas_fir_asm.inc" else f[:-4] + "_once.inc")
 
 
 UNIT_DECL = """
@@ -647,8 +871,11 @@ def main():
     # diagnostic variants (wrong results; tools/ubench_lone_wave.hip): --nowait no waits for the LDS reads, --nobranch no octet
     # masks (all live), --notaps no tap reads, --noalign no alignment padding, --nox no x-row reads; --out=FILE
     global NOWAIT, NOBRANCH, NOTAPS, NOALIGN, NOX, OUT, GENERIC_ONLY, ONE_WAIT, SPREAD, NOFORM, FMA_KEEP
-    global ROLL
+    global ROLL, TAPS_ONCE_PROBE
     NOFORM = "--noform" in sys.argv[1:]
+    # (the ceiling of gen_unit_once, measured on the block it replaces: ffa_unitp_asm without the tap reads of octets 0-3 of
+    # steps 1 .. - the second read of every tap; wrong results)
+    TAPS_ONCE_PROBE = "--taps-once-probe" in sys.argv[1:]
     for a in sys.argv[1:]:
         if a.startswith("--roll="):                             # (A/B: the rolling-x unit block with this many tap buffers)
             ROLL = int(a[7:])
@@ -708,12 +935,20 @@ def main():
                                   n_fma=sum(1 for ln in ul if ln.startswith("v_pk_fma")),
                                   n_ds=sum(1 for ln in ul if ln.startswith("ds_read")),
                                   n_wait=sum(1 for ln in ul if ln.startswith("s_waitcnt")))
+    once = once_text() if 261 in xrs and not GENERIC_ONLY else None      # the second file: the unit block that reads every tap once
     if check:
         same = os.path.exists(OUT) and open(OUT).read() == text
         print(f"{OUT}: {'up to date' if same else 'DIFFERS from what the generator writes'}")
-        sys.exit(0 if same else 1)
-    with open(OUT, "w") as f:
-        f.write(text)
+        # (the second file is a build product - the Makefile writes it, git does not track it: checked where it exists)
+        built = once is not None and os.path.exists(once_path(OUT))
+        same1 = not built or open(once_path(OUT)).read() == once
+        if once is not None:
+            print(f"{once_path(OUT)}: {'not built yet' if not built else 'up to date' if same1 else 'DIFFERS from what the generator writes'}")
+        sys.exit(0 if same and same1 else 1)
+    for path, body in ((OUT, text), (once_path(OUT), once)):
+        if body is not None and not (os.path.exists(path) and open(path).read() == body):    # (a file that is right stays untouched)
+            with open(path, "w") as f:
+                f.write(body)
     print(f"{OUT}: {len(lines)} lines per variant, {n_fma} packed FMAs")
 
 
