@@ -132,6 +132,17 @@ SIGNATURES = {
                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_int, _c_int,
                                       _c_int, _c_void_p, _c_void_p, _c_void_p, _c_long, _c_long, _c_void_p, _c_long,
                                       _c_long, _c_void_p]),
+    # scene colour: air absorption and directivity
+    "bas_scene_params_bands_f64": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long,
+                                            ctypes.c_double, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long,
+                                            _c_void_p, _c_long, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_int,
+                                            _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long,
+                                            _c_void_p, _c_void_p, _c_int, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p,
+                                            _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long,
+                                            _c_long, _c_void_p]),
+    "bas_color_design_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_int, _c_int, ctypes.c_double,
+                                      _c_int, _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_long, _c_void_p]),
     # late reverberation
     "bas_bus_mix_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_int, _c_long,
                                  _c_int, _c_void_p, _c_long, _c_void_p]),

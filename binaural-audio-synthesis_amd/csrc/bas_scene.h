@@ -8,6 +8,7 @@
 
 struct BasScenePoint {
     double el, az, gain, delay;
+    double r, cos_theta;        // path length and emission angle's cosine (directed only)
 };
 
 // p: the source, l: the listener (world frame, metres).  room: L = the shoebox's size and m = the image's index per axis
@@ -18,12 +19,18 @@ struct BasScenePoint {
 // moving: the source is heard where it was when the sound left it.  (ax, ay, az) and (bx, by, bz) are its positions one
 // chunk of spc samples apart around this boundary; the image moves at u = (q(b) - q(a)) / spc per sample, and the delay d
 // that solves |q - u d - l| = d / spm (a quadratic; subsonic u only, else no correction) puts it at q - u d for steps 2-6.
+// directed (bas_scene_params_bands_f64 only): o = (ow, ox, oy, oz) turns the source's frame into the world frame, any
+// non-zero norm; the source radiates along its local +y, f = R(o / |o|) (0, 1, 0); an image's axis is f with component a
+// negated where m_a is odd; cos_theta = f . (l - q) / r for the q of steps 2-6 (r == 0: 1), r unclamped.  The other four
+// results do not depend on it.
 __device__ __forceinline__ BasScenePoint bas_scene_point(double px, double py, double pz, double lx, double ly, double lz,
                                                          bool moving, double ax, double ay, double az_, double bx, double by,
                                                          double bz, double spc,
                                                          bool room, double Lx, double Ly, double Lz, int mx, int my, int mz,
                                                          bool head, double w, double x, double y, double z, double sgain,
-                                                         double igain, double spm, double r_ref, double dmin, double dmax) {
+                                                         double igain, double spm, double r_ref, double dmin, double dmax,
+                                                         bool directed = false, double ow = 1.0, double ox = 0.0,
+                                                         double oy = 0.0, double oz = 0.0) {
 #pragma clang fp contract(off)
     if (room) {
         px = (double)mx * Lx + ((mx & 1) ? Lx - px : px);
@@ -62,5 +69,20 @@ __device__ __forceinline__ BasScenePoint bas_scene_point(double px, double py, d
     o.az = at_listener ? 0.0 : atan2(-vx, vy);
     o.gain = sgain * igain * r_ref / fmax(r, r_ref);
     o.delay = fmax(fmin(r * spm, dmax), dmin);
+    o.r = r;
+    o.cos_theta = 1.0;
+    if (directed) {
+        const double n = sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
+        ow = ow / n; ox = ox / n; oy = oy / n; oz = oz / n;
+        double fx = 2.0 * (ox * oy - ow * oz), fy = 1.0 - 2.0 * (ox * ox + oz * oz), fz = 2.0 * (oy * oz + ow * ox);
+        if (room) {
+            if (mx & 1) fx = -fx;
+            if (my & 1) fy = -fy;
+            if (mz & 1) fz = -fz;
+        }
+        // (v of step 2, before the head turned it: px - lx is q - l, and the emission runs the other way)
+        const double dot = fx * (px - lx) + fy * (py - ly) + fz * (pz - lz);
+        o.cos_theta = r == 0.0 ? 1.0 : -dot / r;
+    }
     return o;
 }

@@ -5,7 +5,10 @@
 #include "bas_internal.h"
 #include "bas_scene.h"
 
+#include <string.h>
+
 #define SC_THREADS 256
+#define SC_MAX_BANDS 16
 
 struct BasSceneArgs {
     const double *pos; long ps_g, ps_s, ps_c;
@@ -19,9 +22,18 @@ struct BasSceneArgs {
     int n_src, n_img, nb;
     double *elev, *azim, *gain; long a_g, a_s;
     double *delay; long d_g, d_s;
+    // bas_scene_params_bands_f64 only: the per-band log-magnitudes of every (row, boundary)
+    const double *orient; long o_g, o_s, o_c;
+    const double *pattern; long pt_s;
+    const double *air, *img_logmag;
+    int n_bands; double floor;
+    double *logmag; long l_g, l_s, l_c;
 };
 
-// one thread per (g, s, i, c) item, c fastest (the stores of a wave are consecutive along c), grid-stride
+// one thread per (g, s, i, c) item, c fastest (the stores of a wave are consecutive along c), grid-stride.  BANDS: the
+// item's n_bands log-magnitudes follow, L[b] = ln W_i[b] - air[b] r + ln max(|a_b + (1 - a_b) cos theta|, floor), floored
+// at ln floor, n_bands consecutive doubles per thread (the threads of a wave tile a consecutive range where l_c = n_bands)
+template <bool BANDS>
 __global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneArgs A, long n_items) {
     const long per_s = (long)A.n_img * A.nb, per_g = per_s * A.n_src;
     const bool room = A.room_size != nullptr;
@@ -59,10 +71,29 @@ __global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneAr
             else b = p + A.ps_c;
         }
         const double sg = A.src_gain ? A.src_gain[g * A.sg_g + s * A.sg_s + c] : 1.0;
+        double ow = 1.0, ox = 0.0, oy = 0.0, oz = 0.0;
+        if (BANDS && A.orient) {
+            const double *q = A.orient + g * A.o_g + s * A.o_s + c * A.o_c;
+            ow = q[0]; ox = q[1]; oy = q[2]; oz = q[3];
+        }
         const BasScenePoint o = bas_scene_point(p[0], p[1], p[2], lx, ly, lz, moving, a[0], a[1], a[2], b[0], b[1],
                                                 b[2], A.spc, room, Lx, Ly, Lz, mx, my, mz, A.head != nullptr,
-                                                w, x, y, z, sg, ig, A.spm, A.r_ref, A.dmin, A.dmax);
+                                                w, x, y, z, sg, ig, A.spm, A.r_ref, A.dmin, A.dmax, BANDS, ow, ox, oy, oz);
         const long row = s * A.n_img + i;
+        if (BANDS) {
+#pragma clang fp contract(off)
+            double *L = A.logmag + g * A.l_g + row * A.l_s + c * A.l_c;
+            const double ln_floor = log(A.floor);
+            for (int bd = 0; bd < A.n_bands; ++bd) {
+                double v = A.img_logmag ? A.img_logmag[i * A.n_bands + bd] : 0.0;
+                if (A.air) v = v - A.air[bd] * o.r;
+                if (A.pattern) {
+                    const double al = A.pattern[s * A.pt_s + bd];
+                    v = v + log(fmax(fabs(al + (1.0 - al) * o.cos_theta), A.floor));
+                }
+                L[bd] = fmax(v, ln_floor);
+            }
+        }
         const long to = g * A.a_g + row * A.a_s + c;
         A.elev[to] = o.el;
         A.azim[to] = o.az;
@@ -76,17 +107,25 @@ static bool sc_one_to_one(long G, long rows, long nb, long sg, long ss) { return
 
 static bool sc_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
-extern "C" int bas_scene_params_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
-                                    const double *pos_prev, long prev_stride_g, long prev_stride_s,
-                                    double samples_per_chunk, const double *lpos, long lpos_stride_g,
-                                    long lpos_stride_c, const double *head,
-                                    long head_stride_g, long head_stride_c, const double *src_gain, long sg_stride_g,
-                                    long sg_stride_s, const double *room_size, const int32_t *images,
-                                    const double *img_gain, int n_img, double samples_per_metre, double r_ref,
-                                    double d_min, double d_max, int n_groups, int n_src, int nb, double *elev,
-                                    double *azim, double *gain, long a_stride_g, long a_stride_s, double *delay,
-                                    long d_stride_g, long d_stride_s, bas_stream_t stream) {
-    const char *fn = "bas_scene_params_f64";
+// what bas_scene_params_bands_f64 adds to the argument list
+struct BasSceneBands {
+    const double *orient; long o_g, o_s, o_c;
+    const double *pattern; long pt_s;
+    const double *air, *img_logmag;
+    int n_bands; double floor;
+    double *logmag; long l_g, l_s, l_c;
+};
+
+// The launcher both entry points share (B == nullptr: bas_scene_params_f64, the kernel without the bands): every check,
+// then one launch.
+static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                     const double *pos_prev, long prev_stride_g, long prev_stride_s, double samples_per_chunk,
+                     const double *lpos, long lpos_stride_g, long lpos_stride_c, const double *head, long head_stride_g,
+                     long head_stride_c, const double *src_gain, long sg_stride_g, long sg_stride_s,
+                     const double *room_size, const int32_t *images, const double *img_gain, int n_img,
+                     double samples_per_metre, double r_ref, double d_min, double d_max, int n_groups, int n_src, int nb,
+                     double *elev, double *azim, double *gain, long a_stride_g, long a_stride_s, double *delay,
+                     long d_stride_g, long d_stride_s, const BasSceneBands *B, bas_stream_t stream) {
     BAS_REQUIRE(n_groups > 0 && n_src > 0 && nb > 0 && n_img > 0, BAS_E_SHAPE,
                 "%s: need n_groups, n_src, nb, n_img > 0 (G=%d n_src=%d nb=%d n_img=%d)", fn, n_groups, n_src, nb, n_img);
     BAS_REQUIRE((long)n_src * n_img <= 0x7fffffffL, BAS_E_SHAPE, "%s: n_src n_img must be below 2^31", fn);
@@ -117,6 +156,35 @@ extern "C" int bas_scene_params_f64(const double *pos, long pos_stride_g, long p
                 sc_aligned(azim, 8) && sc_aligned(gain, 8) && sc_aligned(delay, 8), BAS_E_ALIGN,
                 "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
     BasSceneArgs A;
+    memset(&A, 0, sizeof A);
+    if (B) {
+        BAS_REQUIRE(B->n_bands >= 1 && B->n_bands <= SC_MAX_BANDS, BAS_E_SHAPE, "%s: n_bands (%d) must be in 1..%d", fn,
+                    B->n_bands, SC_MAX_BANDS);
+        BAS_REQUIRE(B->floor > 0.0 && B->floor <= 1.0, BAS_E_SHAPE, "%s: the floor (%g) must be in (0, 1]", fn, B->floor);
+        BAS_REQUIRE(B->o_g >= 0 && B->o_s >= 0 && B->o_c >= 0 && B->pt_s >= 0, BAS_E_SHAPE,
+                    "%s: input strides must be non-negative", fn);
+        BAS_REQUIRE(B->pt_s == 0 || B->pt_s >= B->n_bands, BAS_E_SHAPE,
+                    "%s: the pattern's source stride must be 0 (shared) or >= n_bands", fn);
+        // [G][rows][nb][n_bands] with strides (l_g, l_s, l_c, 1): a boundary's bands must not meet the next one's, and the
+        // rows' extents (nb - 1) l_c + n_bands are held to the rule of the other outputs
+        long extent = 0;
+        BAS_REQUIRE(B->l_g >= 0 && B->l_s >= 0 && B->l_c >= B->n_bands &&
+                    !__builtin_mul_overflow((long)(nb - 1), B->l_c, &extent) &&
+                    !__builtin_add_overflow(extent, (long)B->n_bands, &extent) &&
+                    sc_one_to_one(n_groups, rows, extent, B->l_g, B->l_s), BAS_E_SHAPE,
+                    "%s: logmag output strides (%ld, %ld, %ld, 1) overlap for [%d][%ld][%d][%d]", fn, B->l_g, B->l_s, B->l_c,
+                    n_groups, rows, nb, B->n_bands);
+        BAS_REQUIRE(B->logmag, BAS_E_NULL, "%s: null pointer", fn);
+        BAS_REQUIRE((void *)B->logmag != elev && (void *)B->logmag != azim && (void *)B->logmag != gain &&
+                    (void *)B->logmag != delay, BAS_E_SHAPE, "%s: two outputs are one buffer", fn);
+        BAS_REQUIRE(sc_aligned(B->orient, 8) && sc_aligned(B->pattern, 8) && sc_aligned(B->air, 8) &&
+                    sc_aligned(B->img_logmag, 8) && sc_aligned(B->logmag, 8), BAS_E_ALIGN,
+                    "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
+        A.orient = B->orient; A.o_g = B->o_g; A.o_s = B->o_s; A.o_c = B->o_c;
+        A.pattern = B->pattern; A.pt_s = B->pt_s; A.air = B->air; A.img_logmag = B->img_logmag;
+        A.n_bands = B->n_bands; A.floor = B->floor;
+        A.logmag = B->logmag; A.l_g = B->l_g; A.l_s = B->l_s; A.l_c = B->l_c;
+    }
     A.pos = pos; A.ps_g = pos_stride_g; A.ps_s = pos_stride_s; A.ps_c = pos_stride_c;
     A.prev = pos_prev; A.pp_g = prev_stride_g; A.pp_s = prev_stride_s; A.spc = samples_per_chunk;
     A.lpos = lpos; A.lp_g = lpos_stride_g; A.lp_c = lpos_stride_c;
@@ -129,6 +197,48 @@ extern "C" int bas_scene_params_f64(const double *pos, long pos_stride_g, long p
     A.delay = delay; A.d_g = d_stride_g; A.d_s = d_stride_s;
     const long n_items = (long)n_groups * rows * nb;
     const int blocks = bas_grid_for(n_items, 8 * bas_device_cus());
-    hipLaunchKernelGGL(bas_scene_params_kernel, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
-    return bas_check_launch("bas_scene_params_f64");
+    if (B)
+        hipLaunchKernelGGL(bas_scene_params_kernel<true>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
+    else
+        hipLaunchKernelGGL(bas_scene_params_kernel<false>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
+    return bas_check_launch(fn);
+}
+
+extern "C" int bas_scene_params_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                                    const double *pos_prev, long prev_stride_g, long prev_stride_s,
+                                    double samples_per_chunk, const double *lpos, long lpos_stride_g,
+                                    long lpos_stride_c, const double *head,
+                                    long head_stride_g, long head_stride_c, const double *src_gain, long sg_stride_g,
+                                    long sg_stride_s, const double *room_size, const int32_t *images,
+                                    const double *img_gain, int n_img, double samples_per_metre, double r_ref,
+                                    double d_min, double d_max, int n_groups, int n_src, int nb, double *elev,
+                                    double *azim, double *gain, long a_stride_g, long a_stride_s, double *delay,
+                                    long d_stride_g, long d_stride_s, bas_stream_t stream) {
+    return sc_launch("bas_scene_params_f64", pos, pos_stride_g, pos_stride_s, pos_stride_c, pos_prev, prev_stride_g,
+                     prev_stride_s, samples_per_chunk, lpos, lpos_stride_g, lpos_stride_c, head, head_stride_g,
+                     head_stride_c, src_gain, sg_stride_g, sg_stride_s, room_size, images, img_gain, n_img,
+                     samples_per_metre, r_ref, d_min, d_max, n_groups, n_src, nb, elev, azim, gain, a_stride_g, a_stride_s,
+                     delay, d_stride_g, d_stride_s, nullptr, stream);
+}
+
+extern "C" int bas_scene_params_bands_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                                          const double *pos_prev, long prev_stride_g, long prev_stride_s,
+                                          double samples_per_chunk, const double *lpos, long lpos_stride_g,
+                                          long lpos_stride_c, const double *head, long head_stride_g, long head_stride_c,
+                                          const double *src_gain, long sg_stride_g, long sg_stride_s,
+                                          const double *room_size, const int32_t *images, const double *img_gain,
+                                          int n_img, double samples_per_metre, double r_ref, double d_min, double d_max,
+                                          int n_groups, int n_src, int nb, const double *orient, long orient_stride_g,
+                                          long orient_stride_s, long orient_stride_c, const double *pattern,
+                                          long pattern_stride_s, const double *air, const double *img_logmag, int n_bands,
+                                          double floor, double *elev, double *azim, double *gain, long a_stride_g,
+                                          long a_stride_s, double *delay, long d_stride_g, long d_stride_s, double *logmag,
+                                          long l_stride_g, long l_stride_s, long l_stride_c, bas_stream_t stream) {
+    const BasSceneBands B = {orient, orient_stride_g, orient_stride_s, orient_stride_c, pattern, pattern_stride_s, air,
+                             img_logmag, n_bands, floor, logmag, l_stride_g, l_stride_s, l_stride_c};
+    return sc_launch("bas_scene_params_bands_f64", pos, pos_stride_g, pos_stride_s, pos_stride_c, pos_prev, prev_stride_g,
+                     prev_stride_s, samples_per_chunk, lpos, lpos_stride_g, lpos_stride_c, head, head_stride_g,
+                     head_stride_c, src_gain, sg_stride_g, sg_stride_s, room_size, images, img_gain, n_img,
+                     samples_per_metre, r_ref, d_min, d_max, n_groups, n_src, nb, elev, azim, gain, a_stride_g, a_stride_s,
+                     delay, d_stride_g, d_stride_s, &B, stream);
 }

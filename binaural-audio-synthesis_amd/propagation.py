@@ -346,3 +346,91 @@ def min_phase_fir(freqs, mags, fs, taps):
     fold[1:N // 2] = 2.0 * cep[1:N // 2]                               # causal part doubled: the minimum-phase cepstrum
     h = np.fft.irfft(np.exp(np.fft.rfft(fold)), N)
     return h[:taps].copy()
+
+
+# ---- colour designed from band log-magnitudes, at every boundary ------------------------------------
+# min_phase_fir's interpolation over log-frequency is linear in the band log-magnitudes L[b] = ln |H(f_b)|, and so is the
+# cepstrum: c[0 .. M) = sum_b L[b] basis[b], with basis[b] the folded cepstrum of band b's interpolation weight (a hat over
+# log-frequency, flat outside the outer bands).  The first M taps of exp of a causal cepstrum follow without an FFT:
+#     h[0] = exp(c[0]),  h[n] = (1 / n) sum_{k=1..n} k c[k] h[n - k]
+# which is exact for the infinite response (min_phase_fir's differs by the time aliasing of its FIR_GRID-point FFTs).
+MAX_BANDS = 16
+
+
+def cepstral_basis(bands, fs, taps):
+    """The basis of the linear map from band log-magnitudes to the minimum-phase cepstrum: float64 [n_bands, taps], row b
+    the first `taps` folded cepstrum coefficients (c0 = cep[0], c[k] = 2 cep[k]) of band b's interpolation weight on
+    min_phase_fir's grid (FIR_GRID bins, linear over log-frequency, flat outside the bands).  bands, fs, taps: validated as
+    min_phase_fir validates them (ValueError)."""
+    f = np.asarray(bands, dtype=np.float64).reshape(-1)
+    taps, fs = int(taps), float(fs)
+    if f.size < 1 or not np.isfinite(f).all() or not (f > 0).all() or not (np.diff(f) > 0).all():
+        raise ValueError("bands must be ascending band centres > 0")
+    if not 1 <= taps <= FIR_GRID // 2 or not (np.isfinite(fs) and fs > 0):
+        raise ValueError(f"taps must be in 1..{FIR_GRID // 2} and fs > 0")
+    N = FIR_GRID
+    grid = np.log(np.maximum(np.arange(N // 2 + 1, dtype=np.float64) * (fs / N), 1e-300))
+    out = np.empty((f.size, taps))
+    for b in range(f.size):
+        cep = np.fft.irfft(np.interp(grid, np.log(f), np.eye(f.size)[b]), N)
+        out[b] = 2.0 * cep[:taps]
+        out[b, 0] = cep[0]
+    return out
+
+
+def min_phase_from_logmag(logmag, basis):
+    """The float64 definition of the device's design (bas_color_design_f32).  logmag: [..., n_bands] natural
+    log-magnitudes at the band centres; basis: cepstral_basis(bands, fs, taps).  Each band is floored at ln FIR_FLOOR,
+    c = logmag @ basis, then the recursion above.  Returns float64 [..., taps]: what min_phase_fir returns for
+    exp(logmag), up to the aliasing of its FFTs."""
+    B = np.asarray(basis, dtype=np.float64)
+    L = np.asarray(logmag, dtype=np.float64)
+    if B.ndim != 2 or L.ndim < 1 or L.shape[-1] != B.shape[0]:
+        raise ValueError(f"logmag must be [..., n_bands] and basis [n_bands, taps], got {L.shape} and {B.shape}")
+    M = B.shape[1]
+    c = np.maximum(L, np.log(FIR_FLOOR)) @ B
+    kc = c * np.arange(M)
+    h = np.zeros(c.shape)
+    h[..., 0] = np.exp(c[..., 0])
+    for n in range(1, M):
+        h[..., n] = (kc[..., 1:n + 1] * h[..., n - 1::-1][..., :n]).sum(axis=-1) / n
+    return h
+
+
+def design_colors_device(logmag, basis, out=None):
+    """One bas_color_design_f32 launch: logmag float64 device tensor [(G,) rows, nb, n_bands] (unit stride along the
+    bands, any other strides >= 0), basis [n_bands, M] (cepstral_basis: a host array, uploaded, or a float64 device tensor)
+    -> float32 [(G,) rows, nb, M], the taps bas_color_rows_f32 reads in its per-boundary form.  out: None, or a float32
+    device tensor of that shape with the taps contiguous - a StreamRenderer's color_view(B) is taken in place.  ValueError
+    for other shapes or dtypes, before any device work."""
+    import torch
+    if not (isinstance(logmag, torch.Tensor) and logmag.is_cuda and logmag.dtype == torch.float64 and logmag.dim() in (3, 4)):
+        raise ValueError("logmag must be a float64 device tensor [(G,) rows, nb, n_bands]")
+    dev = logmag.device
+    n_bands = int(logmag.shape[-1])
+    on_dev = isinstance(basis, torch.Tensor) and basis.is_cuda
+    bshape = tuple(basis.shape) if on_dev else np.shape(basis)
+    if len(bshape) != 2 or bshape[0] != n_bands or not 1 <= n_bands <= MAX_BANDS or not 1 <= bshape[1] <= MAX_TAPS:
+        raise ValueError(f"basis must be [{n_bands}, M] with 1 <= M <= {MAX_TAPS} and at most {MAX_BANDS} bands, got {bshape}")
+    if on_dev and basis.dtype != torch.float64:
+        raise ValueError("a device basis must be float64")
+    M = int(bshape[1])
+    shape = tuple(logmag.shape[:-1]) + (M,)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.float32
+                                and tuple(out.shape) == shape and out.stride(-1) == 1
+                                and all(s >= 0 for s in out.stride())):
+        raise ValueError(f"out must be a float32 tensor of shape {shape} on {dev} with contiguous taps")
+    if min(shape) < 1:
+        raise ValueError("logmag must hold at least one row and boundary")
+    bt = basis.to(dev).contiguous() if on_dev else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(basis, dtype=np.float64))).to(dev)
+    lm = logmag if logmag.stride(-1) == 1 and all(s >= 0 for s in logmag.stride()) else logmag.contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    batched = logmag.dim() == 4
+    G = shape[0] if batched else 1
+    with _hip.on_device(dev):
+        _hip.call("bas_color_design_f32", _hip.ptr(lm), lm.stride(0) if batched else 0, lm.stride(-3), lm.stride(-2),
+                  _hip.ptr(bt), n_bands, M, float(np.log(FIR_FLOOR)), G, shape[-3], shape[-2], _hip.ptr(out),
+                  out.stride(0) if batched else 0, out.stride(-3), out.stride(-2), _hip.current_stream(dev))
+    return out

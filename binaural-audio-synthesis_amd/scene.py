@@ -30,6 +30,11 @@ Walls reflect all frequencies alike (one coefficient per wall) unless the room h
 reflection magnitude per frequency band, every image a short minimum-phase FIR designed from the product of the walls it
 met (Room.image_filters), and one colour launch (§3.13) filters every image's delayed input.  The image model holds for
 rigid or nearly rigid walls.
+A `SceneColor` (§3.18) adds what changes with the geometry at every boundary: air absorption over the path length r and the
+source's directivity towards the listener (sources have an orientation, `orient`, which the walls mirror).  The scene
+kernel then also writes every row's band log-magnitudes (`scene_color_params`: the definition; bas_scene_params_bands_f64),
+and a second launch designs a minimum-phase FIR per (row, boundary) from them (propagation.design_colors_device), which the
+colour launch applies in its per-boundary form; a banded room's walls are then among the log-magnitudes.
 """
 import numpy as np
 
@@ -247,6 +252,12 @@ def scene_params(pos, fs, listener_pos=None, head=None, room=None, src_gain=None
     correction); pos_prev (..., n_src, 3): the sources' positions one chunk before the first boundary, or None.
     Returns (elev, azim, gain, delay), float64 (..., n_src n_img, nb), row s n_img + i for image i of source s.
     ValueError for non-finite values, wrong shapes, zero-norm heads and, with a room, positions outside it."""
+    return _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, chunksize, pos_prev)[:4]
+
+
+def _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, chunksize, pos_prev):
+    """scene_params' body; returns its four arrays and, for scene_color_params, the path length r and the vector v = q - l
+    of step 2 (before the head turns it), float64 (..., n_src, n_img, nb) and (..., n_src, n_img, nb, 3)."""
     spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
     if any(_is_device(a) for a in (pos, listener_pos, head, src_gain)):
         raise ValueError("scene_params takes host arrays (scene_params_device takes device tensors)")
@@ -300,7 +311,162 @@ def scene_params(pos, fs, listener_pos=None, head=None, room=None, src_gain=None
     gain = sg * ig * r_ref / np.fmax(r, r_ref)
     delay = np.fmax(np.fmin(r * spm, d_max), d_min)
     shape = r.shape[:-3] + (r.shape[-3] * r.shape[-2], r.shape[-1])
-    return tuple(np.ascontiguousarray(np.broadcast_to(a, r.shape)).reshape(shape) for a in (el, az, gain, delay))
+    return tuple(np.ascontiguousarray(np.broadcast_to(a, r.shape)).reshape(shape) for a in (el, az, gain, delay)) \
+        + (r, np.broadcast_to(v, r.shape + (3,)))
+
+
+def air_absorption(freqs, temperature=20.0, humidity=50.0, pressure=101.325):
+    """Atmospheric absorption of a pure tone in dB per metre (ISO 9613-1's formula).  freqs: Hz, > 0 (any shape);
+    temperature in degrees Celsius, relative humidity in percent, pressure in kPa.  At the defaults: 4.66 dB/km at 1 kHz,
+    29.7 at 4 kHz, 105 at 8 kHz.  ValueError for non-finite or non-positive inputs (a temperature at or below -273.15)."""
+    f = np.asarray(freqs, dtype=np.float64)
+    T, hum, pa = float(temperature) + 273.15, float(humidity), float(pressure)
+    if not np.isfinite(f).all() or not (f > 0).all():
+        raise ValueError("freqs must be finite and > 0")
+    if not (np.isfinite(T) and T > 0 and np.isfinite(hum) and hum > 0 and np.isfinite(pa) and pa > 0):
+        raise ValueError("temperature (above absolute zero), humidity and pressure must be finite and > 0")
+    T0, T01, pr = 293.15, 273.16, 101.325
+    psat = pr * 10.0 ** (-6.8346 * (T01 / T) ** 1.261 + 4.6151)
+    h = hum * psat / pa                                                # molar concentration of water vapour, percent
+    frO = (pa / pr) * (24.0 + 4.04e4 * h * (0.02 + h) / (0.391 + h))   # relaxation frequencies of oxygen and nitrogen
+    frN = (pa / pr) * (T / T0) ** -0.5 * (9.0 + 280.0 * h * np.exp(-4.170 * ((T / T0) ** (-1.0 / 3.0) - 1.0)))
+    return 8.686 * f * f * (1.84e-11 * (pr / pa) * (T / T0) ** 0.5 + (T / T0) ** -2.5 * (
+        0.01275 * np.exp(-2239.1 / T) / (frO + f * f / frO) + 0.1068 * np.exp(-3352.0 / T) / (frN + f * f / frN)))
+
+
+class SceneColor:
+    """What a path does to a source's spectrum besides its walls: air absorption over its length and the
+    source's directivity towards the listener, per frequency band, designed into a minimum-phase FIR of `taps` coefficients
+    per (row, chunk boundary) on the device.
+    bands: centre frequencies in Hz, ascending and > 0, at most 16; taps in 1..64.
+    air: None, True (air_absorption(bands) at its defaults) or [n_bands] dB per metre, >= 0.
+    directivity: None (omnidirectional), [n_bands] or [n_src, n_bands] first-order pattern coefficients a in [0, 1]:
+    D_b(cos theta) = |a_b + (1 - a_b) cos theta| with theta the angle off the source's forward axis (its local +y): 1 omni,
+    0.5 cardioid, 0 figure-of-eight.  With a banded Room, bands and taps must equal the room's.  ValueError otherwise."""
+
+    def __init__(self, bands, taps=32, air=None, directivity=None):
+        bands = np.asarray(bands, dtype=np.float64)
+        if bands.ndim != 1 or not 1 <= bands.size <= propagation.MAX_BANDS or not np.isfinite(bands).all() \
+                or not (bands > 0).all() or not (np.diff(bands) > 0).all():
+            raise ValueError(f"bands must be 1..{propagation.MAX_BANDS} centre frequencies in Hz, ascending and > 0")
+        if int(taps) != taps or not 1 <= int(taps) <= propagation.MAX_TAPS:
+            raise ValueError(f"taps must be in 1..{propagation.MAX_TAPS}")
+        self.bands, self.taps = bands, int(taps)
+        if air is True:
+            air = air_absorption(bands)
+        if air is not None:
+            air = np.asarray(air, dtype=np.float64)
+            if air.shape != bands.shape or not np.isfinite(air).all() or (air < 0).any():
+                raise ValueError("air must be None, True or [n_bands] dB per metre >= 0")
+        self.air = air
+        self.air_nepers = None if air is None else (np.log(10.0) / 20.0) * air
+        if directivity is not None:
+            directivity = np.asarray(directivity, dtype=np.float64)
+            if directivity.ndim not in (1, 2) or directivity.shape[-1] != bands.size or directivity.shape[0] < 1 \
+                    or not np.isfinite(directivity).all() or not ((directivity >= 0) & (directivity <= 1)).all():
+                raise ValueError("directivity must be None, [n_bands] or [n_src, n_bands] pattern coefficients in [0, 1]")
+        self.directivity = directivity
+        self._basis, self._device = {}, {}
+
+    def basis(self, fs):
+        """propagation.cepstral_basis(bands, fs, taps), cached per fs."""
+        fs = float(fs)
+        if fs not in self._basis:
+            self._basis[fs] = propagation.cepstral_basis(self.bands, fs, self.taps)
+        return self._basis[fs]
+
+    def check(self, room, n_src):
+        """ValueError unless this colour goes with `room` (a banded room's bands and taps are this colour's) and `n_src`
+        sources (per-source patterns: one row each).  Returns the images' wall log-magnitudes [n_img, n_bands], floored at
+        ln FIR_FLOOR, or None (no room, or a scalar one: img_gain carries its walls)."""
+        _n_img(room)
+        if self.directivity is not None and self.directivity.ndim == 2 and self.directivity.shape[0] != int(n_src):
+            raise ValueError(f"directivity has {self.directivity.shape[0]} rows for {n_src} sources")
+        if room is None or room.bands is None:
+            return None
+        if room.bands.shape != self.bands.shape or not np.array_equal(room.bands, self.bands) or room.taps != self.taps:
+            raise ValueError("the colour's bands and taps must equal the banded room's")
+        return np.log(np.maximum(image_band_magnitudes(room.images, room.beta), propagation.FIR_FLOOR))
+
+    def device_arrays(self, dev, fs, room):
+        """(pattern [n_src or 1, n_bands] or None, air in nepers per metre [n_bands] or None, the images' ln W
+        [n_img, n_bands] or None, basis [n_bands, taps]) as float64 tensors on `dev`, uploaded once per (device, fs, room)."""
+        import torch
+        key = (str(dev), float(fs), room)                              # (a Room hashes by identity)
+        if key not in self._device:
+            lnw = None if room is None or room.bands is None else \
+                np.log(np.maximum(image_band_magnitudes(room.images, room.beta), propagation.FIR_FLOOR))
+            pat = None if self.directivity is None else np.atleast_2d(self.directivity)
+            self._device[key] = tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                                      for a in (pat, self.air_nepers, lnw, self.basis(fs)))
+        return self._device[key]
+
+
+def _check_color(color, room, n_src):
+    if not isinstance(color, SceneColor):
+        raise ValueError("color must be a scene.SceneColor")
+    return color.check(room, n_src)
+
+
+def _check_orient(orient, pos_shape):
+    """orient against pos (..., n_src, nb, 3): host data as a float64 array (..., n_src, nb, 4) validated as a head is
+    (finite, non-zero norms: ValueError); a device tensor is checked for shape and dtype only; None stays None."""
+    import torch
+    if orient is None:
+        return None
+    shape = tuple(pos_shape[:-1]) + (4,)
+    if _is_device(orient):
+        if tuple(orient.shape) != shape or orient.dtype != torch.float64:
+            raise ValueError(f"orient must be a float64 tensor of shape {shape}")
+        return orient
+    arr = _host_array("orient", orient, shape)
+    sphere.check_head(arr)
+    return arr
+
+
+def scene_color_params(pos, fs, listener_pos=None, head=None, room=None, src_gain=None, c=SPEED_OF_SOUND, r_ref=1.0,
+                       interp="cubic", max_delay=None, chunksize=None, pos_prev=None, color=None, orient=None):
+    """scene_params plus the per-band log-magnitudes of a SceneColor: the float64 definition (numpy).
+    Arguments as for scene_params; color: a SceneColor (required); orient (..., n_src, nb, 4): quaternions (w, x, y, z)
+    turning each source's frame into the world frame, any non-zero norm (validated as head is), None: the identity.  A
+    source radiates along its local +y; an image's forward axis is the source's with component a negated where m_a is odd.
+    With q the image's position of steps 1-1b, v = q - l and r = |v| (unclamped, whatever max_delay):
+        cos theta = -(f . v) / r   (r == 0: 1),     D_b = |a_b + (1 - a_b) cos theta|
+        L[b] = max(ln max(W_i[b], FLOOR) - (ln 10 / 20) air[b] r + ln max(D_b, FLOOR), ln FLOOR)
+    with FLOOR = propagation.FIR_FLOOR and W_i the image's wall magnitudes of a banded room (1 otherwise: a scalar room's
+    walls stay in the gain).  Returns (elev, azim, gain, delay, logmag): scene_params' four, bit for bit, and logmag
+    float64 (..., n_src n_img, nb, n_bands)."""
+    lnw = _check_color(color, room, np.shape(pos)[-3] if len(np.shape(pos)) >= 3 else 0)
+    if _is_device(orient):
+        raise ValueError("scene_color_params takes host arrays (scene_color_params_device takes device tensors)")
+    el, az, gain, delay, r, v = _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay,
+                                              chunksize, pos_prev)
+    o = _check_orient(orient, np.shape(pos))
+    floor = propagation.FIR_FLOOR
+    L = np.zeros(r.shape + (color.bands.size,))
+    if lnw is not None:
+        L = L + lnw[:, None, :]                                        # (n_img, 1, n_bands)
+    if color.air_nepers is not None:
+        L = L - color.air_nepers * r[..., None]
+    if color.directivity is not None:
+        if o is None:
+            f = np.array([0.0, 1.0, 0.0])
+        else:
+            w, x, y, z = o[..., 0], o[..., 1], o[..., 2], o[..., 3]
+            n = np.sqrt(w * w + x * x + y * y + z * z)
+            w, x, y, z = w / n, x / n, y / n, z / n
+            f = np.stack([2.0 * (x * y - w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z + w * x)], axis=-1)
+            f = f[..., :, None, :, :]                                  # (..., n_src, 1, nb, 3)
+        if room is not None:
+            f = np.where(room.images[:, None, :] % 2 != 0, -f, f)      # the mirror turns the source
+        dot = f[..., 0] * v[..., 0] + f[..., 1] * v[..., 1] + f[..., 2] * v[..., 2]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            cos = np.where(r == 0.0, 1.0, -dot / r)
+        a = color.directivity if color.directivity.ndim == 1 else color.directivity[:, None, None, :]
+        L = L + np.log(np.maximum(np.abs(a + (1.0 - a) * cos[..., None]), floor))
+    L = np.maximum(L, np.log(floor))
+    shape = r.shape[:-3] + (r.shape[-3] * r.shape[-2], r.shape[-1], color.bands.size)
+    return el, az, gain, delay, np.ascontiguousarray(L).reshape(shape)
 
 
 def _unit_last(t):
@@ -317,6 +483,29 @@ def scene_params_device(pos, fs, listener_pos=None, head=None, room=None, src_ga
     out = (elev, azim, gain, delay): float64 device tensors [(G,) n_src n_img, nb] with unit stride on the last axis -
     strided views such as a stream renderer's trajectory_views(B) + (gain_view(B), delay_view(B)) serve; elev, azim and
     gain must share their strides; gain and delay may each be None (not computed).  Returns (elev, azim, gain, delay)."""
+    return _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, out, chunksize, pos_prev)
+
+
+def scene_color_params_device(pos, fs, listener_pos=None, head=None, room=None, src_gain=None, c=SPEED_OF_SOUND, r_ref=1.0,
+                              interp="cubic", max_delay=None, out=None, chunksize=None, pos_prev=None, color=None,
+                              orient=None):
+    """scene_color_params on the GPU (bas_scene_params_bands_f64, one launch): scene_params_device's arguments, a
+    SceneColor and orient [(G,) n_src, nb, 4] (a host array validated as head is, or a float64 device tensor).
+    out = (elev, azim, gain, delay, logmag): as for scene_params_device, and logmag a float64 device tensor
+    [(G,) n_src n_img, nb, n_bands] with unit stride along the bands (required).  Every argument is validated before any
+    device work (ValueError).  Returns (elev, azim, gain, delay, logmag); the first four are scene_params_device's bits."""
+    pos_shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
+    if len(pos_shape) not in (3, 4):
+        raise ValueError(f"pos must have shape [G, n_src, nb, 3] or [n_src, nb, 3], got {pos_shape}")
+    _check_color(color, room, pos_shape[-3])
+    return _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, out, chunksize, pos_prev,
+                         color, _check_orient(orient, pos_shape))
+
+
+def _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, out, chunksize, pos_prev,
+                  color=None, orient=None):
+    """The one body of scene_params_device (color None: bas_scene_params_f64, four outputs) and scene_color_params_device
+    (bas_scene_params_bands_f64, five; color and orient checked by the caller)."""
     import torch
     spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
     pos_shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
@@ -325,31 +514,52 @@ def scene_params_device(pos, fs, listener_pos=None, head=None, room=None, src_ga
     args = check_scene_args(pos_shape, pos, listener_pos, head, src_gain, room)
     spc, prev = _check_motion(chunksize, pos_prev, pos_shape, room)
     n_img = _n_img(room)
-    tensors = [t for t in args + (prev,) + tuple(out or ()) if _is_device(t)]
+    n_out = 4 if color is None else 5
+    tensors = [t for t in args + (prev, orient) + tuple(out or ()) if _is_device(t)]
     dev = tensors[0].device if tensors else _hip.require_gpu()
-    p, l, q, sg, prev = (None if a is None else _unit_last(a.to(dev) if _is_device(a) else torch.from_numpy(a).to(dev))
-                         for a in args + (prev,))
+    p, l, q, sg, prev, orient = (None if a is None else _unit_last(a.to(dev) if _is_device(a) else torch.from_numpy(a).to(dev))
+                                 for a in args + (prev, orient))
     batched = len(pos_shape) == 4
     G = pos_shape[0] if batched else 1
     n_src, nb = pos_shape[-3], pos_shape[-2]
     if min(G, n_src, nb) < 1:
         raise ValueError("pos must hold at least one group, source and boundary")
     shape = pos_shape[:-3] + (n_src * n_img, nb)
+    lshape = None if color is None else shape + (color.bands.size,)
     if out is None:
         out = tuple(torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(4))
-    if len(out) != 4 or out[0] is None or out[1] is None:
-        raise ValueError("out must be (elev, azim, gain, delay); gain and delay may be None")
-    for t in out:
+        if color is not None:
+            out += (torch.empty(lshape, dtype=torch.float64, device=dev),)
+    if len(out) != n_out or out[0] is None or out[1] is None or (color is not None and out[4] is None):
+        raise ValueError("out must be (elev, azim, gain, delay" + (")" if color is None else ", logmag)") +
+                         "; gain and delay may be None")
+    for t in out[:4]:
         if t is not None and not (_is_device(t) and t.device == dev and t.dtype == torch.float64 and tuple(t.shape) == shape
                                   and t.stride(-1) == 1):
             raise ValueError(f"out tensors must be float64 of shape {shape} on {dev} with unit stride on the last axis")
-    eo, ao, go, do = out
+    if color is not None and not (_is_device(out[4]) and out[4].device == dev and out[4].dtype == torch.float64
+                                  and tuple(out[4].shape) == lshape and out[4].stride(-1) == 1
+                                  and all(s >= 0 for s in out[4].stride())):
+        raise ValueError(f"out's logmag must be float64 of shape {lshape} on {dev} with unit stride along the bands")
+    eo, ao, go, do = out[:4]
     if ao.stride() != eo.stride() or (go is not None and go.stride() != eo.stride()):
         raise ValueError("out's elev, azim and gain must have equal strides")
 
     def gs(t, k):                                                      # (group stride, stride of axis k) of an argument
         return (0, 0) if t is None else (t.stride(0) if batched else 0, t.stride(k))
     size, images, gains = (None, None, None) if room is None else room.device_arrays(dev)
+    if color is not None:
+        lo = out[4]
+        pat, air, lnw, _ = color.device_arrays(dev, fs, room)
+        with _hip.on_device(dev):
+            _hip.call("bas_scene_params_bands_f64", _hip.ptr(p), *gs(p, -3), p.stride(-2), _hip.ptr(prev), *gs(prev, -2),
+                      spc, _hip.ptr(l), *gs(l, -2), _hip.ptr(q), *gs(q, -2), _hip.ptr(sg), *gs(sg, -2), _hip.ptr(size),
+                      _hip.ptr(images), _hip.ptr(gains), n_img, spm, r_ref, d_min, d_max, G, n_src, nb, _hip.ptr(orient),
+                      *gs(orient, -3), 0 if orient is None else orient.stride(-2), _hip.ptr(pat),
+                      0 if pat is None or pat.shape[0] == 1 else pat.stride(0), _hip.ptr(air), _hip.ptr(lnw),
+                      color.bands.size, propagation.FIR_FLOOR, _hip.ptr(eo), _hip.ptr(ao), _hip.ptr(go), *gs(eo, -2),
+                      _hip.ptr(do), *gs(do, -2), _hip.ptr(lo), *gs(lo, -3), lo.stride(-2), _hip.current_stream(dev))
+        return eo, ao, go, do, lo
     with _hip.on_device(dev):
         _hip.call("bas_scene_params_f64", _hip.ptr(p), *gs(p, -3), p.stride(-2), _hip.ptr(prev), *gs(prev, -2), spc,
                   _hip.ptr(l), *gs(l, -2), _hip.ptr(q),
@@ -365,7 +575,8 @@ def _table_L(tbl):
 
 
 def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=None, head=None, room=None, src_gain=None,
-                 normalize="mix", interp="cubic", c=SPEED_OF_SOUND, r_ref=1.0, fused=None, late=None):
+                 normalize="mix", interp="cubic", c=SPEED_OF_SOUND, r_ref=1.0, fused=None, late=None, color=None,
+                 orient=None):
     """Render and mix moving sources given by their positions (render_sources with the geometry done on the device).
 
     signals: [n_src, N] (numpy or tensor); pos: [n_src, n_chunks + 1, 3], the sources' positions in metres at t = 0, K, ..,
@@ -380,7 +591,13 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     late: None, or a reverb.LateTail: the raw source signals, weighted by src_gain, are mixed into one bus
     (bas_bus_mix_f32), the dry render runs un-normalised, and bas_long_fir_f32 writes dry + bus * tail into a new buffer of
     in_length + max(L, lag + Lr) - 1 samples, on which the peak rule then runs (bas_peak_normalize_f32).  The chunk size
-    must be a multiple of 32 (reverb.partition: ValueError).  late=None: the launches and the bits of a call without it."""
+    must be a multiple of 32 (reverb.partition: ValueError).  late=None: the launches and the bits of a call without it.
+    color: None, or a SceneColor (air absorption and source directivity, with orient [n_src, n_chunks + 1, 4]
+    the sources' orientations, None: all facing +y).  The scene kernel then also writes every row's band log-magnitudes at
+    every boundary (bas_scene_params_bands_f64; a banded room's walls are among them, its static bank is not used), one
+    bas_color_design_f32 launch designs the taps [rows, n_chunks + 1, taps] (rows x (n_chunks + 1) x taps x 4 bytes, not
+    slabbed), the delay launch writes the staging rows and bas_color_rows_f32 filters them in its per-boundary form.
+    color=None: the launches and the bits of a call without it (orient then needs a color: ValueError)."""
     import torch
     from .apply_hrtf import as_device_table, padded_rows, render_lengths, render_angles_device
     K, S = int(chunksize), int(subchunksize)
@@ -398,21 +615,35 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     n_q = in_length // K + 1
     _scalars(fs, c, r_ref, interp, None)
     args = check_scene_args((n_src, n_q, 3), pos, listener_pos, head, src_gain, room)
+    if color is None and orient is not None:
+        raise ValueError("orient needs a color (a scene.SceneColor)")
+    if color is not None:
+        _check_color(color, room, n_src)
+        orient = _check_orient(orient, (n_src, n_q, 3))
     tbl = as_device_table(tbl)
     dev = tbl.device
     args = tuple(a.to(dev) if _is_device(a) else a for a in args)
     if not any(_is_device(a) for a in args):
         args = (torch.from_numpy(args[0]).to(dev),) + args[1:]        # (so that the scene runs on the table's device)
-    el, az, g, d = scene_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp, chunksize=K)
-    banded = room is not None and room.bands is not None
+    taps = None
+    if color is None:
+        el, az, g, d = scene_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp, chunksize=K)
+    else:                                                              # the bands with the geometry, then every row's taps
+        orient = orient.to(dev) if _is_device(orient) else orient
+        el, az, g, d, lm = scene_color_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp,
+                                                     chunksize=K, color=color, orient=orient)
+        taps = propagation.design_colors_device(lm, color.device_arrays(dev, fs, room)[3])
+    banded = room is not None and room.bands is not None and color is None
     x = padded_rows(n_src * n_img, in_length, dev)
     if n:
         src = sig.to(device=dev, dtype=torch.float32).contiguous()
         lens = torch.full((n_src * n_img,), n, dtype=torch.int64, device=dev)
-        pre = padded_rows(n_src * n_img, in_length, dev) if banded else x
+        pre = padded_rows(n_src * n_img, in_length, dev) if banded or color is not None else x
         # groups = sources, rows of a group = its images: the input's row stride is 0, every image reads the one signal
         propagation.delay_rows_device(src[:1].expand(n_img, n), d[:n_img], K, interp, pre[:n_img], lengths=lens,
                                       groups=(n_src, src.stride(0), n_img * d.stride(0), n_img * pre.stride(0)))
+        if color is not None:                                          # every row its own taps at every boundary
+            propagation.color_rows_device(pre, taps, K, x, lengths=lens)
         if banded:                                                     # every source's images read the one bank
             propagation.color_rows_device(pre[:n_img], room.device_filters(fs, dev), K, x[:n_img], lengths=lens,
                                           groups=(n_src, n_img * pre.stride(0), 0, n_img * x.stride(0)))
@@ -437,7 +668,7 @@ class SceneStreamRenderer:
     into the inner renderer's own buffers (one launch in front of the block's graph, where §3.9's head launch sits)."""
 
     def __init__(self, tbl, n_src, chunksize, subchunksize, fs, max_distance, room=None, interp="cubic", c=SPEED_OF_SOUND,
-                 r_ref=1.0, graph=True, copy_out=True, late=None):
+                 r_ref=1.0, graph=True, copy_out=True, late=None, color=None):
         """n_src sources (each rendered as room.n_img image sources: the inner StreamRenderer has n_src n_img rows);
         max_distance: the largest source-to-listener path in metres, images included (a longer one is heard at
         max_distance's delay: the clamp of §3.11); the stream carries max_distance / c * fs samples of history per row.
@@ -445,11 +676,18 @@ class SceneStreamRenderer:
         late: None, or a reverb.LateTail: behind every block's render (and its graph) one bus-mix launch
         - the block's raw signals weighted by src_gain - and bas_long_fir_f32, which adds the wet signal to the block's
         output, then the carry of the bus's history (reverb.LateStream); `peak` is then the running maximum over the sums
-        and finish() returns max(L, lag + Lr) - 1 samples.  The chunk size must be a multiple of 32 (ValueError)."""
+        and finish() returns max(L, lag + Lr) - 1 samples.  The chunk size must be a multiple of 32 (ValueError).
+        color: None, or a SceneColor: the inner renderer is built with color_taps = color.taps; every
+        block's scene launch also writes the rows' band log-magnitudes (a banded room's walls among them: its static
+        bank is not used) and one bas_color_design_f32 launch writes the block's taps into the inner renderer's
+        color_view(B) in place, in front of the block's graph; process() then takes orient=."""
         from .stream import StreamRenderer
         self.n_src, self.n_img = int(n_src), _n_img(room)
         if self.n_src < 1:
             raise ValueError("n_src must be >= 1")
+        self.color = color
+        if color is not None:
+            _check_color(color, room, self.n_src)
         self._spm, self.r_ref, _, _ = _scalars(fs, c, r_ref, interp, None)
         self.fs, self.c, self.room, self.interp = float(fs), float(c), room, interp
         md = float(max_distance)
@@ -460,14 +698,16 @@ class SceneStreamRenderer:
         self.K = int(chunksize)
         assert self.K % int(subchunksize) == 0, 'subchunksize does not divide chunksize evenly'
         self._prev = None                                 # the sources' positions one chunk before the next block (device)
-        banded = room is not None and room.bands is not None
+        banded = room is not None and room.bands is not None and color is None
         self.copy_out = bool(copy_out)
         if reverb.check_late(late) is not None:           # (the sums are this class's to hand out: the inner renderer's
             reverb.partition(self.K)                      # blocks stay views of its own output buffer)
             copy_out = False
         self.inner = StreamRenderer(tbl, self.n_src * self.n_img, chunksize, subchunksize, graph=graph, copy_out=copy_out,
-                                    max_delay=self.max_delay, interp=interp, color_taps=room.taps if banded else None)
+                                    max_delay=self.max_delay, interp=interp,
+                                    color_taps=color.taps if color is not None else room.taps if banded else None)
         self._bank = None
+        self._logmag = None                               # the block's band log-magnitudes [rows, B/K + 1, n_bands] (device)
         if banded:                                        # the static bank, every source's images alike: written once into
             dev = self.inner.tbl.device                   # the inner renderer's own static colour buffer, passed every block
             self._bank = self.inner.color_view(None, static=True)
@@ -479,6 +719,8 @@ class SceneStreamRenderer:
         """StreamRenderer.prepare for blocks of B samples, with the gains live (so that the captured graph is the one
         process() replays)."""
         self.inner.gain_view(B)
+        if self.color is not None:                        # (the per-boundary colour live too: process() passes color_view(B))
+            self.inner.color_view(B)
         self.inner.prepare(B)
         if self._late is not None:
             self._late.prepare(B)
@@ -493,24 +735,42 @@ class SceneStreamRenderer:
             raise ValueError("block length must be a positive multiple of the chunk size")
         return B, check_scene_args((self.n_src, B // self.K + 1, 3), pos, listener_pos, head, src_gain, self.room)
 
-    def process(self, block, pos, listener_pos=None, head=None, src_gain=None):
+    def process(self, block, pos, listener_pos=None, head=None, src_gain=None, orient=None):
         """block: [n_src, B] (B a multiple of the chunk size); pos: [n_src, B/K + 1, 3], the sources' positions at the
         block's chunk boundaries t0, t0 + K, .., t0 + B; listener_pos [B/K + 1, 3], head [B/K + 1, 4], src_gain
         [n_src, B/K + 1]: as for scene_params_device.  Consecutive blocks should repeat their shared boundary.
+        orient [n_src, B/K + 1, 4]: the sources' orientations at the same boundaries (a renderer built with color only:
+        ValueError otherwise; None: all facing +y).
         Returns the B stereo samples this block completes as a device tensor (B, 2), un-normalised."""
         import torch
         blk = torch.as_tensor(block)
         B, args = self.check_block(tuple(blk.shape), pos, listener_pos, head, src_gain)
+        if orient is not None and self.color is None:
+            raise ValueError("orient= needs a renderer built with color")
+        orient = _check_orient(orient, (self.n_src, B // self.K + 1, 3))
         st, dev = self.inner, self.inner.tbl.device
         out = st.trajectory_views(B) + (st.gain_view(B), st.delay_view(B))
         args = tuple(a.to(dev) if _is_device(a) else a for a in args)
         p = args[0] if _is_device(args[0]) else torch.from_numpy(args[0]).to(dev)
-        el, az, g, d = scene_params_device(p, self.fs, args[1], args[2], self.room, args[3], self.c, self.r_ref,
-                                           self.interp, self.max_delay, out=out, chunksize=self.K, pos_prev=self._prev)
+        taps = self._bank
+        if self.color is None:
+            el, az, g, d = scene_params_device(p, self.fs, args[1], args[2], self.room, args[3], self.c, self.r_ref,
+                                               self.interp, self.max_delay, out=out, chunksize=self.K, pos_prev=self._prev)
+        else:                                             # the bands with the geometry, then the block's taps in place
+            taps = st.color_view(B)
+            lshape = (self.n_src * self.n_img, B // self.K + 1, self.color.bands.size)
+            if self._logmag is None or tuple(self._logmag.shape) != lshape:
+                self._logmag = torch.empty(lshape, dtype=torch.float64, device=dev)
+            orient = orient.to(dev) if _is_device(orient) else orient
+            el, az, g, d, lm = scene_color_params_device(p, self.fs, args[1], args[2], self.room, args[3], self.c,
+                                                         self.r_ref, self.interp, self.max_delay, out=out + (self._logmag,),
+                                                         chunksize=self.K, pos_prev=self._prev, color=self.color,
+                                                         orient=orient)
+            propagation.design_colors_device(lm, self.color.device_arrays(dev, self.fs, self.room)[3], out=taps)
         self._prev = p[:, -2].clone()                     # (the velocity at the next block's first boundary)
         x = st.input_view(B)                                           # [n_src n_img, B]: every image's copy of the block
         x.view(self.n_src, self.n_img, B).copy_(blk.to(dev).unsqueeze(1))   # (one broadcast copy, converts to float32)
-        dry = st.process(x, el, az, gain=g, delay=d, color=self._bank)
+        dry = st.process(x, el, az, gain=g, delay=d, color=taps)
         if self._late is None:
             return dry
         # the bus from the block's raw signals (every source's first image row holds its float32 copy) and src_gain, then

@@ -580,6 +580,56 @@ int bas_scene_params_f64(const double *pos, long pos_stride_g, long pos_stride_s
                          int nb, double *elev, double *azim, double *gain, long a_stride_g, long a_stride_s,
                          double *delay, long d_stride_g, long d_stride_s, bas_stream_t stream);
 
+/* ---- scene colour: air absorption and source directivity (no reference counterpart) -------------------
+ * Per (row, boundary) of a Cartesian scene, the natural log-magnitude in each of n_bands frequency bands of what the
+ * path does to the sound - the walls the image met, the air it crossed, the source's pattern towards the listener - and,
+ * from such log-magnitudes, the taps of a minimum-phase FIR per (row, boundary), laid out as "per-source colour" reads them.
+ *   bas_scene_params_bands_f64: bas_scene_params_f64 (same arguments, same four outputs bit for bit, same checks) plus
+ *     orient [G][n_src][nb][4] at orient[g orient_stride_g + s orient_stride_s + c orient_stride_c + k]: (w, x, y, z)
+ *       turning the source's frame into the world frame, any non-zero norm, normalised here; NULL: the identity.  A source
+ *       radiates along its local +y: f = R(orient) (0, 1, 0) = (2(xy - wz), 1 - 2(x^2 + z^2), 2(yz + wx));
+ *     pattern [n_src][n_bands] at pattern[s pattern_stride_s + b]: first-order coefficients a in [0, 1] (1 omni, 0.5
+ *       cardioid, 0 figure-of-eight); pattern_stride_s 0 shares one row over the sources, else >= n_bands; NULL: omni;
+ *     air [n_bands]: absorption in nepers per metre (dB per metre times ln 10 / 20), >= 0; NULL: none;
+ *     img_logmag [n_img][n_bands]: ln of the images' wall magnitudes (floored by the caller); NULL: 0;
+ *     n_bands in 1..16; floor in (0, 1]: the magnitude below which the pattern term and the sum are floored.
+ *   With q the image's position of steps 1-1b, v = q - listener and r of step 2 (unclamped), in binary64 without
+ *   contraction: f_a is negated where images[i][a] is odd (the mirror turns the source);
+ *     cos = -(fx vx + fy vy + fz vz) / r  (r == 0: 1);   D_b = |a_b + (1 - a_b) cos|;
+ *     L[b] = fmax(((img_logmag[i][b] - air[b] r) + log(fmax(D_b, floor))), log(floor))
+ *   (a NULL term is skipped), written at logmag[g l_stride_g + row l_stride_s + c l_stride_c + b], row = s n_img + i.
+ *   l_stride_c >= n_bands and [G][rows][(nb - 1) l_stride_c + n_bands] with strides (l_stride_g, l_stride_s, 1) must
+ *   address no element twice; logmag distinct from the other outputs; input strides >= 0 (BAS_E_SHAPE); logmag required
+ *   (BAS_E_NULL); the new float64 pointers 8-byte aligned (BAS_E_ALIGN).  Still one launch, capturable.
+ *   bas_color_design_f32: logmag float64 at logmag[g l_stride_g + s l_stride_s + k l_stride_k + b] (strides in 0..2^40,
+ *     0 repeats), g < n_groups, s < n_src, k < nb; basis float64 [n_bands][M] (device): row b holds the first M folded
+ *     cepstrum coefficients of band b's interpolation weight (propagation.cepstral_basis).  Per filter, in binary64:
+ *       L[b] = fmax(logmag[b], logmag_floor);  c[m] = sum_b L[b] basis[b][m]  (fma from 0, b ascending);
+ *       h[0] = exp(c[0]);  h[n] = (sum_{k=1..n} (k c[k]) h[n - k]) / n  (fma from 0, k ascending),  1 <= n < M;
+ *     the first M taps of the minimum-phase response whose log-magnitude has those band values.  Output: (float)h[m] at
+ *     color[g c_stride_g + s c_stride_s + k c_stride_k + m], M contiguous floats.  A filter's bits depend on its n_bands
+ *     inputs, the basis and the floor alone, not on the grid nor on its place in it.  M in 1..64, n_bands in 1..16,
+ *     logmag_floor finite and <= 0, n_groups n_src nb < 2^40, c_stride_k >= M and [G][n_src][(nb - 1) c_stride_k + M] with
+ *     strides (c_stride_g, c_stride_s, 1) must address no element twice (BAS_E_SHAPE; a StreamRenderer's color_view(B)
+ *     passes); any count 0: nothing to do; logmag, basis, color required (BAS_E_NULL), 8-, 8- and 4-byte aligned
+ *     (BAS_E_ALIGN).  color must not overlap logmag or basis.  One launch, no allocation, no synchronisation
+ *     (capturable once the first call on a device has been made).  Nothing is validated on the device. */
+int bas_scene_params_bands_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                               const double *pos_prev, long prev_stride_g, long prev_stride_s, double samples_per_chunk,
+                               const double *lpos, long lpos_stride_g, long lpos_stride_c, const double *head,
+                               long head_stride_g, long head_stride_c, const double *src_gain, long sg_stride_g,
+                               long sg_stride_s, const double *room_size, const int32_t *images, const double *img_gain,
+                               int n_img, double samples_per_metre, double r_ref, double d_min, double d_max, int n_groups,
+                               int n_src, int nb, const double *orient, long orient_stride_g, long orient_stride_s,
+                               long orient_stride_c, const double *pattern, long pattern_stride_s, const double *air,
+                               const double *img_logmag, int n_bands, double floor, double *elev, double *azim,
+                               double *gain, long a_stride_g, long a_stride_s, double *delay, long d_stride_g,
+                               long d_stride_s, double *logmag, long l_stride_g, long l_stride_s, long l_stride_c,
+                               bas_stream_t stream);
+int bas_color_design_f32(const double *logmag, long l_stride_g, long l_stride_s, long l_stride_k, const double *basis,
+                         int n_bands, int M, double logmag_floor, int n_groups, int n_src, int nb, float *color,
+                         long c_stride_g, long c_stride_s, long c_stride_k, bas_stream_t stream);
+
 /* ---- late reverberation (no reference counterpart) ---------------------------------------------------
  * One send bus per group - a weighted mono mix of the group's source rows - through one long static stereo tail, added to
  * the binaural mix.  All entries: one stream, no allocation, no synchronisation (capturable); every argument check runs

@@ -1,0 +1,308 @@
+// The host half of scene colour (include/bas.h "scene colour") under AddressSanitizer and
+// UndefinedBehaviorSanitizer, stand-alone: `make -C binaural-audio-synthesis_amd/csrc hostsan_design` links this file with
+// the library's objects (host code sanitized, device code as shipped).  Three parts:
+//   1. bas_scene_params_bands_f64 and bas_color_design_f32: one valid argument list each, which with no device to run on
+//      returns a positive hipError_t, and its violations, each of which returns the code bas.h documents and leaves a text
+//      naming the entry point.  The pointers are never dereferenced by the host code.
+//   2. the host build of the per-filter function of the design kernel (bas_design.h: bas_design_filter) against a plain C
+//      restatement of the recursion, over tap and band counts and log-magnitudes spanning [ln 1e-6, 0], at unit and at
+//      lane strides.
+//   3. `hostsan_design design IN OUT`: the same host build as a filter bank for the Python tests - IN holds int32 n_bands,
+//      M, n, then float64 floor, basis [n_bands][M], logmag [n][n_bands]; OUT receives float32 taps [n][M].
+// Exits 77 where a GPU is visible.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/bas.h"
+#include "../../binaural-audio-synthesis_amd/csrc/bas_design.h"
+
+static int g_fail = 0, g_checks = 0;
+
+static void expect(int line, const char *what, int rc, int want, const char *entry) {
+    ++g_checks;
+    const char *text = bas_last_error();
+    bool ok = want > 0 ? rc > 0 : rc == want;
+    if (ok && want != 0) ok = text && strstr(text, entry) != nullptr;      // every failure leaves a text naming the entry
+    if (!ok && ++g_fail <= 40)
+        fprintf(stderr, "hostsan_design: FAIL line %d: %s: returned %d, want %s%d, text \"%s\"\n", line, what, rc,
+                want > 0 ? "> " : "", want > 0 ? 0 : want, text ? text : "(null)");
+}
+#define EXPECT(what, call, want, entry) expect(__LINE__, what, (call), (want), entry)
+
+static const int E_NULL = -1, E_SHAPE = -2, E_ALIGN = -3, NO_DEVICE = 1;
+
+template <class T>
+static T *at(uintptr_t base, long bytes) {
+    return reinterpret_cast<T *>(base + bytes);
+}
+
+struct Bands {
+    const double *pos;
+    long ps_g, ps_s, ps_c;
+    const double *room_size;
+    const int32_t *images;
+    const double *img_gain;
+    int n_img, G, n_src, nb;
+    const double *orient;
+    long o_g, o_s, o_c;
+    const double *pattern;
+    long pt_s;
+    const double *air, *lnw;
+    int n_bands;
+    double floor;
+    double *elev, *azim, *gain;
+    long a_g, a_s;
+    double *delay;
+    long d_g, d_s;
+    double *logmag;
+    long l_g, l_s, l_c;
+    int call() const {
+        return bas_scene_params_bands_f64(pos, ps_g, ps_s, ps_c, nullptr, 0, 0, 0.0, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
+                                          room_size, images, img_gain, n_img, 128.0, 1.0, 2.0, 1e4, G, n_src, nb, orient, o_g,
+                                          o_s, o_c, pattern, pt_s, air, lnw, n_bands, floor, elev, azim, gain, a_g, a_s, delay,
+                                          d_g, d_s, logmag, l_g, l_s, l_c, nullptr);
+    }
+};
+
+static void bands_section() {
+    static const char *N = "bas_scene_params_bands_f64";
+    const uintptr_t p = uintptr_t(1) << 32;                                  // made-up device addresses, 64-byte aligned
+    const int G = 2, n_src = 5, n_img = 7, nb = 9, n_bands = 6;
+    const long rows = (long)n_src * n_img;
+    const Bands ok = {at<const double>(p, 0), (long)n_src * nb * 3, (long)nb * 3, 3, at<const double>(p, 1 << 20),
+                      at<const int32_t>(p, 2 << 20), at<const double>(p, 3 << 20), n_img, G, n_src, nb,
+                      at<const double>(p, 4 << 20), (long)n_src * nb * 4, (long)nb * 4, 4, at<const double>(p, 5 << 20),
+                      n_bands, at<const double>(p, 6 << 20), at<const double>(p, 7 << 20), n_bands, 1e-6,
+                      at<double>(p, 8 << 20), at<double>(p, 9 << 20), at<double>(p, 10 << 20), rows * nb, nb,
+                      at<double>(p, 11 << 20), rows * nb, nb, at<double>(p, 12 << 20), rows * nb * n_bands,
+                      (long)nb * n_bands, n_bands};
+    Bands a;
+    EXPECT("valid arguments, no device", ok.call(), NO_DEVICE, N);
+    a = ok; a.orient = nullptr; a.pattern = nullptr; a.air = nullptr; a.lnw = nullptr; a.o_g = a.o_s = a.o_c = a.pt_s = 0;
+    EXPECT("valid arguments without the optional inputs, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.pt_s = 0;
+    EXPECT("one pattern for all sources, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.l_c = n_bands + 2; a.l_s = (long)nb * (n_bands + 2); a.l_g = rows * a.l_s + 5;
+    EXPECT("padded logmag rows, no device", a.call(), NO_DEVICE, N);
+    // ---- the checks of bas_scene_params_f64 hold here too (a sample of them)
+    a = ok; a.pos = nullptr; EXPECT("pos null", a.call(), E_NULL, N);
+    a = ok; a.elev = nullptr; EXPECT("elev null", a.call(), E_NULL, N);
+    a = ok; a.nb = 0; EXPECT("nb 0", a.call(), E_SHAPE, N);
+    a = ok; a.a_s = nb - 1; EXPECT("angle rows overlap", a.call(), E_SHAPE, N);
+    a = ok; a.azim = a.elev; EXPECT("azim == elev", a.call(), E_SHAPE, N);
+    a = ok; a.pos = at<const double>(p, 4); EXPECT("pos misaligned", a.call(), E_ALIGN, N);
+    // ---- the new arguments
+    a = ok; a.logmag = nullptr; EXPECT("logmag null", a.call(), E_NULL, N);
+    for (int n : {0, -1, 17}) { a = ok; a.n_bands = n; EXPECT("n_bands", a.call(), E_SHAPE, N); }
+    for (double f : {0.0, -1e-6, 1.5, (double)NAN}) { a = ok; a.floor = f; EXPECT("floor", a.call(), E_SHAPE, N); }
+    for (int i = 0; i < 7; ++i) {
+        a = ok;
+        long *f[7] = {&a.o_g, &a.o_s, &a.o_c, &a.pt_s, &a.l_g, &a.l_s, &a.l_c};
+        *f[i] = -1;
+        EXPECT("negative stride", a.call(), E_SHAPE, N);
+    }
+    a = ok; a.l_c = 1L << 62; EXPECT("(nb - 1) l_stride_c leaves a signed long", a.call(), E_SHAPE, N);
+    a = ok; a.pt_s = n_bands - 1; EXPECT("pattern rows overlap", a.call(), E_SHAPE, N);
+    a = ok; a.l_c = n_bands - 1; EXPECT("boundaries' bands overlap", a.call(), E_SHAPE, N);
+    a = ok; a.l_c = 0; EXPECT("boundaries alias", a.call(), E_SHAPE, N);
+    a = ok; a.l_s = (long)nb * n_bands - 1; EXPECT("rows overlap by one", a.call(), E_SHAPE, N);
+    a = ok; a.l_s = 0; EXPECT("rows alias", a.call(), E_SHAPE, N);
+    a = ok; a.l_g = 0; EXPECT("groups alias", a.call(), E_SHAPE, N);
+    a = ok; a.l_g = rows * nb * n_bands - 1; EXPECT("groups overlap by one", a.call(), E_SHAPE, N);
+    a = ok; a.logmag = a.gain; EXPECT("logmag == gain", a.call(), E_SHAPE, N);
+    a = ok; a.logmag = a.delay; EXPECT("logmag == delay", a.call(), E_SHAPE, N);
+    a = ok; a.logmag = a.elev; EXPECT("logmag == elev", a.call(), E_SHAPE, N);
+    a = ok; a.orient = at<const double>(p, (4 << 20) + 4); EXPECT("orient misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.pattern = at<const double>(p, (5 << 20) + 2); EXPECT("pattern misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.air = at<const double>(p, (6 << 20) + 1); EXPECT("air misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.lnw = at<const double>(p, (7 << 20) + 4); EXPECT("img_logmag misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.logmag = at<double>(p, (12 << 20) + 4); EXPECT("logmag misaligned", a.call(), E_ALIGN, N);
+}
+
+struct Design {
+    const double *logmag;
+    long l_g, l_s, l_k;
+    const double *basis;
+    int n_bands, M;
+    double floor;
+    int G, n_src, nb;
+    float *color;
+    long c_g, c_s, c_k;
+    int call() const {
+        return bas_color_design_f32(logmag, l_g, l_s, l_k, basis, n_bands, M, floor, G, n_src, nb, color, c_g, c_s, c_k, nullptr);
+    }
+};
+
+static void design_section() {
+    static const char *N = "bas_color_design_f32";
+    const uintptr_t p = uintptr_t(1) << 33;
+    const int G = 3, n_src = 40, nb = 5, n_bands = 6, M = 32;
+    const Design ok = {at<const double>(p, 0), (long)n_src * nb * n_bands, (long)nb * n_bands, n_bands,
+                       at<const double>(p, 1 << 20), n_bands, M, std::log(1e-6), G, n_src, nb, at<float>(p, 2 << 20),
+                       (long)n_src * nb * M, (long)nb * M, M};
+    Design a;
+    EXPECT("valid arguments, no device", ok.call(), NO_DEVICE, N);
+    a = ok; a.l_g = a.l_s = a.l_k = 0;
+    EXPECT("one set of bands for every filter, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.c_k = M + 4; a.c_s = (long)nb * (M + 4) + 8; a.c_g = (long)n_src * a.c_s;
+    EXPECT("padded output, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.M = 64; a.c_k = 64; a.c_s = 64L * nb; a.c_g = a.c_s * n_src; a.n_bands = 16;
+    EXPECT("the largest filter, no device", a.call(), NO_DEVICE, N);
+    a = ok; a.G = 0; a.color = nullptr; EXPECT("no groups: nothing to do", a.call(), 0, N);
+    a = ok; a.n_src = 0; a.logmag = nullptr; EXPECT("no rows: nothing to do", a.call(), 0, N);
+    a = ok; a.nb = 0; a.basis = nullptr; EXPECT("no boundaries: nothing to do", a.call(), 0, N);
+    // ---- null pointers
+    a = ok; a.logmag = nullptr; EXPECT("logmag null", a.call(), E_NULL, N);
+    a = ok; a.basis = nullptr; EXPECT("basis null", a.call(), E_NULL, N);
+    a = ok; a.color = nullptr; EXPECT("color null", a.call(), E_NULL, N);
+    // ---- counts and limits
+    for (int m : {0, -1, 65}) { a = ok; a.M = m; EXPECT("M", a.call(), E_SHAPE, N); }
+    for (int n : {0, -1, 17}) { a = ok; a.n_bands = n; EXPECT("n_bands", a.call(), E_SHAPE, N); }
+    a = ok; a.G = -1; EXPECT("n_groups < 0", a.call(), E_SHAPE, N);
+    a = ok; a.n_src = -1; EXPECT("n_src < 0", a.call(), E_SHAPE, N);
+    a = ok; a.nb = -1; EXPECT("nb < 0", a.call(), E_SHAPE, N);
+    a = ok; a.G = 1 << 14; a.n_src = 1 << 14; a.nb = 1 << 12; EXPECT("2^40 filters", a.call(), E_SHAPE, N);
+    for (double f : {1e-3, (double)-INFINITY, (double)NAN}) { a = ok; a.floor = f; EXPECT("floor", a.call(), E_SHAPE, N); }
+    // ---- negative strides and strides of 2^40 (and an extent that leaves a signed long)
+    for (int i = 0; i < 6; ++i)
+        for (long v : {-1L, 1L << 40}) {
+            a = ok;
+            long *f[6] = {&a.l_g, &a.l_s, &a.l_k, &a.c_g, &a.c_s, &a.c_k};
+            *f[i] = v;
+            if (i >= 3 && v > 0) continue;                                       // (a sparse output layout is legal)
+            EXPECT("stride", a.call(), E_SHAPE, N);
+        }
+    a = ok; a.nb = 1 << 30; a.c_k = 1L << 40; a.G = 1; a.n_src = 1; EXPECT("(nb - 1) c_stride_k overflows", a.call(), E_SHAPE, N);
+    // ---- a doubly addressed output
+    for (long v : {0L, 1L, (long)M - 1}) { a = ok; a.c_k = v; EXPECT("c_stride_k inside a filter", a.call(), E_SHAPE, N); }
+    a = ok; a.c_s = (long)nb * M - 1; EXPECT("rows overlap by one", a.call(), E_SHAPE, N);
+    a = ok; a.c_s = 0; EXPECT("rows alias", a.call(), E_SHAPE, N);
+    a = ok; a.c_g = 0; EXPECT("groups alias", a.call(), E_SHAPE, N);
+    a = ok; a.c_g = a.c_s; EXPECT("groups meet rows", a.call(), E_SHAPE, N);
+    a = ok; a.c_g = (long)n_src * nb * M - 1; EXPECT("groups overlap by one", a.call(), E_SHAPE, N);
+    // ---- misaligned pointers
+    a = ok; a.logmag = at<const double>(p, 4); EXPECT("logmag misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.basis = at<const double>(p, (1 << 20) + 2); EXPECT("basis misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.color = at<float>(p, (2 << 20) + 2); EXPECT("color misaligned", a.call(), E_ALIGN, N);
+}
+
+// ---- part 2: the per-filter function's host build against a restatement --------------------------------------------------
+// (plain sums and products in long double, no fused operations, its own loop order over b: another program of the same
+// mathematics)
+static void restated(const double *logmag, const double *basis, int n_bands, int M, double floor, long double *h) {
+    std::vector<long double> c(M);
+    for (int m = 0; m < M; ++m) {
+        long double acc = 0;
+        for (int b = n_bands - 1; b >= 0; --b) acc += (long double)(logmag[b] < floor ? floor : logmag[b]) * basis[b * M + m];
+        c[m] = acc;
+    }
+    h[0] = expl(c[0]);
+    for (int n = 1; n < M; ++n) {
+        long double acc = 0;
+        for (int k = 1; k <= n; ++k) acc += k * c[k] * h[n - k];
+        h[n] = acc / n;
+    }
+}
+
+static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
+static double uniform() {                                                   // xorshift64*, in [0, 1)
+    g_rng ^= g_rng >> 12; g_rng ^= g_rng << 25; g_rng ^= g_rng >> 27;
+    return (double)((g_rng * 0x2545f4914f6cdd1dull) >> 11) / 9007199254740992.0;
+}
+
+static double filter_section() {
+    const double floor = std::log(1e-6);
+    double worst = 0.0;
+    for (int M : {1, 5, 32, 33, 64})
+        for (int n_bands : {1, 6, 16}) {
+            // a smooth, decaying stand-in for a cepstral basis (the real one comes from Python in part 3)
+            std::vector<double> basis((size_t)n_bands * M);
+            for (int b = 0; b < n_bands; ++b)
+                for (int m = 0; m < M; ++m)
+                    basis[(size_t)b * M + m] = m == 0 ? 1.0 / n_bands : std::cos(0.37 * (b + 1) * m) / ((m + 1.0) * n_bands);
+            for (int trial = 0; trial < 24; ++trial) {
+                std::vector<double> L(n_bands);
+                for (int b = 0; b < n_bands; ++b)
+                    L[b] = trial == 0 ? 0.0 : trial == 1 ? floor : trial == 2 ? 2.0 * floor : trial == 3 ? (b & 1 ? floor : 0.0)
+                                                                                                          : floor * uniform();
+                std::vector<long double> want(M);
+                restated(L.data(), basis.data(), n_bands, M, floor, want.data());
+                for (long stride : {1L, 64L, 65L}) {                         // unit stride, and the kernel's lane strides
+                    std::vector<double> c((size_t)M * stride, -7.0), h((size_t)M * stride, -7.0);
+                    bas_design_filter(L.data(), basis.data(), n_bands, M, floor, c.data(), stride, h.data(), stride);
+                    long double num = 0, den = 0;
+                    for (int m = 0; m < M; ++m) {
+                        const long double d = (long double)(float)h[(size_t)m * stride] - want[m];
+                        num += d * d;
+                        den += want[m] * want[m];
+                    }
+                    const double err = (double)sqrtl(num / den);
+                    if (err > worst) worst = err;
+                    ++g_checks;
+                    bool ok = err <= 1e-5;
+                    for (size_t i = 0; i < h.size(); ++i)                     // nothing written between the lanes' elements
+                        if (i % stride && (h[i] != -7.0 || c[i] != -7.0)) ok = false;
+                    if (trial == 0 && (h[0] != 1.0 || (M > 1 && h[(size_t)stride] != 0.0))) ok = false;   // ln 1: a delta
+                    if (!ok && ++g_fail <= 40)
+                        fprintf(stderr, "hostsan_design: FAIL filter M=%d n_bands=%d trial=%d stride=%ld: error %.3e\n", M,
+                                n_bands, trial, stride, err);
+                }
+            }
+        }
+    return worst;
+}
+
+// ---- part 3: a filter bank for the Python tests ---------------------------------------------------------------------
+static int design_file(const char *in_path, const char *out_path) {
+    FILE *in = fopen(in_path, "rb");
+    if (!in) return 2;
+    int32_t dims[3];
+    double floor;
+    if (fread(dims, sizeof(int32_t), 3, in) != 3 || fread(&floor, sizeof(double), 1, in) != 1) { fclose(in); return 2; }
+    const int n_bands = dims[0], M = dims[1], n = dims[2];
+    if (n_bands < 1 || n_bands > BAS_DESIGN_MAX_BANDS || M < 1 || M > BAS_DESIGN_MAX_TAPS || n < 0 || n > (1 << 20)) {
+        fclose(in);
+        return 2;
+    }
+    std::vector<double> basis((size_t)n_bands * M), L((size_t)n * n_bands), c(M), h(M);
+    const bool read = fread(basis.data(), sizeof(double), basis.size(), in) == basis.size() &&
+                      fread(L.data(), sizeof(double), L.size(), in) == L.size();
+    fclose(in);
+    if (!read) return 2;
+    std::vector<float> taps((size_t)n * M);
+    for (int i = 0; i < n; ++i) {
+        bas_design_filter(L.data() + (size_t)i * n_bands, basis.data(), n_bands, M, floor, c.data(), 1, h.data(), 1);
+        for (int m = 0; m < M; ++m) taps[(size_t)i * M + m] = (float)h[m];
+    }
+    FILE *out = fopen(out_path, "wb");
+    if (!out) return 2;
+    const bool wrote = fwrite(taps.data(), sizeof(float), taps.size(), out) == taps.size();
+    return fclose(out) == 0 && wrote ? 0 : 2;
+}
+
+int main(int argc, char **argv) {
+    int n_dev = 0;
+    const hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e == hipSuccess && n_dev > 0) {
+        printf("hostsan_design: refused: %d GPU device(s) visible - sanitized host code never drives a GPU; hide them "
+               "(HIP_VISIBLE_DEVICES=-1)\n", n_dev);
+        return 77;
+    }
+    (void)hipGetLastError();
+    if (argc == 4 && strcmp(argv[1], "design") == 0) return design_file(argv[2], argv[3]);
+    bands_section();
+    const int after_bands = g_checks;
+    design_section();
+    const int after_design = g_checks;
+    const double worst = filter_section();
+    printf("hostsan_design: bas_scene_params_bands_f64 %d checks, bas_color_design_f32 %d checks, bas_design_filter %d "
+           "checks (worst norm-relative error %.3e), %d failed\n", after_bands, after_design - after_bands,
+           g_checks - after_design, worst, g_fail);
+    printf("hostsan_design: %s\n", g_fail ? "FAILED" : "ok");
+    return g_fail ? 1 : 0;
+}
