@@ -309,7 +309,10 @@ def test_entry_points_are_declared_listed_and_exported():
         assert hdr.count(f"int {name}(") == 1 and name in bas._hip.SIGNATURES and getattr(lib, name) is not None
     assert "#define BAS_ABI_VERSION 7" in hdr and bas._hip.ABI_VERSION == 7          # additive: the version stays
     mk = open(os.path.join(ROOT, "binaural-audio-synthesis_amd", "csrc", "Makefile")).read()
-    assert "bas_design.hip" in mk and mk.count("bas_design.h ") >= 3 and "hostsan_design" in mk
+    hdrs = [line for line in mk.splitlines() if line.startswith("HDRS =")]            # the one header list: both libraries, hostsan
+    assert "bas_design.hip" in mk and len(hdrs) == 1 and "bas_design.h " in hdrs[0] and "hostsan_design" in mk
+    for rule in ("%.o: %.hip", "libbas_hip_diag.so: $(SRCS)", "$(HOSTSAN_OUT)/asan/%.o: %.hip"):
+        assert rule + " $(HDRS)\n" in mk, rule
     hdr_d = open(os.path.join(ROOT, "binaural-audio-synthesis_amd", "csrc", "bas_design.h")).read()
     assert "__host__ __device__ inline void bas_design_filter" in hdr_d
 

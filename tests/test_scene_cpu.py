@@ -212,7 +212,9 @@ def test_entry_point_is_declared_listed_and_exported():
     assert getattr(bas._hip.lib(), name) is not None
     assert "#define BAS_ABI_VERSION 7" in hdr and bas._hip.ABI_VERSION == 7          # additive: the version stays
     mk = open(os.path.join(ROOT, "binaural-audio-synthesis_amd", "csrc", "Makefile")).read()
-    assert "bas_scene.hip" in mk and mk.count("bas_scene.h ") >= 2                    # both libraries depend on the header
+    hdrs = [line for line in mk.splitlines() if line.startswith("HDRS =")]
+    assert "bas_scene.hip" in mk and len(hdrs) == 1 and "bas_scene.h " in hdrs[0]
+    assert "%.o: %.hip $(HDRS)\n" in mk and "libbas_hip_diag.so: $(SRCS) $(HDRS)\n" in mk   # both libraries depend on the header
     assert bas.scene is scene and bas.render_scene is scene.render_scene
     assert bas.SceneStreamRenderer is scene.SceneStreamRenderer
 

@@ -5,6 +5,7 @@
 #    for everything else) and tools/ubench_unit_NAME (tools/ubench_unit_block.hip on the same variant).  Both git-ignored.
 # VARIANT_DEFS: further definitions for bas_fused_split.hip, e.g. VARIANT_DEFS=-DFS_TAPS_ONCE=0 for variants of the block that
 # reads every tap twice (ffa_unitp_asm: --notaps, --taps-once-probe ...; the shipped kernel runs ffa_unitp1_asm).
+# --spread=N wants --roll=0 with it (round 3's block is the only one with that schedule; the generator refuses it alone).
 set -e
 cd "$(dirname "$0")/.."
 C=binaural-audio-synthesis_amd/csrc

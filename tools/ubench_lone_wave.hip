@@ -1,6 +1,7 @@
 // Micro-benchmark: the assembly row step of the fused kernels (bas_fir_asm.inc) run by ONE wave per SIMD and by two, to see
 // what a wave that has its SIMD to itself pays for the non-VALU instructions of the block (LDS reads, waits, mask branches,
-// alignment padding).  FIR_INC = a variant written by tools/gen_fir_asm.py (--nowait, --nobranch, --notaps, --nox, --noalign).
+// alignment padding).  FIR_INC = a variant written by tools/gen_fir_asm.py (--generic, --nobranch; and the leave-out switches,
+// which the row step honours like every block: --nowait, --notaps, --nox, --noalign, --noform, --fma-keep=K).
 //   hipcc -O3 --offload-arch=gfx950 -DFIR_INC='"/tmp/v_full.inc"' tools/ubench_lone_wave.hip -o ubench_lone_full
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -2,7 +2,8 @@
 // one (tile, source) unit, 3 605 vector instructions, 296 ds_read_b128, 35 waits) run by the four filter waves of a workgroup,
 // one per SIMD, on LDS data - alone, or with four partner waves that issue a stager's worth of vector instructions beside
 // them (PARTNER_VALU per unit, in bursts between s_sleep).  FIR_INC = a variant written by tools/gen_fir_asm.py
-// (--spread=N, --two-waits, --nowait, --notaps, --nox, --noalign).  Clocks per unit say what the filter stream costs with
+// (--roll=N, --two-waits, --roll=0 --spread=N: the spread exists in round 3's block only; and the leave-out switches, which
+// act on every block: --nowait, --notaps, --nox, --noalign, --noform, --fma-keep=K).  Clocks per unit say what the filter stream costs with
 // nothing else in the way; the kernel-level A/B (tools/ab_fir.py) decides.
 //   hipcc -O3 --offload-arch=gfx950 -DFIR_INC='"/tmp/v.inc"' tools/ubench_unit_block.hip -o ubench_unit_v
 #include <hip/hip_runtime.h>
