@@ -143,6 +143,17 @@ SIGNATURES = {
                                             _c_long, _c_void_p]),
     "bas_color_design_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_int, _c_int, ctypes.c_double,
                                       _c_int, _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_long, _c_void_p]),
+    # screens: occlusion and edge diffraction: the bands entry's list with (screens, transmission, its
+    # screen stride, fresnel, n_screens) in front of the outputs
+    "bas_scene_params_occluded_f64": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long,
+                                               ctypes.c_double, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long,
+                                               _c_void_p, _c_long, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_int,
+                                               _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long,
+                                               _c_void_p, _c_void_p, _c_int, ctypes.c_double, _c_void_p, _c_void_p, _c_long,
+                                               _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_long, _c_long,
+                                               _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long,
+                                               _c_void_p]),
     # late reverberation
     "bas_bus_mix_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_int, _c_long,
                                  _c_int, _c_void_p, _c_long, _c_void_p]),

@@ -9,6 +9,7 @@
 struct BasScenePoint {
     double el, az, gain, delay;
     double r, cos_theta;        // path length and emission angle's cosine (directed only)
+    double qx, qy, qz;          // the image's position after steps 1 and 1b: the path's far end (screens)
 };
 
 // p: the source, l: the listener (world frame, metres).  room: L = the shoebox's size and m = the image's index per axis
@@ -70,6 +71,7 @@ __device__ __forceinline__ BasScenePoint bas_scene_point(double px, double py, d
     o.gain = sgain * igain * r_ref / fmax(r, r_ref);
     o.delay = fmax(fmin(r * spm, dmax), dmin);
     o.r = r;
+    o.qx = px; o.qy = py; o.qz = pz;
     o.cos_theta = 1.0;
     if (directed) {
         const double n = sqrt(ow * ow + ox * ox + oy * oy + oz * oz);

@@ -4,6 +4,7 @@
 // place.  One launch.
 #include "bas_internal.h"
 #include "bas_scene.h"
+#include "bas_occlude.h"
 
 #include <string.h>
 
@@ -30,11 +31,24 @@ struct BasSceneArgs {
     double *logmag; long l_g, l_s, l_c;
 };
 
+// bas_scene_params_occluded_f64's kernel also takes the screens every path is held against; the other two
+// keep the argument block they had
+struct BasSceneOccArgs : BasSceneArgs {
+    BasOccludeScreens scr;
+};
+
 // one thread per (g, s, i, c) item, c fastest (the stores of a wave are consecutive along c), grid-stride.  BANDS: the
 // item's n_bands log-magnitudes follow, L[b] = ln W_i[b] - air[b] r + ln max(|a_b + (1 - a_b) cos theta|, floor), floored
 // at ln floor, n_bands consecutive doubles per thread (the threads of a wave tile a consecutive range where l_c = n_bands)
-template <bool BANDS>
-__global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneArgs A, long n_items) {
+// MODE: SC_PLAIN (no bands), SC_BANDS, SC_SCREENS (the bands, and the screens' term in them: + bas_occlude_sum before the
+// floor).  The first two are the kernels they were before the third existed: what SC_SCREENS adds is compiled out of them.
+enum { SC_PLAIN = 0, SC_BANDS = 1, SC_SCREENS = 2 };
+template <int MODE> struct ScArgs { typedef BasSceneArgs type; };
+template <> struct ScArgs<SC_SCREENS> { typedef BasSceneOccArgs type; };
+
+template <int MODE>
+__global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(typename ScArgs<MODE>::type A, long n_items) {
+    constexpr bool BANDS = MODE != SC_PLAIN;
     const long per_s = (long)A.n_img * A.nb, per_g = per_s * A.n_src;
     const bool room = A.room_size != nullptr;
     double Lx = 0.0, Ly = 0.0, Lz = 0.0;
@@ -80,7 +94,33 @@ __global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneAr
                                                 b[2], A.spc, room, Lx, Ly, Lz, mx, my, mz, A.head != nullptr,
                                                 w, x, y, z, sg, ig, A.spm, A.r_ref, A.dmin, A.dmax, BANDS, ow, ox, oy, oz);
         const long row = s * A.n_img + i;
-        if (BANDS) {
+        if constexpr (MODE == SC_SCREENS) {
+#pragma clang fp contract(off)
+            // (the four results first: they need not stay in registers through the screens)
+            const long to = g * A.a_g + row * A.a_s + c;
+            A.elev[to] = o.el;
+            A.azim[to] = o.az;
+            if (A.gain) A.gain[to] = o.gain;
+            if (A.delay) A.delay[g * A.d_g + row * A.d_s + c] = o.delay;
+            double occ[SC_MAX_BANDS];
+#pragma unroll
+            for (int k = 0; k < SC_MAX_BANDS; ++k) occ[k] = 0.0;
+            bas_occlude_sum(A.scr, o.qx, o.qy, o.qz, lx, ly, lz, room, Lx, Ly, Lz, mx, my, mz, occ);
+            double *L = A.logmag + g * A.l_g + row * A.l_s + c * A.l_c;
+            const double ln_floor = log(A.floor);
+            for (int bd = 0; bd < A.n_bands; ++bd) {
+                double v = A.img_logmag ? A.img_logmag[i * A.n_bands + bd] : 0.0;
+                if (A.air) v = v - A.air[bd] * o.r;
+                if (A.pattern) {
+                    const double al = A.pattern[s * A.pt_s + bd];
+                    v = v + log(fmax(fabs(al + (1.0 - al) * o.cos_theta), A.floor));
+                }
+                double ob = 0.0;
+#pragma unroll
+                for (int k = 0; k < SC_MAX_BANDS; ++k) ob = k == bd ? occ[k] : ob;
+                L[bd] = fmax(v + ob, ln_floor);
+            }
+        } else if (BANDS) {
 #pragma clang fp contract(off)
             double *L = A.logmag + g * A.l_g + row * A.l_s + c * A.l_c;
             const double ln_floor = log(A.floor);
@@ -94,6 +134,7 @@ __global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(BasSceneAr
                 L[bd] = fmax(v, ln_floor);
             }
         }
+        if (MODE == SC_SCREENS) continue;
         const long to = g * A.a_g + row * A.a_s + c;
         A.elev[to] = o.el;
         A.azim[to] = o.az;
@@ -114,10 +155,14 @@ struct BasSceneBands {
     const double *air, *img_logmag;
     int n_bands; double floor;
     double *logmag; long l_g, l_s, l_c;
+    // bas_scene_params_occluded_f64 only (fn names it: occluded)
+    bool occluded;
+    const double *screens, *transmission; long t_s;
+    const double *fresnel; int n_screens;
 };
 
-// The launcher both entry points share (B == nullptr: bas_scene_params_f64, the kernel without the bands): every check,
-// then one launch.
+// The launcher the three entry points share (B == nullptr: bas_scene_params_f64, the kernel without the bands;
+// B->occluded: bas_scene_params_occluded_f64, the bands with the screens): every check, then one launch.
 static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
                      const double *pos_prev, long prev_stride_g, long prev_stride_s, double samples_per_chunk,
                      const double *lpos, long lpos_stride_g, long lpos_stride_c, const double *head, long head_stride_g,
@@ -155,8 +200,9 @@ static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long 
                 sc_aligned(room_size, 8) && sc_aligned(img_gain, 8) && sc_aligned(images, 4) && sc_aligned(elev, 8) &&
                 sc_aligned(azim, 8) && sc_aligned(gain, 8) && sc_aligned(delay, 8), BAS_E_ALIGN,
                 "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
-    BasSceneArgs A;
-    memset(&A, 0, sizeof A);
+    BasSceneOccArgs AO;
+    memset(&AO, 0, sizeof AO);
+    BasSceneArgs &A = AO;
     if (B) {
         BAS_REQUIRE(B->n_bands >= 1 && B->n_bands <= SC_MAX_BANDS, BAS_E_SHAPE, "%s: n_bands (%d) must be in 1..%d", fn,
                     B->n_bands, SC_MAX_BANDS);
@@ -184,6 +230,17 @@ static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long 
         A.pattern = B->pattern; A.pt_s = B->pt_s; A.air = B->air; A.img_logmag = B->img_logmag;
         A.n_bands = B->n_bands; A.floor = B->floor;
         A.logmag = B->logmag; A.l_g = B->l_g; A.l_s = B->l_s; A.l_c = B->l_c;
+        if (B->occluded) {
+            BAS_REQUIRE(B->n_screens >= 1 && B->n_screens <= BAS_OCCLUDE_MAX_SCREENS, BAS_E_SHAPE,
+                        "%s: n_screens (%d) must be in 1..%d", fn, B->n_screens, BAS_OCCLUDE_MAX_SCREENS);
+            BAS_REQUIRE(B->t_s == 0 || B->t_s >= B->n_bands, BAS_E_SHAPE,
+                        "%s: the transmission's screen stride (%ld) must be 0 (shared) or >= n_bands", fn, B->t_s);
+            BAS_REQUIRE(B->screens && B->fresnel, BAS_E_NULL, "%s: null pointer (screens, fresnel)", fn);
+            BAS_REQUIRE(sc_aligned(B->screens, 8) && sc_aligned(B->transmission, 8) && sc_aligned(B->fresnel, 8), BAS_E_ALIGN,
+                        "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
+            AO.scr.screens = B->screens; AO.scr.transmission = B->transmission; AO.scr.fresnel = B->fresnel;
+            AO.scr.t_s = B->t_s; AO.scr.n_screens = B->n_screens; AO.scr.n_bands = B->n_bands;
+        }
     }
     A.pos = pos; A.ps_g = pos_stride_g; A.ps_s = pos_stride_s; A.ps_c = pos_stride_c;
     A.prev = pos_prev; A.pp_g = prev_stride_g; A.pp_s = prev_stride_s; A.spc = samples_per_chunk;
@@ -197,10 +254,12 @@ static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long 
     A.delay = delay; A.d_g = d_stride_g; A.d_s = d_stride_s;
     const long n_items = (long)n_groups * rows * nb;
     const int blocks = bas_grid_for(n_items, 8 * bas_device_cus());
-    if (B)
-        hipLaunchKernelGGL(bas_scene_params_kernel<true>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
+    if (B && B->occluded)
+        hipLaunchKernelGGL(bas_scene_params_kernel<SC_SCREENS>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), AO, n_items);
+    else if (B)
+        hipLaunchKernelGGL(bas_scene_params_kernel<SC_BANDS>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
     else
-        hipLaunchKernelGGL(bas_scene_params_kernel<false>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
+        hipLaunchKernelGGL(bas_scene_params_kernel<SC_PLAIN>, dim3(blocks), dim3(SC_THREADS), 0, bas_stream(stream), A, n_items);
     return bas_check_launch(fn);
 }
 
@@ -235,8 +294,34 @@ extern "C" int bas_scene_params_bands_f64(const double *pos, long pos_stride_g, 
                                           long a_stride_s, double *delay, long d_stride_g, long d_stride_s, double *logmag,
                                           long l_stride_g, long l_stride_s, long l_stride_c, bas_stream_t stream) {
     const BasSceneBands B = {orient, orient_stride_g, orient_stride_s, orient_stride_c, pattern, pattern_stride_s, air,
-                             img_logmag, n_bands, floor, logmag, l_stride_g, l_stride_s, l_stride_c};
+                             img_logmag, n_bands, floor, logmag, l_stride_g, l_stride_s, l_stride_c, false, nullptr, nullptr,
+                             0, nullptr, 0};
     return sc_launch("bas_scene_params_bands_f64", pos, pos_stride_g, pos_stride_s, pos_stride_c, pos_prev, prev_stride_g,
+                     prev_stride_s, samples_per_chunk, lpos, lpos_stride_g, lpos_stride_c, head, head_stride_g,
+                     head_stride_c, src_gain, sg_stride_g, sg_stride_s, room_size, images, img_gain, n_img,
+                     samples_per_metre, r_ref, d_min, d_max, n_groups, n_src, nb, elev, azim, gain, a_stride_g, a_stride_s,
+                     delay, d_stride_g, d_stride_s, &B, stream);
+}
+
+extern "C" int bas_scene_params_occluded_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                                             const double *pos_prev, long prev_stride_g, long prev_stride_s,
+                                             double samples_per_chunk, const double *lpos, long lpos_stride_g,
+                                             long lpos_stride_c, const double *head, long head_stride_g, long head_stride_c,
+                                             const double *src_gain, long sg_stride_g, long sg_stride_s,
+                                             const double *room_size, const int32_t *images, const double *img_gain,
+                                             int n_img, double samples_per_metre, double r_ref, double d_min, double d_max,
+                                             int n_groups, int n_src, int nb, const double *orient, long orient_stride_g,
+                                             long orient_stride_s, long orient_stride_c, const double *pattern,
+                                             long pattern_stride_s, const double *air, const double *img_logmag, int n_bands,
+                                             double floor, const double *screens, const double *transmission,
+                                             long transmission_stride_s, const double *fresnel, int n_screens, double *elev,
+                                             double *azim, double *gain, long a_stride_g, long a_stride_s, double *delay,
+                                             long d_stride_g, long d_stride_s, double *logmag, long l_stride_g,
+                                             long l_stride_s, long l_stride_c, bas_stream_t stream) {
+    const BasSceneBands B = {orient, orient_stride_g, orient_stride_s, orient_stride_c, pattern, pattern_stride_s, air,
+                             img_logmag, n_bands, floor, logmag, l_stride_g, l_stride_s, l_stride_c, true, screens,
+                             transmission, transmission_stride_s, fresnel, n_screens};
+    return sc_launch("bas_scene_params_occluded_f64", pos, pos_stride_g, pos_stride_s, pos_stride_c, pos_prev, prev_stride_g,
                      prev_stride_s, samples_per_chunk, lpos, lpos_stride_g, lpos_stride_c, head, head_stride_g,
                      head_stride_c, src_gain, sg_stride_g, sg_stride_s, room_size, images, img_gain, n_img,
                      samples_per_metre, r_ref, d_min, d_max, n_groups, n_src, nb, elev, azim, gain, a_stride_g, a_stride_s,

@@ -35,6 +35,12 @@ source's directivity towards the listener (sources have an orientation, `orient`
 kernel then also writes every row's band log-magnitudes (`scene_color_params`: the definition; bas_scene_params_bands_f64),
 and a second launch designs a minimum-phase FIR per (row, boundary) from them (propagation.design_colors_device), which the
 colour launch applies in its per-boundary form; a banded room's walls are then among the log-magnitudes.
+A colour may also hold `Screens` (§3.19): up to 32 static thin rectangles - partitions, pillars, the wall beside a doorway.
+Every straight path from an image to the listener is held against every screen (in a room: against its mirror copies in the
+cells the unfolded path runs through); a screen it crosses attenuates each band by the Kurze-Anderson diffraction loss of the
+least detour round its edges, a screen it passes close by a little less than that, and the sum of ln M[b] is one more term
+of the log-magnitudes (`occlusion_logmag`: the definition; bas_scene_params_occluded_f64).  Gain, delay and direction stay
+those of the straight path.
 """
 import numpy as np
 
@@ -42,6 +48,7 @@ from . import _hip, sphere, propagation, reverb
 
 MAX_ORDER = 3
 SPEED_OF_SOUND = 343.0
+MAX_SCREENS = 32
 
 
 def shoebox_images(order):
@@ -256,8 +263,9 @@ def scene_params(pos, fs, listener_pos=None, head=None, room=None, src_gain=None
 
 
 def _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, chunksize, pos_prev):
-    """scene_params' body; returns its four arrays and, for scene_color_params, the path length r and the vector v = q - l
-    of step 2 (before the head turns it), float64 (..., n_src, n_img, nb) and (..., n_src, n_img, nb, 3)."""
+    """scene_params' body; returns its four arrays and, for scene_color_params, the path length r, the vector v = q - l
+    of step 2 (before the head turns it) and the path's ends q and l themselves, float64 (..., n_src, n_img, nb) and three
+    times (..., n_src, n_img, nb, 3)."""
     spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
     if any(_is_device(a) for a in (pos, listener_pos, head, src_gain)):
         raise ValueError("scene_params takes host arrays (scene_params_device takes device tensors)")
@@ -312,7 +320,7 @@ def _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
     delay = np.fmax(np.fmin(r * spm, d_max), d_min)
     shape = r.shape[:-3] + (r.shape[-3] * r.shape[-2], r.shape[-1])
     return tuple(np.ascontiguousarray(np.broadcast_to(a, r.shape)).reshape(shape) for a in (el, az, gain, delay)) \
-        + (r, np.broadcast_to(v, r.shape + (3,)))
+        + (r, np.broadcast_to(v, r.shape + (3,)), np.broadcast_to(p, r.shape + (3,)), np.broadcast_to(l, r.shape + (3,)))
 
 
 def air_absorption(freqs, temperature=20.0, humidity=50.0, pressure=101.325):
@@ -334,6 +342,203 @@ def air_absorption(freqs, temperature=20.0, humidity=50.0, pressure=101.325):
         0.01275 * np.exp(-2239.1 / T) / (frO + f * f / frO) + 0.1068 * np.exp(-3352.0 / T) / (frN + f * f / frN)))
 
 
+class Screens:
+    """Static thin rectangles that occlude and diffract.  centre, half_u, half_v: [n, 3] in metres (world
+    frame): screen k spans centre[k] + a half_u[k] + b half_v[k] for |a|, |b| <= 1; 1..32 screens, finite, both half-edges
+    non-zero and orthogonal to within 1e-9 |half_u| |half_v|.  transmission: None (opaque), [n_bands] (all screens alike) or
+    [n, n_bands] magnitudes in [0, 1] of what passes through the screen itself.  ValueError otherwise."""
+
+    def __init__(self, centre, half_u, half_v, transmission=None):
+        arrs = []
+        for name, a in (("centre", centre), ("half_u", half_u), ("half_v", half_v)):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] != 3 or not np.isfinite(a).all():
+                raise ValueError(f"{name} must be finite [n, 3]")
+            arrs.append(a)
+        c, e1, e2 = arrs
+        if not 1 <= c.shape[0] <= MAX_SCREENS or e1.shape != c.shape or e2.shape != c.shape:
+            raise ValueError(f"centre, half_u and half_v must hold the same 1..{MAX_SCREENS} screens")
+        n1, n2 = np.sqrt((e1 * e1).sum(axis=1)), np.sqrt((e2 * e2).sum(axis=1))
+        if not (n1 > 0).all() or not (n2 > 0).all():
+            raise ValueError("half_u and half_v must be non-zero")
+        if not (np.abs((e1 * e2).sum(axis=1)) <= 1e-9 * n1 * n2).all():
+            raise ValueError("half_u and half_v must be orthogonal")
+        self.centre, self.half_u, self.half_v, self.n = c, e1, e2, c.shape[0]
+        if transmission is not None:
+            transmission = np.asarray(transmission, dtype=np.float64)
+            if transmission.ndim not in (1, 2) or transmission.shape[-1] < 1 \
+                    or (transmission.ndim == 2 and transmission.shape[0] != self.n) \
+                    or not np.isfinite(transmission).all() or not ((transmission >= 0) & (transmission <= 1)).all():
+                raise ValueError("transmission must be None, [n_bands] or [n, n_bands] magnitudes in [0, 1]")
+        self.transmission = transmission
+
+    def table(self):
+        """float64 [n, 9]: centre, half_u, half_v of every screen (bas_scene_params_occluded_f64's `screens`)."""
+        return np.ascontiguousarray(np.concatenate([self.centre, self.half_u, self.half_v], axis=1))
+
+    def corners(self):
+        """float64 [n, 4, 3]: centre -+ half_u -+ half_v."""
+        return np.stack([self.centre + a * self.half_u + b * self.half_v for a in (-1.0, 1.0) for b in (-1.0, 1.0)], axis=1)
+
+    def check(self, n_bands, room=None):
+        """ValueError unless the transmission (if any) has n_bands bands and, with a room, every corner lies inside it (the
+        unfolded test is only then exact for "does the reflected path cross the real screen")."""
+        _n_img(room)
+        if self.transmission is not None and self.transmission.shape[-1] != int(n_bands):
+            raise ValueError(f"the screens' transmission has {self.transmission.shape[-1]} bands, not {int(n_bands)}")
+        if room is not None:
+            k = self.corners()
+            if (k < 0).any() or (k > room.size).any():
+                raise ValueError(f"every corner of every screen must lie inside the room [0, {tuple(room.size)}]")
+
+
+_TWO_PI = 6.283185307179586                                            # bas_occlude.h's constants
+_NEPERS_PER_DB = 0.11512925464970229                                   # ln 10 / 20
+
+
+def screen_attenuation(N):
+    """The diffraction loss A(N) in dB of a thin screen at Fresnel number N (Kurze-Anderson, continued into the lit zone
+    N < 0): with x = sqrt(2 pi |N|), min(5 + 20 log10(x / tanh x), 24) for N >= 0, max(5 + 20 log10(x / tan x), 0) for
+    -0.2 < N < 0, 0 for N <= -0.2.  5 dB at the shadow boundary, continuous with a continuous slope there."""
+    N = np.asarray(N, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        x = np.sqrt(_TWO_PI * N)
+        shadow = np.fmin(5.0 + 20.0 * np.log10(np.where(x == 0.0, 1.0, x / np.tanh(x))), 24.0)
+        x = np.sqrt(_TWO_PI * -N)
+        lit = np.fmax(5.0 + 20.0 * np.log10(x / np.tan(x)), 0.0)
+    return np.where(N >= 0.0, shadow, np.where(N > -0.2, lit, 0.0))
+
+
+def edge_path(q, l, A, B):
+    """The least of |q - P| + |P - l| over the points P of the segment from A to B, in closed form (all [..., 3],
+    broadcast): with t the coordinate along the edge and d the distance from its line the sum is convex in t, least at
+    t* = t_q + (t_l - t_q) d_q / (d_q + d_l) (the midpoint where d_q + d_l = 0), clamped to [0, |B - A|]."""
+    q, l, A, B = (np.asarray(a, dtype=np.float64) for a in (q, l, A, B))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dx, dy, dz = B[..., 0] - A[..., 0], B[..., 1] - A[..., 1], B[..., 2] - A[..., 2]
+        ln = np.sqrt(dx * dx + dy * dy + dz * dz)
+        ux, uy, uz = dx / ln, dy / ln, dz / ln
+        qax, qay, qaz = q[..., 0] - A[..., 0], q[..., 1] - A[..., 1], q[..., 2] - A[..., 2]
+        lax, lay, laz = l[..., 0] - A[..., 0], l[..., 1] - A[..., 1], l[..., 2] - A[..., 2]
+        tq = qax * ux + qay * uy + qaz * uz
+        tl = lax * ux + lay * uy + laz * uz
+        wqx, wqy, wqz = qax - tq * ux, qay - tq * uy, qaz - tq * uz
+        wlx, wly, wlz = lax - tl * ux, lay - tl * uy, laz - tl * uz
+        dq = np.sqrt(wqx * wqx + wqy * wqy + wqz * wqz)
+        dl = np.sqrt(wlx * wlx + wly * wly + wlz * wlz)
+        ds = dq + dl
+        ts = np.where(ds == 0.0, 0.5 * (tq + tl), tq + (tl - tq) * dq / ds)
+        ts = np.fmin(np.fmax(ts, 0.0), ln)
+        return np.hypot(dq, ts - tq) + np.hypot(dl, ts - tl)
+
+
+def screen_sides(q, l, c, e1, e2):
+    """s_q s_l < 0 for n = e1 x e2, s_q = n.(q - c), s_l = n.(l - c): the ends of q -> l lie strictly on opposite sides of
+    the screen's plane (all [..., 3], broadcast).  The model's one discontinuity."""
+    q, l, c, e1, e2 = (np.asarray(a, dtype=np.float64) for a in (q, l, c, e1, e2))
+    X, Y, Z = (..., 0), (..., 1), (..., 2)
+    with np.errstate(invalid="ignore", over="ignore"):
+        nx = e1[Y] * e2[Z] - e1[Z] * e2[Y]
+        ny = e1[Z] * e2[X] - e1[X] * e2[Z]
+        nz = e1[X] * e2[Y] - e1[Y] * e2[X]
+        sq = nx * (q[X] - c[X]) + ny * (q[Y] - c[Y]) + nz * (q[Z] - c[Z])
+        sl = nx * (l[X] - c[X]) + ny * (l[Y] - c[Y]) + nz * (l[Z] - c[Z])
+        return sq * sl < 0.0
+
+
+def screen_detour(q, l, c, e1, e2):
+    """One screen (copy) against straight paths q -> l (all [..., 3], broadcast): (crossed, sd).  crossed: the ends lie
+    strictly on opposite sides of the screen's plane (s_q s_l < 0); sd: the signed detour in metres where crossed (+ delta:
+    the hit point lies on the rectangle, the path is blocked; - delta: it passes beside it), undefined elsewhere.
+    bas_occlude.h's bas_occlude_detour, expression for expression."""
+    q, l, c, e1, e2 = (np.asarray(a, dtype=np.float64) for a in (q, l, c, e1, e2))
+    X, Y, Z = (..., 0), (..., 1), (..., 2)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nx = e1[Y] * e2[Z] - e1[Z] * e2[Y]
+        ny = e1[Z] * e2[X] - e1[X] * e2[Z]
+        nz = e1[X] * e2[Y] - e1[Y] * e2[X]
+        sq = nx * (q[X] - c[X]) + ny * (q[Y] - c[Y]) + nz * (q[Z] - c[Z])
+        sl = nx * (l[X] - c[X]) + ny * (l[Y] - c[Y]) + nz * (l[Z] - c[Z])
+        crossed = sq * sl < 0.0
+        vx, vy, vz = l[X] - q[X], l[Y] - q[Y], l[Z] - q[Z]
+        t = sq / (sq - sl)
+        hx, hy, hz = (q[X] + t * vx) - c[X], (q[Y] + t * vy) - c[Y], (q[Z] + t * vz) - c[Z]
+        a = (hx * e1[X] + hy * e1[Y] + hz * e1[Z]) / (e1[X] * e1[X] + e1[Y] * e1[Y] + e1[Z] * e1[Z])
+        b = (hx * e2[X] + hy * e2[Y] + hz * e2[Z]) / (e2[X] * e2[X] + e2[Y] * e2[Y] + e2[Z] * e2[Z])
+        blocked = (np.abs(a) <= 1.0) & (np.abs(b) <= 1.0)
+        mm, pm, mp, pp = (c - e1) - e2, (c + e1) - e2, (c - e1) + e2, (c + e1) + e2
+        best = np.inf
+        for A, B in ((mm, pm), (mp, pp), (mm, mp), (pm, pp)):
+            best = np.fmin(best, edge_path(q, l, A, B))
+        delta = np.fmax(best - np.sqrt(vx * vx + vy * vy + vz * vz), 0.0)
+    return crossed, np.where(blocked, delta, -delta)
+
+
+def occlusion_logmag(q, l, screens, bands, c=SPEED_OF_SOUND, room=None, images=None):
+    """The screens' term of the band log-magnitudes for straight paths from q to l: the float64 definition (numpy;
+    DESIGN.md §3.19).  q, l: [..., 3] (broadcast against each other), the paths' ends - for a scene, q is the image's
+    position after steps 1 and 1b and l the listener; screens: a Screens; bands: centre frequencies in Hz; c: speed of sound.
+    room, images: None (free field: one copy of every screen), or a Room and the image index m [..., 3] (integers) of every
+    path: q then lies in cell m of the unfolded room, l in cell 0, and the path is held against the mirror copies of every
+    screen in the cells (i, j, k) with each index between 0 and m_a inclusive.  Per crossed copy and band, with the signed
+    detour sd of screen_detour:
+        N = (2 f_b / c) sd,   A = screen_attenuation(N),   M = T_b + (1 - T_b) exp(-A ln 10 / 20)
+    Returns the sum of ln M over screens and copies, float64 [..., n_bands], un-floored (callers of
+    render_sources(color=) add it to their own log-magnitudes).  ValueError for shapes that do not fit."""
+    if not isinstance(screens, Screens):
+        raise ValueError("screens must be a scene.Screens")
+    bands = np.asarray(bands, dtype=np.float64)
+    if bands.ndim != 1 or bands.size < 1 or not np.isfinite(bands).all() or not (bands > 0).all():
+        raise ValueError("bands must be centre frequencies in Hz, > 0")
+    c = float(c)
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError("c must be finite and > 0")
+    screens.check(bands.size, room)
+    q, l = np.asarray(q, dtype=np.float64), np.asarray(l, dtype=np.float64)
+    if q.ndim < 1 or l.ndim < 1 or q.shape[-1] != 3 or l.shape[-1] != 3:
+        raise ValueError("q and l must be [..., 3]")
+    if room is None:
+        if images is not None:
+            raise ValueError("images needs a room")
+        m = np.zeros(3, dtype=np.int64)
+    else:
+        m = np.zeros(3, dtype=np.int64) if images is None else np.asarray(images)
+        if m.ndim < 1 or m.shape[-1] != 3 or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("images must be integers [..., 3]")
+        m = m.astype(np.int64)
+    shape = np.broadcast_shapes(q.shape[:-1], l.shape[:-1], m.shape[:-1])
+    fresnel = 2.0 * bands / c
+    q, l, m = (np.broadcast_to(a, shape + (3,)).reshape(-1, 3) for a in (q, l, m))
+    acc = np.zeros((q.shape[0], bands.size))
+    n_cells = np.abs(m)
+    top = n_cells.max(axis=0) if len(m) else np.zeros(3, dtype=np.int64)
+    for k in range(screens.n):
+        T = 0.0 if screens.transmission is None else \
+            screens.transmission if screens.transmission.ndim == 1 else screens.transmission[k]
+        for ia in range(int(top[0]) + 1):
+            for ja in range(int(top[1]) + 1):
+                for ka in range(int(top[2]) + 1):
+                    here = (ia <= n_cells[:, 0]) & (ja <= n_cells[:, 1]) & (ka <= n_cells[:, 2])
+                    if not here.any():
+                        continue
+                    cc, e1, e2 = (np.broadcast_to(a[k], q.shape) for a in (screens.centre, screens.half_u, screens.half_v))
+                    if room is not None:                               # the copy in cell (i, j, k): the mirror rule of step 1
+                        cell = np.where(m < 0, -1, 1) * np.array([ia, ja, ka])
+                        odd = cell % 2 != 0
+                        cc = cell.astype(np.float64) * room.size + np.where(odd, room.size - cc, cc)
+                        e1, e2 = np.where(odd, -e1, e1), np.where(odd, -e2, e2)
+                    # (the paths whose ends lie on opposite sides alone go on to the edges: element for element the values
+                    # of the whole array)
+                    sel = here & screen_sides(q, l, cc, e1, e2)
+                    if not sel.any():
+                        continue
+                    sd = screen_detour(q[sel], l[sel], cc[sel], e1[sel], e2[sel])[1]
+                    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                        A = screen_attenuation(fresnel * sd[:, None])
+                        acc[sel] = acc[sel] + np.log(T + (1.0 - T) * np.exp(-A * _NEPERS_PER_DB))
+    return acc.reshape(shape + (bands.size,))
+
+
 class SceneColor:
     """What a path does to a source's spectrum besides its walls: air absorption over its length and the
     source's directivity towards the listener, per frequency band, designed into a minimum-phase FIR of `taps` coefficients
@@ -342,9 +547,12 @@ class SceneColor:
     air: None, True (air_absorption(bands) at its defaults) or [n_bands] dB per metre, >= 0.
     directivity: None (omnidirectional), [n_bands] or [n_src, n_bands] first-order pattern coefficients a in [0, 1]:
     D_b(cos theta) = |a_b + (1 - a_b) cos theta| with theta the angle off the source's forward axis (its local +y): 1 omni,
-    0.5 cardioid, 0 figure-of-eight.  With a banded Room, bands and taps must equal the room's.  ValueError otherwise."""
+    0.5 cardioid, 0 figure-of-eight.  With a banded Room, bands and taps must equal the room's.
+    screens: None, or a Screens: occlusion and edge diffraction by static thin rectangles; its
+    transmission must have this colour's bands and, with a room, every corner must lie inside it (check).
+    ValueError otherwise."""
 
-    def __init__(self, bands, taps=32, air=None, directivity=None):
+    def __init__(self, bands, taps=32, air=None, directivity=None, screens=None):
         bands = np.asarray(bands, dtype=np.float64)
         if bands.ndim != 1 or not 1 <= bands.size <= propagation.MAX_BANDS or not np.isfinite(bands).all() \
                 or not (bands > 0).all() or not (np.diff(bands) > 0).all():
@@ -366,7 +574,10 @@ class SceneColor:
                     or not np.isfinite(directivity).all() or not ((directivity >= 0) & (directivity <= 1)).all():
                 raise ValueError("directivity must be None, [n_bands] or [n_src, n_bands] pattern coefficients in [0, 1]")
         self.directivity = directivity
-        self._basis, self._device = {}, {}
+        if screens is not None and not isinstance(screens, Screens):
+            raise ValueError("screens must be None or a scene.Screens")
+        self.screens = screens
+        self._basis, self._device, self._screens_device = {}, {}, {}
 
     def basis(self, fs):
         """propagation.cepstral_basis(bands, fs, taps), cached per fs."""
@@ -377,9 +588,12 @@ class SceneColor:
 
     def check(self, room, n_src):
         """ValueError unless this colour goes with `room` (a banded room's bands and taps are this colour's) and `n_src`
-        sources (per-source patterns: one row each).  Returns the images' wall log-magnitudes [n_img, n_bands], floored at
-        ln FIR_FLOOR, or None (no room, or a scalar one: img_gain carries its walls)."""
+        sources (per-source patterns: one row each), and its screens have its bands and lie inside the room.  Returns the
+        images' wall log-magnitudes [n_img, n_bands], floored at ln FIR_FLOOR, or None (no room, or a scalar one: img_gain
+        carries its walls)."""
         _n_img(room)
+        if self.screens is not None:
+            self.screens.check(self.bands.size, room)
         if self.directivity is not None and self.directivity.ndim == 2 and self.directivity.shape[0] != int(n_src):
             raise ValueError(f"directivity has {self.directivity.shape[0]} rows for {n_src} sources")
         if room is None or room.bands is None:
@@ -400,6 +614,21 @@ class SceneColor:
             self._device[key] = tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
                                       for a in (pat, self.air_nepers, lnw, self.basis(fs)))
         return self._device[key]
+
+
+    def screen_arrays(self, dev, c=SPEED_OF_SOUND):
+        """The screens on `dev` for speed of sound c: (table [n, 9], transmission [n or 1, n_bands] or None (opaque),
+        fresnel [n_bands] = 2 f_b / c) as float64 tensors, uploaded once per (device, c).  ValueError without screens."""
+        import torch
+        if self.screens is None:
+            raise ValueError("screen_arrays: the colour has no screens")
+        key = (str(dev), float(c))
+        if key not in self._screens_device:
+            T = self.screens.transmission
+            arrs = (self.screens.table(), None if T is None else np.atleast_2d(T), 2.0 * self.bands / float(c))
+            self._screens_device[key] = tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                                              for a in arrs)
+        return self._screens_device[key]
 
 
 def _check_color(color, room, n_src):
@@ -432,15 +661,16 @@ def scene_color_params(pos, fs, listener_pos=None, head=None, room=None, src_gai
     source radiates along its local +y; an image's forward axis is the source's with component a negated where m_a is odd.
     With q the image's position of steps 1-1b, v = q - l and r = |v| (unclamped, whatever max_delay):
         cos theta = -(f . v) / r   (r == 0: 1),     D_b = |a_b + (1 - a_b) cos theta|
-        L[b] = max(ln max(W_i[b], FLOOR) - (ln 10 / 20) air[b] r + ln max(D_b, FLOOR), ln FLOOR)
-    with FLOOR = propagation.FIR_FLOOR and W_i the image's wall magnitudes of a banded room (1 otherwise: a scalar room's
-    walls stay in the gain).  Returns (elev, azim, gain, delay, logmag): scene_params' four, bit for bit, and logmag
+        L[b] = max(ln max(W_i[b], FLOOR) - (ln 10 / 20) air[b] r + ln max(D_b, FLOOR) + S[b], ln FLOOR)
+    with FLOOR = propagation.FIR_FLOOR, W_i the image's wall magnitudes of a banded room (1 otherwise: a scalar room's
+    walls stay in the gain) and S the screens' term occlusion_logmag(q, l, ..) of a colour with screens (DESIGN.md §3.19;
+    without them nothing is added: the bits of a colour that never had any).  Returns (elev, azim, gain, delay, logmag): scene_params' four, bit for bit, and logmag
     float64 (..., n_src n_img, nb, n_bands)."""
     lnw = _check_color(color, room, np.shape(pos)[-3] if len(np.shape(pos)) >= 3 else 0)
     if _is_device(orient):
         raise ValueError("scene_color_params takes host arrays (scene_color_params_device takes device tensors)")
-    el, az, gain, delay, r, v = _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay,
-                                              chunksize, pos_prev)
+    el, az, gain, delay, r, v, q, l = _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
+                                                    max_delay, chunksize, pos_prev)
     o = _check_orient(orient, np.shape(pos))
     floor = propagation.FIR_FLOOR
     L = np.zeros(r.shape + (color.bands.size,))
@@ -464,6 +694,9 @@ def scene_color_params(pos, fs, listener_pos=None, head=None, room=None, src_gai
             cos = np.where(r == 0.0, 1.0, -dot / r)
         a = color.directivity if color.directivity.ndim == 1 else color.directivity[:, None, None, :]
         L = L + np.log(np.maximum(np.abs(a + (1.0 - a) * cos[..., None]), floor))
+    if color.screens is not None:
+        L = L + occlusion_logmag(q, l, color.screens, color.bands, c, room,
+                                 None if room is None else room.images[:, None, :])
     L = np.maximum(L, np.log(floor))
     shape = r.shape[:-3] + (r.shape[-3] * r.shape[-2], r.shape[-1], color.bands.size)
     return el, az, gain, delay, np.ascontiguousarray(L).reshape(shape)
@@ -489,7 +722,8 @@ def scene_params_device(pos, fs, listener_pos=None, head=None, room=None, src_ga
 def scene_color_params_device(pos, fs, listener_pos=None, head=None, room=None, src_gain=None, c=SPEED_OF_SOUND, r_ref=1.0,
                               interp="cubic", max_delay=None, out=None, chunksize=None, pos_prev=None, color=None,
                               orient=None):
-    """scene_color_params on the GPU (bas_scene_params_bands_f64, one launch): scene_params_device's arguments, a
+    """scene_color_params on the GPU (bas_scene_params_bands_f64 - with screens in the colour
+    bas_scene_params_occluded_f64 - one launch): scene_params_device's arguments, a
     SceneColor and orient [(G,) n_src, nb, 4] (a host array validated as head is, or a float64 device tensor).
     out = (elev, azim, gain, delay, logmag): as for scene_params_device, and logmag a float64 device tensor
     [(G,) n_src n_img, nb, n_bands] with unit stride along the bands (required).  Every argument is validated before any
@@ -505,7 +739,8 @@ def scene_color_params_device(pos, fs, listener_pos=None, head=None, room=None, 
 def _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp, max_delay, out, chunksize, pos_prev,
                   color=None, orient=None):
     """The one body of scene_params_device (color None: bas_scene_params_f64, four outputs) and scene_color_params_device
-    (bas_scene_params_bands_f64, five; color and orient checked by the caller)."""
+    (bas_scene_params_bands_f64, or bas_scene_params_occluded_f64 where the colour has screens, five; color and orient
+    checked by the caller)."""
     import torch
     spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
     pos_shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
@@ -551,14 +786,21 @@ def _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
     if color is not None:
         lo = out[4]
         pat, air, lnw, _ = color.device_arrays(dev, fs, room)
+        entry, screens = "bas_scene_params_bands_f64", ()
+        if color.screens is not None:                                  # the screens' five arguments in front of the outputs
+            tab, tr, fres = color.screen_arrays(dev, c)
+            entry = "bas_scene_params_occluded_f64"
+            screens = (_hip.ptr(tab), _hip.ptr(tr), 0 if tr is None or tr.shape[0] == 1 else tr.stride(0), _hip.ptr(fres),
+                       color.screens.n)
         with _hip.on_device(dev):
-            _hip.call("bas_scene_params_bands_f64", _hip.ptr(p), *gs(p, -3), p.stride(-2), _hip.ptr(prev), *gs(prev, -2),
+            _hip.call(entry, _hip.ptr(p), *gs(p, -3), p.stride(-2), _hip.ptr(prev), *gs(prev, -2),
                       spc, _hip.ptr(l), *gs(l, -2), _hip.ptr(q), *gs(q, -2), _hip.ptr(sg), *gs(sg, -2), _hip.ptr(size),
                       _hip.ptr(images), _hip.ptr(gains), n_img, spm, r_ref, d_min, d_max, G, n_src, nb, _hip.ptr(orient),
                       *gs(orient, -3), 0 if orient is None else orient.stride(-2), _hip.ptr(pat),
                       0 if pat is None or pat.shape[0] == 1 else pat.stride(0), _hip.ptr(air), _hip.ptr(lnw),
-                      color.bands.size, propagation.FIR_FLOOR, _hip.ptr(eo), _hip.ptr(ao), _hip.ptr(go), *gs(eo, -2),
-                      _hip.ptr(do), *gs(do, -2), _hip.ptr(lo), *gs(lo, -3), lo.stride(-2), _hip.current_stream(dev))
+                      color.bands.size, propagation.FIR_FLOOR, *screens, _hip.ptr(eo), _hip.ptr(ao), _hip.ptr(go),
+                      *gs(eo, -2), _hip.ptr(do), *gs(do, -2), _hip.ptr(lo), *gs(lo, -3), lo.stride(-2),
+                      _hip.current_stream(dev))
         return eo, ao, go, do, lo
     with _hip.on_device(dev):
         _hip.call("bas_scene_params_f64", _hip.ptr(p), *gs(p, -3), p.stride(-2), _hip.ptr(prev), *gs(prev, -2), spc,
@@ -597,6 +839,8 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
     every boundary (bas_scene_params_bands_f64; a banded room's walls are among them, its static bank is not used), one
     bas_color_design_f32 launch designs the taps [rows, n_chunks + 1, taps] (rows x (n_chunks + 1) x taps x 4 bytes, not
     slabbed), the delay launch writes the staging rows and bas_color_rows_f32 filters them in its per-boundary form.
+    A colour with screens runs bas_scene_params_occluded_f64 in the scene kernel's place: the same
+    launches, one more term in the log-magnitudes.
     color=None: the launches and the bits of a call without it (orient then needs a color: ValueError)."""
     import torch
     from .apply_hrtf import as_device_table, padded_rows, render_lengths, render_angles_device
@@ -680,7 +924,8 @@ class SceneStreamRenderer:
         color: None, or a SceneColor: the inner renderer is built with color_taps = color.taps; every
         block's scene launch also writes the rows' band log-magnitudes (a banded room's walls among them: its static
         bank is not used) and one bas_color_design_f32 launch writes the block's taps into the inner renderer's
-        color_view(B) in place, in front of the block's graph; process() then takes orient=."""
+        color_view(B) in place, in front of the block's graph; process() then takes orient=.  A colour with screens
+         changes the scene launch's entry point and nothing else."""
         from .stream import StreamRenderer
         self.n_src, self.n_img = int(n_src), _n_img(room)
         if self.n_src < 1:

@@ -630,6 +630,43 @@ int bas_color_design_f32(const double *logmag, long l_stride_g, long l_stride_s,
                          int n_bands, int M, double logmag_floor, int n_groups, int n_src, int nb, float *color,
                          long c_stride_g, long c_stride_s, long c_stride_k, bas_stream_t stream);
 
+/* ---- screens: occlusion and edge diffraction (no reference counterpart) ------------------------------
+ * Static thin rectangles between the image sources and the listener, as one more term of "scene colour"'s L[b].
+ *   bas_scene_params_occluded_f64: bas_scene_params_bands_f64 (same arguments, same checks, the four outputs bit for bit)
+ *   plus
+ *     screens [n_screens][9]: centre c, half-edge vectors e1, e2 (metres, world frame; e1, e2 non-zero and orthogonal: the
+ *       caller's to check), n_screens in 1..32;
+ *     transmission [n_screens][n_bands] at transmission[k transmission_stride_s + b]: magnitudes T in [0, 1];
+ *       transmission_stride_s 0 shares one row over the screens, else >= n_bands; NULL: opaque (T = 0);
+ *     fresnel [n_bands]: 2 f_b / c per band centre f_b (1/metres).
+ *   For the straight path from q (the image's position of steps 1-1b) to the listener l and one screen copy, in binary64
+ *   without contraction (bas_occlude.h holds the expressions and their order):
+ *     n = e1 x e2, s_q = n.(q - c), s_l = n.(l - c); unless s_q s_l < 0 the copy contributes exactly 0 to every band;
+ *     h = q + (s_q / (s_q - s_l)) (l - q), a = (h - c).e1 / |e1|^2, b = (h - c).e2 / |e2|^2, blocked: |a| <= 1 and |b| <= 1;
+ *     delta = max(min over the four edges A-B of [min over P in AB of |q - P| + |P - l|] - |q - l|, 0)   (closed form);
+ *     N_b = +- fresnel[b] delta (+ blocked, - lit), x = sqrt(2 pi |N_b|),
+ *     A = min(5 + 20 log10(x / tanh x), 24) for N >= 0, max(5 + 20 log10(x / tan x), 0) for -0.2 < N < 0, else 0 (dB);
+ *     M_b = T_b + (1 - T_b) exp(-A ln 10 / 20).
+ *   With a room, image m = images[i] meets the copies of every screen in the cells (i, j, k), each index between 0 and
+ *   m_a inclusive: c'_a = i_a L_a + (i_a odd ? L_a - c_a : c_a), component a of e1, e2 negated where i_a is odd.  The sum
+ *   of ln M_b over screens (ascending) and cells (x outermost, each index from 0 towards m_a), from 0, is added to the
+ *   sum of "scene colour" before its final fmax(., log(floor)).  n_screens out of range, a transmission stride in
+ *   (0, n_bands) or negative (BAS_E_SHAPE); screens, fresnel required (BAS_E_NULL); the new pointers 8-byte aligned
+ *   (BAS_E_ALIGN).  room_size may be NULL (screens in the free field: one copy each).  Still one launch, capturable. */
+int bas_scene_params_occluded_f64(const double *pos, long pos_stride_g, long pos_stride_s, long pos_stride_c,
+                                  const double *pos_prev, long prev_stride_g, long prev_stride_s, double samples_per_chunk,
+                                  const double *lpos, long lpos_stride_g, long lpos_stride_c, const double *head,
+                                  long head_stride_g, long head_stride_c, const double *src_gain, long sg_stride_g,
+                                  long sg_stride_s, const double *room_size, const int32_t *images, const double *img_gain,
+                                  int n_img, double samples_per_metre, double r_ref, double d_min, double d_max,
+                                  int n_groups, int n_src, int nb, const double *orient, long orient_stride_g,
+                                  long orient_stride_s, long orient_stride_c, const double *pattern, long pattern_stride_s,
+                                  const double *air, const double *img_logmag, int n_bands, double floor,
+                                  const double *screens, const double *transmission, long transmission_stride_s,
+                                  const double *fresnel, int n_screens, double *elev, double *azim, double *gain,
+                                  long a_stride_g, long a_stride_s, double *delay, long d_stride_g, long d_stride_s,
+                                  double *logmag, long l_stride_g, long l_stride_s, long l_stride_c, bas_stream_t stream);
+
 /* ---- late reverberation (no reference counterpart) ---------------------------------------------------
  * One send bus per group - a weighted mono mix of the group's source rows - through one long static stereo tail, added to
  * the binaural mix.  All entries: one stream, no allocation, no synchronisation (capturable); every argument check runs

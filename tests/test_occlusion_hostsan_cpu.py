@@ -1,0 +1,46 @@
+"""The host half of screens under AddressSanitizer and UndefinedBehaviorSanitizer, without a GPU
+(tests/hostsan/hostsan_occlude.cpp).
+
+`make hostsan_occlude` links the library's translation units - host code sanitized, device code compiled as shipped - with a
+stand-alone program that holds, for bas_scene_params_occluded_f64, valid argument lists and their violations, and the host
+build of bas_occlude.h (what the scene kernel runs per path and screen copy) checked against a long double restatement:
+edges by a search, mirror copies by reflecting wall by wall.  The program runs as a fresh child process whose environment
+hides every GPU from the HIP runtime, and refuses (exit status 77) to call the library where a device is visible.  Nothing
+here loads sanitized code into python, nothing sets LD_PRELOAD, nothing runs on a GPU.
+"""
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+from test_host_sanitizers_cpu import CSRC, OUT, HIPCC
+from test_scene_color_hostsan_cpu import run_program
+
+pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc here")
+
+
+def build_program():
+    """make hostsan_occlude; returns the program's path."""
+    env = dict(os.environ, HIPCC=HIPCC)
+    r = subprocess.run(["make", "-C", CSRC, "-j16", "hostsan_occlude"], env=env, capture_output=True, text=True, timeout=3000)
+    assert r.returncode == 0, f"make hostsan_occlude failed:\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    program = os.path.join(OUT, "hostsan_occlude")
+    assert os.access(program, os.X_OK), program
+    return program
+
+
+def test_argument_checks_and_the_arithmetic_of_screens():
+    r, tail = run_program(build_program())
+    assert r.returncode == 0, f"exit status {r.returncode}\n{tail}"
+    m = re.search(r"bas_scene_params_occluded_f64 (\d+) checks, bas_occlude_edge (\d+) checks \(worst ([0-9.e+-]+) m\), "
+                  r"bas_occlude_sum (\d+) checks \(worst detour ([0-9.e+-]+) m, worst ln M sum ([0-9.e+-]+)\), 0 failed",
+                  r.stdout)
+    assert m and int(m.group(1)) >= 45 and int(m.group(2)) >= 2000 and int(m.group(4)) >= 3000, tail
+    # the restatement's search resolves a detour to 1e-9 m; dL / d delta <= (4 pi / 3) f / c = 100 per metre at 8 kHz
+    assert float(m.group(3)) <= 1e-9 and float(m.group(5)) <= 1e-9 and float(m.group(6)) <= 1e-7, tail
+    assert "hostsan_occlude: ok" in r.stdout, tail
+    print(r.stdout.strip())
+    src = open(os.path.join(ROOT, "tests", "hostsan", "hostsan_occlude.cpp")).read()
+    assert "int main(" in src and "return 77;" in src
