@@ -1,5 +1,5 @@
 // Row step of the output-stationary FIR kernels (bas_render.hip: bas_render_hd_kernel; bas_fused.hip:
-// bas_render_fz_kernel): one lane owns a row of 32 consecutive outputs (both ears: 64 accumulators) and meets
+// bas_render_fz_kernel; what those kernels share around the row step is bas_window.h): one lane owns a row of 32 consecutive outputs (both ears: 64 accumulators) and meets
 // one row of 32 inputs with the 64 taps that connect the two rows - a 32 x 32 Toeplitz block of packed FMAs
 // (apply_hrtf.py:445-446 is the direct FIR these sums restate; :442-443 the crossfade g = h0 + al d formed here).
 #pragma once

@@ -2,7 +2,7 @@
 // per-subchunk crossfade (:442-443), direct FIR (:445-446), overlap-add and the mix over sources (:450-453).
 // The [n_src][n_chunks+1][2][L] chunk-IR array of the two-kernel path never exists in HBM.
 //
-// Work split and FIR: as bas_render_hd_kernel (bas_render.hip) - a workgroup of NW waves owns a tile of
+// Work split and FIR: as bas_render_hd_kernel (bas_render.hip; what the two have in common is bas_window.h) - a workgroup of NW waves owns a tile of
 // 2048 NW outputs and walks over (tile, source) units with the mix in registers; lane = one row of 32 outputs;
 // row step = 32 x 32 Toeplitz block of packed FMAs on an x row and 64 (h0, d) taps from LDS, evaluated as a
 // 2-parallel fast FIR (three half-rate products instead of four: bas_fir.h).
@@ -54,18 +54,6 @@ __device__ unsigned long long bas_fz_stamps[2048 * 4 * 8];
 #ifndef FZ_SLICE_SHIFT
 #define FZ_SLICE_SHIFT 14       // FIR priority alternates between the two workgroups of a CU every 2^shift x 10 ns (0: off)
 #endif
-#ifndef FZ_START_DELAY
-#define FZ_START_DELAY 0        // x 10 ns: head start of the first workgroup of every CU (0: none)
-#endif
-#ifndef FZ_NT_LOADS
-#define FZ_NT_LOADS 1           // x window and plans are read once: non-temporal, so that L2 keeps the table (same speed,
-#endif                          // 13 % fewer bytes fetched past L2)
-#ifndef FZ_NT_STORES
-#define FZ_NT_STORES 0          // non-temporal slab stores: WRITE_SIZE 40 -> 135 MB per launch - off
-#endif
-#ifndef FZ_FFA
-#define FZ_FFA 1                // row step as a 2-parallel fast FIR (bas_fir.h: 3/4 of the FMAs); 0: direct form
-#endif
 #ifndef FZ_SPLIT
 #define FZ_SPLIT FZ_ASM            // scenes with more than one (tile of 8192, source) unit per CU: the split-role kernel (bas_fused_split.hip)
 #endif
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
     constexpr int XFLOATS = 8 * XR * 4;
     constexpr int MAXEV = HONLY ? FZ_HO_MAXEV : (NW == 4 ? 6 : 7);   // chunk IRs one wave evaluates (its slots + 1; HONLY: its share)
     constexpr int SLOTF = HONLY ? HO_SLOT : HD_SLOT;         // floats per LDS row of taps
-    constexpr int PL4 = 2 * BAS_PLANS_WORDS / 4;             // float4 per chunk IR's pair of plans (18)
+    constexpr int PL4 = WIN_PL4;
     constexpr int NPV = (MAXEV * PL4 + 63) / 64;             // 16-byte plan pieces per lane
     static_assert(XR % 2 == 1, "x image rows must be odd");
     static_assert(NW != 1 || MAXEV * 2 * BAS_PLANS_WORDS <= HD_SLOT, "NW = 1: the plans must fit the last chunk slot");
@@ -125,20 +113,16 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
     const int lane0 = tid0 & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
 
-    const long unit0 = (long)blockIdx.x * A.units_per_wg;
-    long unit1 = unit0 + A.units_per_wg;
-    if (unit1 > A.units_total) unit1 = A.units_total;
-    const int nseg = (A.Lp + RT_SEG - 1) / RT_SEG;
-    const long n_pass = (unit1 - unit0) * nseg;
+    const WinWalk W = win_walk(A.units_total, A.units_per_wg, A.Lp);
+    const long n_pass = W.n_pass;
     if (!A.direct && peak_bits && blockIdx.x == 0 && tid0 == 0) *peak_bits = 0u;   // the reduce kernel maxes into it later
     if (n_pass <= 0) {
         if (A.direct && A.tail_mode) bas_tail<THREADS>(fz_tail(A, y, peak_bits), 0.f);
         return;
     }
 
-    constexpr bool USE_ASM = FZ_ASM && FZ_FFA && !HONLY;
+    constexpr bool USE_ASM = FZ_ASM && !HONLY;
     static_assert(!USE_ASM || XR == 261 || XR == 69, "bas_fir_asm.inc holds the row step for these x-image strides");
-#if FZ_FFA
     // half-rate partial sums (bas_fir.h), combined in flush().  Assembly row step: the same 49 pairs as three 32-float
     // vectors + one pair, pinned to v[0:97] by the asm statement's register constraints (A = fa, B = fb[0..15], P = fp)
     f32x2 fa[16], fb[17], fp[16];
@@ -153,20 +137,13 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
 #define FZ_ACC_CLEAR()                                                               \
     do {                                                                             \
         if constexpr (USE_ASM) {                                                     \
-            _Pragma("unroll") for (int i = 0; i < 32; ++i) accA[i] = accB[i] = accP[i] = 0.f; \
-            accB16 = f32x2{0.f, 0.f};                                                \
+            win_zero_pinned(accA, accB, accB16, accP);                               \
         } else {                                                                     \
             ffa_zero(fa, fb, fp);                                                    \
         }                                                                            \
     } while (0)
-#else
-    f32x2 acc[32];
-#define FZ_ACC_CLEAR()                                        \
-    _Pragma("unroll") for (int o = 0; o < 32; ++o) acc[o] = f32x2{0.f, 0.f}
-    FZ_ACC_CLEAR();
-#endif
 
-    const long first_tile = unit0 / A.n_src;
+    const long first_tile = W.unit0 / A.n_src;
     float *slab_wg = slab + (long)blockIdx.x * A.parts_per_wg * 2 * TILE;
     unsigned wmax_bits = 0u;                                 // direct output with a tail: max|y| this wave has stored (uniform)
     const unsigned prio_flip = blockIdx.x >= (gridDim.x >> 1) ? 1u : 0u;
@@ -175,72 +152,35 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
     const unsigned L4 = 4u * (unsigned)A.L;
 
     auto flush = [&](long tile) {
-#if FZ_FFA
         f32x2 acc[32];
         if constexpr (USE_ASM) {
-#pragma unroll
-            for (int p = 0; p < 16; ++p) {                   // y[2p] = A[p] + B[p-1];  y[2p+1] = P[p] - A[p] - B[p]
-                const f32x2 a = f32x2{accA[2 * p], accA[2 * p + 1]}, b0 = f32x2{accB[2 * p], accB[2 * p + 1]};
-                const f32x2 b1 = p < 15 ? f32x2{accB[2 * p + 2], accB[2 * p + 3]} : accB16;
-                const f32x2 pp = f32x2{accP[2 * p], accP[2 * p + 1]};
-                acc[2 * p] = a + b0;
-                acc[2 * p + 1] = (pp - a) - b1;
-            }
+            win_combine_pinned(acc, accA, accB, accB16, accP);
         } else {
             ffa_combine(acc, fa, fb, fp);
         }
-#endif
         if (A.direct) {                                      // uniform
             const long n0 = tile * TILE + 2048 * wv + 32 * lane0;       // this lane's first output
-            const float lmax = fz_store_row_direct(acc, y, A.T_out, n0, A.accumulate);
-            if (A.tail_mode) {
-                const unsigned b = fz_wave_max_bits(lmax);
-                wmax_bits = b > wmax_bits ? b : wmax_bits;
-            } else if (peak_bits) {
-                bas_wave_peak_max(lmax, peak_bits);
-            }
+            wmax_bits = win_flush_row_direct(acc, y, A.T_out, n0, A.accumulate, A.tail_mode, peak_bits, wmax_bits);
             FZ_ACC_CLEAR();
             return;
         }
+        // (win_store_row_slab written out: through the helper the h-only instantiation's scratch size changes)
         float *dst = slab_wg + (tile - first_tile) * 2 * TILE + 2048 * wv + 32 * lane0;
         f32x4 *l4 = reinterpret_cast<f32x4 *>(dst);
         f32x4 *r4 = reinterpret_cast<f32x4 *>(dst + TILE);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-#if FZ_NT_STORES
-            __builtin_nontemporal_store(f32x4{acc[4 * i].x, acc[4 * i + 1].x, acc[4 * i + 2].x, acc[4 * i + 3].x}, l4 + i);
-            __builtin_nontemporal_store(f32x4{acc[4 * i].y, acc[4 * i + 1].y, acc[4 * i + 2].y, acc[4 * i + 3].y}, r4 + i);
-#else
             l4[i] = f32x4{acc[4 * i].x, acc[4 * i + 1].x, acc[4 * i + 2].x, acc[4 * i + 3].x};
             r4[i] = f32x4{acc[4 * i].y, acc[4 * i + 1].y, acc[4 * i + 2].y, acc[4 * i + 3].y};
-#endif
         }
         FZ_ACC_CLEAR();
     };
 
     // scalar state of the walk over (tile, source, tap segment): advanced by counters, never re-divided
     long tile = first_tile;
-    int s = (int)(unit0 - first_tile * A.n_src);
+    int s = (int)(W.unit0 - first_tile * A.n_src);
     int sg = 0;
-    // window geometry of a (tile, segment); recomputed only when either changes
-    struct Geo {
-        int seg0, Lseg, halo, nrows, c0, mo0;
-        long xbase;
-    };
-    auto make_geo = [&](long t, int g) {
-        Geo G;
-        G.seg0 = g * RT_SEG;
-        G.Lseg = A.Lp - G.seg0 < RT_SEG ? A.Lp - G.seg0 : RT_SEG;
-        G.halo = (G.Lseg + 31) >> 5;                         // input rows above the tile that matter
-        G.xbase = t * TILE - G.seg0 - 32L * G.halo;          // first input sample in LDS (multiple of 32)
-        G.nrows = TILE / 32 + G.halo;
-        long cf = G.xbase / A.K;                             // floor division, consistent across 0
-        if (cf * A.K > G.xbase) --cf;
-        G.c0 = (int)cf;
-        G.mo0 = (int)(G.xbase - cf * A.K);
-        return G;
-    };
-    Geo G = make_geo(tile, sg);
+    WinGeo G = win_geo<TILE>(tile, sg, A.K, A.Lp);
     long open_tile = -1;                                     // tile whose partial sums the accumulators hold
     // this wave's share of the chunk IRs.  HONLY: rows [slot_a, slot_b) of the nslots + 1 (h_L, h_R) rows, one chunk IR
     // each.  (h0, d) slots: the nslots + 1 chunk IRs are dealt in balanced contiguous ranges [slot_a, slot_b) - 5, 5, 4, 4
@@ -254,6 +194,8 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
         slot_a = wv * A.spw;
         slot_b = slot_a + A.spw < nrows_h ? slot_a + A.spw : nrows_h;
     } else {
+        // (as bas_render_fq_kernel and the stagers of bas_render_fs_kernel deal them; each keeps its copy: through a shared
+        // helper the scratch size of <1, false> here goes from 36 to 0 bytes, and the stagers put both ends through readfirstlane)
         const int n_ir = A.nslots + 1, base = n_ir / NW, rem = n_ir - base * NW;
         slot_a = wv * base + (wv < rem ? wv : rem);
         slot_b = slot_a + base + (wv < rem ? 1 : 0);
@@ -265,17 +207,6 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
 #endif
     const bool need_next = !HONLY && NW > 1 && n_ev > 0 && slot_b <= A.nslots;   // slot slot_b - 1 exists: it needs IR slot_b
 
-#if FZ_START_DELAY
-    // The two workgroups of a CU alternate between a latency-bound staging phase and a VALU-bound FIR phase.
-    // Started together they stage together (VALU idle) and then share the FIR phase; started half a pass apart,
-    // one stages while the other has the SIMDs to itself.  The second half of the grid (the blocks that join the
-    // first half's CUs under the observed dispatch order; speed only) waits FZ_START_DELAY x 10 ns before its
-    // first pass.
-    if (prio_flip) {
-        const unsigned long long t_go = __builtin_amdgcn_s_memrealtime() + FZ_START_DELAY;
-        while (__builtin_amdgcn_s_memrealtime() < t_go) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
 #ifdef BAS_STAMPS
     unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long st_begin = __builtin_amdgcn_s_memrealtime();
@@ -286,40 +217,18 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
         if (tid0 < NW) flags0[tid0] = 0u;                      // (ordered before their first use by the first pass's barrier)
     }
     // ---- global -> registers: this wave's read plans (chunk IRs slot_a .. slot_b, both ears) and the x window of a pass
-    auto plan_src = [&](int lane, int r, const Geo &Gq, int src) {
+    auto plan_src = [&](int lane, int r, const WinGeo &Gq, int src) {
         const f32x4 *pl_src = reinterpret_cast<const f32x4 *>(plans) + (long)src * (A.n_chunks + 1) * PL4;
-        int p = lane + 64 * r;                               // 16-byte piece of the wave's n_ev * 18
-        p = p < n_ev * PL4 ? p : 0;
-        const int i = (p * 3641) >> 16;                      // p / 18 for p < 1000
-        const int c = clampi(Gq.c0 + slot_a + i, 0, A.n_chunks);
-        return pl_src + (long)c * PL4 + (p - i * PL4);
+        return win_plan_piece(pl_src, lane, r, n_ev, Gq.c0 + slot_a, A.n_chunks);
     };
-    auto issue_plans = [&](int lane, const Geo &Gq, int src, f32x4 (&pv)[NPV]) {
+    auto issue_plans = [&](int lane, const WinGeo &Gq, int src, f32x4 (&pv)[NPV]) {
 #pragma unroll
         for (int r = 0; r < NPV; ++r) {
-#if FZ_NT_LOADS
             pv[r] = __builtin_nontemporal_load(plan_src(lane, r, Gq, src));
-#else
-            pv[r] = *plan_src(lane, r, Gq, src);
-#endif
         }
     };
-    auto issue_x = [&](int tid, const Geo &Gq, int src, f32x4 (&xv)[NX]) {
-        const float *xwin = x + (long)src * A.x_stride + Gq.xbase;
-        const long lo_l = -Gq.xbase, hi_l = A.T_in - Gq.xbase;
-        const int x_lo = lo_l < -(1 << 30) ? -(1 << 30) : (lo_l > (1 << 30) ? (1 << 30) : (int)lo_l);
-        const int x_hi = hi_l < -(1 << 30) ? -(1 << 30) : (hi_l > (1 << 30) ? (1 << 30) : (int)hi_l);
-#pragma unroll
-        for (int j = 0; j < NX; ++j) {
-            int i = 4 * (tid + j * THREADS);
-            i = i < x_lo ? x_lo : i;
-            i = i > x_hi - 4 ? x_hi - 4 : i;                 // clamped into the row (T_in is a multiple of K >= 32)
-#if FZ_NT_LOADS
-            xv[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xwin + i));   // streamed once: keep L2 for the table
-#else
-            xv[j] = *reinterpret_cast<const f32x4 *>(xwin + i);
-#endif
-        }
+    auto issue_x = [&](int tid, const WinGeo &Gq, int src, f32x4 (&xv)[NX]) {
+        win_fetch_x<NX, THREADS>(xv, x + (long)src * A.x_stride + Gq.xbase, tid, win_x_bounds(Gq.xbase, A.T_in));
     };
     // prefetch: the NEXT pass's x window is requested in front of the FIR phase and held in 36 registers per lane across the
     // row steps - only the assembly row step (78 operand registers against ~104 of hipcc's schedule) leaves them: with
@@ -350,10 +259,8 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
             issue_plans(lane, G, s, pv);
             issue_x(tid, G, s, xv);
         }
-        const long lo_l = -xbase, hi_l = A.T_in - xbase;     // offsets of the signal's first sample / one past its last
-        const int x_lo = lo_l < -(1 << 30) ? -(1 << 30) : (lo_l > (1 << 30) ? (1 << 30) : (int)lo_l);
-        const int x_hi = hi_l < -(1 << 30) ? -(1 << 30) : (hi_l > (1 << 30) ? (1 << 30) : (int)hi_l);
-        const bool x_inside = x_lo <= 0 && x_hi >= 4 * NX * THREADS;   // whole window inside the signal
+        const WinXBounds XB = win_x_bounds(xbase, A.T_in);
+        const bool x_inside = win_x_inside<NX, THREADS>(XB);
         FZ_STAMP_NW(t1);
         __syncthreads();                                     // previous pass has finished reading LDS
         FZ_STAMP_NW(t2);
@@ -373,12 +280,12 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the plans' LDS-DMA has landed (only this wave reads them)
         }
 #pragma unroll
-        for (int j = 0; j < NX; ++j) {
+        for (int j = 0; j < NX; ++j) {                       // (as in bas_render_fq_kernel; a shared helper changed both kernels' branches)
             const int i4 = tid + j * THREADS;
             f32x4 v = xv[j];
             if (!x_inside) {                                 // uniform: only windows that overlap an end of the signal
-                const int e = 4 * i4;                        // x_lo, x_hi are multiples of 4: all four in or out
-                if (!(e >= x_lo && e < x_hi)) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                const int e = 4 * i4;                        // the bounds are multiples of 4: all four in or out
+                if (!(e >= XB.lo && e < XB.hi)) v = f32x4{0.f, 0.f, 0.f, 0.f};
             }
             if (i4 < nrows * 8) xs4[(i4 & 7) * XR + (i4 >> 3)] = v;
         }
@@ -387,7 +294,8 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
 
         // ---- chunk IRs from the table: lanes 0-31 four adjacent taps of the left ear, lanes 32-63 of the right.
         // Two halves of 8 reads are in flight at any time; slot i - 1 = (IR i-1, IR i - IR i-1) is stored as soon
-        // as IR i is known: both ears of two taps per 16-byte LDS write.
+        // as IR i is known: both ears of two taps per 16-byte LDS write.  (bas_render_fq_kernel holds a copy of the (h0, d)
+        // form of this loop: here the h-only rows are a branch inside the same loop body, which a shared loop would split in two.)
         {
             const int half = lane >> 5;
             const int m = seg0 + 4 * (lane & 31);
@@ -461,17 +369,9 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
         FZ_STAMP_NW(t5);
 
         // ---- next (tile, source, segment); its x window and read plans are requested now and arrive under the FIR phase
-        long n_tile = tile;
-        int n_s = s, n_sg = sg + 1;
-        if (n_sg == nseg) {
-            n_sg = 0;
-            if (++n_s == A.n_src) {
-                n_s = 0;
-                ++n_tile;
-            }
-        }
-        Geo GN = G;
-        if (n_tile != tile || n_sg != sg) GN = make_geo(n_tile, n_sg);
+        const WinPos N = win_next(tile, s, sg, W.nseg, A.n_src);
+        WinGeo GN = G;
+        if (N.tile != tile || N.sg != sg) GN = win_geo<TILE>(N.tile, N.sg, A.K, A.Lp);
         if constexpr (PREFETCH) {
             if (pid + 1 < n_pass) {
 #if defined(__HIP_DEVICE_COMPILE__)                          // (the builtin exists in the device pass only)
@@ -479,81 +379,46 @@ __global__ __launch_bounds__(64 * NW, 2) void bas_render_fz_kernel(
 #pragma unroll
                 for (int r = 0; r < NPV; ++r)
                     if (lane + 64 * r < n_ev * PL4)          // (inactive lanes write nothing: the region holds n_ev * 18 pieces)
-                        __builtin_amdgcn_global_load_lds(plan_src(lane, r, GN, n_s),
+                        __builtin_amdgcn_global_load_lds(plan_src(lane, r, GN, N.s),
                                                          (lds_ptr_t)(uintptr_t)(unsigned)reinterpret_cast<uintptr_t>(plw + 64 * r), 16, 0, 2);
 #endif
-                issue_x(tid, GN, n_s, xv);
+                issue_x(tid, GN, N.s, xv);
             }
         }
 
         // ---- FIR: input rows rho' = 0..halo above/at the lane's output row
         const int row_out = 64 * wv + lane + halo;           // window row holding the lane's outputs
-        const int pos = mo0 + 32 * row_out;
-        int sl = (int)((float)pos * A.invK);                 // chunk slot of that row (float estimate, corrected)
-        int m_in = pos - sl * A.K;                           // offset of the row inside its chunk
-        if (m_in < 0) { m_in += A.K; sl -= 1; }
-        if (m_in >= A.K) { m_in -= A.K; sl += 1; }
+        int sl, m_in;                                        // chunk slot of that row, its offset inside the chunk
+        win_row_slot(mo0 + 32 * row_out, A.K, A.invK, sl, m_in);
         const f32x4 *xrow = xs4 + row_out;
 #if FZ_SLICE_SHIFT
-        {   // fair time slicing between the two workgroups of a CU (see bas_render_hd_kernel)
+        {   // fair time slicing between the two workgroups of a CU (see bas_render_hd_kernel, which keeps its own copy with a run-time shift)
             const unsigned t = (unsigned)(__builtin_amdgcn_s_memrealtime() >> FZ_SLICE_SHIFT);
             if ((t & 1u) ^ prio_flip) __builtin_amdgcn_s_setprio(2);
             else __builtin_amdgcn_s_setprio(0);
         }
-#elif defined(FZ_ASYM_PRIO)
-        if (prio_flip) __builtin_amdgcn_s_setprio(0);        // experiment: the first half of the grid always goes first
-        else __builtin_amdgcn_s_setprio(FZ_ASYM_PRIO);
 #elif FZ_STAGE_PRIO
         __builtin_amdgcn_s_setprio(0);
 #endif
 #pragma unroll 1
         for (int rp = 0; rp <= halo; ++rp) {
-            float al[1];
-            if (A.s_pow2) {
-                al[0] = (float)(m_in & ~(A.S - 1)) * A.invK;
-            } else {                                         // any multiple of 32: m_in / S by float estimate, corrected
-                int q = (int)((float)m_in * A.invS);
-                const int r = m_in - q * A.S;
-                if (r < 0) q -= 1;
-                if (r >= A.S) q += 1;
-                al[0] = (float)(q * A.S) * A.invK;
-            }
-            // octet i holds taps t0 = 32 rp - 32 + 8 i .. + 7 of the segment and is live for 0 <= t0 < Lseg (a multiple of 8):
-            // i in [lo, hi).  (Closed form: eight compare-and-or chains per row step were 60 scalar instructions, which a wave
-            // that has its SIMD to itself pays ~6 clocks each for.)
-            const int oct_lo = 4 - 4 * rp > 0 ? 4 - 4 * rp : 0;
-            int oct_hi = (Lseg + 32 - 32 * rp) >> 3;         // >= 1 for rp <= halo
-            oct_hi = oct_hi > 8 ? 8 : oct_hi;
-            const unsigned mk = ((1u << oct_hi) - 1u) & ~((1u << oct_lo) - 1u);
-#if !FZ_FFA
-            float xr[32];
-            fz_load_xrow<XR>(xr, xrow);
-#endif
-#if FZ_FFA
+            const float al = win_weight(m_in, A.S, A.s_pow2, A.invK, A.invS);
+            const unsigned mk = win_octet_mask(rp, Lseg);
             if constexpr (USE_ASM) {
                 ffa_row_step_asm<XR>(accA, accB, accB16, accP, (unsigned)reinterpret_cast<uintptr_t>(xrow),
-                                     (unsigned)reinterpret_cast<uintptr_t>(hd + sl * SLOTF + (32 * rp - 32) * 4), al[0], mk);
+                                     (unsigned)reinterpret_cast<uintptr_t>(hd + sl * SLOTF + (32 * rp - 32) * 4), al, mk);
             } else {
                 float xr[32];
                 fz_load_xrow<XR>(xr, xrow);
-                ffa_row_step_x<HONLY>(fa, fb, fp, xr, hd + sl * SLOTF + (32 * rp - 32) * (HONLY ? 2 : 4), al[0], mk);
+                ffa_row_step_x<HONLY>(fa, fb, fp, xr, hd + sl * SLOTF + (32 * rp - 32) * (HONLY ? 2 : 4), al, mk);
             }
-#else
-            hd_row_step_x<1, HONLY>(acc, xr, hd + sl * SLOTF + (32 * rp - 32) * (HONLY ? 2 : 4), al, mk);
-#endif
             xrow -= 1;
-            m_in -= 32;
-            if (m_in < 0) {
-                m_in += A.K;
-                sl -= 1;
-            }
+            win_row_up(A.K, sl, m_in);
         }
 
         FZ_STAMP_NW(t6);
         FZ_ADD(0, t0, t1); FZ_ADD(1, t1, t2); FZ_ADD(2, t2, t3); FZ_ADD(3, t3, t4); FZ_ADD(4, t4, t5); FZ_ADD(5, t5, t6);
-        tile = n_tile;
-        s = n_s;
-        sg = n_sg;
+        tile = N.tile, s = N.s, sg = N.sg;
         G = GN;
     }
     flush(open_tile);

@@ -12,12 +12,9 @@
 //             order 0, 1, 2, 3 (deterministic) and writes the tile (y itself for one source, a slab part otherwise).
 //
 // One wave per SIMD runs this instruction stream at ~5 clocks per vector instruction, so a unit takes about a
-// quarter of the one-wave kernel's 19 us plus two barriers.  No MFMA: this is a 1-D FIR (BASELINE.json north_star).
+// quarter of the one-wave kernel's 19 us plus two barriers.  The walk, the window geometry, the row-step setup and the flush's
+// combine and stores are bas_window.h, shared with the other FIR kernels.  No MFMA: this is a 1-D FIR (BASELINE.json north_star).
 #include "bas_fused.h"
-
-#ifndef FZ_NT_LOADS
-#define FZ_NT_LOADS 1
-#endif
 
 #if FZ_ASM
 __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
@@ -34,7 +31,7 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
     constexpr int NX = (ROWS * 8 + THREADS - 1) / THREADS;   // float4 of x per thread (3)
     constexpr int XFLOATS = 8 * XR * 4;
     constexpr int MAXEV = BAS_FQ_MAXEV;                      // chunk IRs one wave evaluates per unit
-    constexpr int PL4 = 2 * BAS_PLANS_WORDS / 4;             // float4 per chunk IR's pair of plans (18)
+    constexpr int PL4 = WIN_PL4;
     constexpr int NPV = (MAXEV * PL4 + 63) / 64;             // 16-byte plan pieces per lane
     static_assert(XR == 69, "bas_fir_asm.inc holds the row step for this x-image stride");
     extern __shared__ f32x4 lds4[];
@@ -51,11 +48,8 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
     const int lane0 = tid0 & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
 
-    const long unit0 = (long)blockIdx.x * A.units_per_wg;
-    long unit1 = unit0 + A.units_per_wg;
-    if (unit1 > A.units_total) unit1 = A.units_total;
-    const int nseg = (A.Lp + RT_SEG - 1) / RT_SEG;
-    const long n_pass = (unit1 - unit0) * nseg;
+    const WinWalk W = win_walk(A.units_total, A.units_per_wg, A.Lp);
+    const long n_pass = W.n_pass;
     if (!A.direct && peak_bits && blockIdx.x == 0 && tid0 == 0) *peak_bits = 0u;   // the reduce kernel maxes into it later
     if (n_pass <= 0) {
         if (A.direct && A.tail_mode) bas_tail<THREADS>(fz_tail(A, y, peak_bits), 0.f);
@@ -66,10 +60,9 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
                                                              // (ordered before their first use by the first pass's barrier)
     f32x32 accA, accB, accP;                                 // half-rate partial sums (bas_fir.h), pinned to v[0:97] by the block
     f32x2 accB16 = f32x2{0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 32; ++i) accA[i] = accB[i] = accP[i] = 0.f;
+    win_zero_pinned(accA, accB, accB16, accP);
 
-    const long first_tile = unit0 / A.n_src;
+    const long first_tile = W.unit0 / A.n_src;
     float *slab_wg = slab + (long)blockIdx.x * A.parts_per_wg * 2 * TILE;
     const __amdgpu_buffer_rsrc_t tab =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(packed), 0, (int)A.packed_bytes, 0x00020000);
@@ -78,17 +71,8 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
     // every wave holds a share of the tile's outputs (its row steps' taps): they meet in LDS, wave 0 writes the tile
     auto flush = [&](long t) {
         f32x2 acc[32];
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {                       // y[2p] = A[p] + B[p-1];  y[2p+1] = P[p] - A[p] - B[p]
-            const f32x2 a = f32x2{accA[2 * p], accA[2 * p + 1]}, b0 = f32x2{accB[2 * p], accB[2 * p + 1]};
-            const f32x2 b1 = p < 15 ? f32x2{accB[2 * p + 2], accB[2 * p + 3]} : accB16;
-            const f32x2 pp = f32x2{accP[2 * p], accP[2 * p + 1]};
-            acc[2 * p] = a + b0;
-            acc[2 * p + 1] = (pp - a) - b1;
-        }
-#pragma unroll
-        for (int i = 0; i < 32; ++i) accA[i] = accB[i] = accP[i] = 0.f;
-        accB16 = f32x2{0.f, 0.f};
+        win_combine_pinned(acc, accA, accB, accB16, accP);
+        win_zero_pinned(accA, accB, accB16, accP);
         if (wv > 0) {
             f32x2 *c = comb + (wv - 1) * 32 * 64 + lane0;
 #pragma unroll
@@ -104,53 +88,24 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
             }
             if (A.direct) {                                  // uniform
                 const long n0 = t * TILE + 32 * lane0;       // this lane's first output
-                const float lmax = fz_store_row_direct(acc, y, A.T_out, n0, A.accumulate);
-                if (A.tail_mode) {
-                    const unsigned b = fz_wave_max_bits(lmax);
-                    wmax_bits = b > wmax_bits ? b : wmax_bits;
-                } else if (peak_bits) {
-                    bas_wave_peak_max(lmax, peak_bits);
-                }
+                wmax_bits = win_flush_row_direct(acc, y, A.T_out, n0, A.accumulate, A.tail_mode, peak_bits, wmax_bits);
             } else {
-                float *dst = slab_wg + (t - first_tile) * 2 * TILE + 32 * lane0;
-                f32x4 *l4 = reinterpret_cast<f32x4 *>(dst);
-                f32x4 *r4 = reinterpret_cast<f32x4 *>(dst + TILE);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    l4[i] = f32x4{acc[4 * i].x, acc[4 * i + 1].x, acc[4 * i + 2].x, acc[4 * i + 3].x};
-                    r4[i] = f32x4{acc[4 * i].y, acc[4 * i + 1].y, acc[4 * i + 2].y, acc[4 * i + 3].y};
-                }
+                win_store_row_slab(acc, slab_wg + (t - first_tile) * 2 * TILE + 32 * lane0, TILE);
             }
         }
         __syncthreads();                                     // (the next flush may write the meeting place again)
     };
 
-    // scalar state of the walk over (tile, source, tap segment): advanced by counters, never re-divided
+    // scalar state of the walk over (tile, source, tap segment)
     long tile = first_tile;
-    int s = (int)(unit0 - first_tile * A.n_src);
+    int s = (int)(W.unit0 - first_tile * A.n_src);
     int sg = 0;
-    struct Geo {
-        int seg0, Lseg, halo, nrows, c0, mo0;
-        long xbase;
-    };
-    auto make_geo = [&](long t, int g) {
-        Geo G;
-        G.seg0 = g * RT_SEG;
-        G.Lseg = A.Lp - G.seg0 < RT_SEG ? A.Lp - G.seg0 : RT_SEG;
-        G.halo = (G.Lseg + 31) >> 5;                         // input rows above the tile that matter
-        G.xbase = t * TILE - G.seg0 - 32L * G.halo;          // first input sample in LDS (multiple of 32)
-        G.nrows = TILE / 32 + G.halo;
-        long cf = G.xbase / A.K;                             // floor division, consistent across 0
-        if (cf * A.K > G.xbase) --cf;
-        G.c0 = (int)cf;
-        G.mo0 = (int)(G.xbase - cf * A.K);
-        return G;
-    };
-    Geo G = make_geo(tile, sg);
+    WinGeo G = win_geo<TILE>(tile, sg, A.K, A.Lp);
     long open_tile = -1;                                     // tile whose partial sums the accumulators hold
     // this wave's share of the nslots + 1 chunk IRs: balanced contiguous ranges [slot_a, slot_b); it writes the slots
     // [slot_a, slot_b): slot i holds (IR i, IR i+1 - IR i), so its LAST slot needs the FIRST IR of the next wave, which that
-    // wave leaves in LDS as soon as it has it (bnd / flags)
+    // wave leaves in LDS as soon as it has it (bnd / flags).  (A copy of bas_render_fz_kernel's deal: that kernel cannot take a
+    // shared helper - its scratch size changes - and the split-role stagers' copy differs on purpose.)
     const int n_ir = A.nslots + 1, base = n_ir / NW, rem = n_ir - base * NW;
     const int slot_a = wv * base + (wv < rem ? wv : rem);
     const int slot_b = slot_a + base + (wv < rem ? 1 : 0);
@@ -169,43 +124,16 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
             open_tile = tile;
         }
         const int seg0 = G.seg0, Lseg = G.Lseg, halo = G.halo, nrows = G.nrows;
-        const long xbase = G.xbase;
         __builtin_amdgcn_s_setprio(3);                       // staging is latency bound: its few instructions go first
         // ---- global -> registers: read plans of this wave's chunk IRs (both ears) and the x window
         f32x4 pv[NPV], xv[NX];
-        {
-            const f32x4 *pl_src = reinterpret_cast<const f32x4 *>(plans) + (long)s * (A.n_chunks + 1) * PL4;
+        const f32x4 *pl_src = reinterpret_cast<const f32x4 *>(plans) + (long)s * (A.n_chunks + 1) * PL4;
 #pragma unroll
-            for (int r = 0; r < NPV; ++r) {
-                int p = lane + 64 * r;                       // 16-byte piece of the wave's n_ev * 18
-                p = p < n_ev * PL4 ? p : 0;
-                const int i = (p * 3641) >> 16;              // p / 18 for p < 1000
-                const int c = clampi(G.c0 + slot_a + i, 0, A.n_chunks);
-#if FZ_NT_LOADS
-                pv[r] = __builtin_nontemporal_load(pl_src + (long)c * PL4 + (p - i * PL4));
-#else
-                pv[r] = pl_src[(long)c * PL4 + (p - i * PL4)];
-#endif
-            }
-        }
-        const long lo_l = -xbase, hi_l = A.T_in - xbase;     // offsets of the signal's first sample / one past its last
-        const int x_lo = lo_l < -(1 << 30) ? -(1 << 30) : (lo_l > (1 << 30) ? (1 << 30) : (int)lo_l);
-        const int x_hi = hi_l < -(1 << 30) ? -(1 << 30) : (hi_l > (1 << 30) ? (1 << 30) : (int)hi_l);
-        const bool x_inside = x_lo <= 0 && x_hi >= 4 * NX * THREADS;   // whole window inside the signal
-        {
-            const float *xwin = x + (long)s * A.x_stride + xbase;
-#pragma unroll
-            for (int j = 0; j < NX; ++j) {
-                int i = 4 * (tid + j * THREADS);
-                i = i < x_lo ? x_lo : i;
-                i = i > x_hi - 4 ? x_hi - 4 : i;             // clamped into the row (T_in is a multiple of K >= 32)
-#if FZ_NT_LOADS
-                xv[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xwin + i));   // streamed once
-#else
-                xv[j] = *reinterpret_cast<const f32x4 *>(xwin + i);
-#endif
-            }
-        }
+        for (int r = 0; r < NPV; ++r)                        // (read once, as the x window is: non-temporal)
+            pv[r] = __builtin_nontemporal_load(win_plan_piece(pl_src, lane, r, n_ev, G.c0 + slot_a, A.n_chunks));
+        const WinXBounds XB = win_x_bounds(G.xbase, A.T_in);
+        const bool x_inside = win_x_inside<NX, THREADS>(XB);
+        win_fetch_x<NX, THREADS>(xv, x + (long)s * A.x_stride + G.xbase, tid, XB);
         __syncthreads();                                     // previous pass has finished reading LDS
         // ---- registers -> LDS: plans into this wave's own region, the x window as a column-major image
         const unsigned pass_id = (unsigned)pid + 1u;
@@ -213,12 +141,12 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
         for (int r = 0; r < NPV; ++r)
             if (lane + 64 * r < n_ev * PL4) plw[lane + 64 * r] = pv[r];
 #pragma unroll
-        for (int j = 0; j < NX; ++j) {
+        for (int j = 0; j < NX; ++j) {                       // (as in bas_render_fz_kernel; a shared helper changed both kernels' branches)
             const int i4 = tid + j * THREADS;
             f32x4 v = xv[j];
             if (!x_inside) {                                 // uniform: only windows that overlap an end of the signal
-                const int e = 4 * i4;                        // x_lo, x_hi are multiples of 4: all four in or out
-                if (!(e >= x_lo && e < x_hi)) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                const int e = 4 * i4;                        // the bounds are multiples of 4: all four in or out
+                if (!(e >= XB.lo && e < XB.hi)) v = f32x4{0.f, 0.f, 0.f, 0.f};
             }
             if (i4 < nrows * 8) xs4[(i4 & 7) * XR + (i4 >> 3)] = v;
         }
@@ -226,7 +154,8 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
 
         // ---- chunk IRs from the table: lanes 0-31 four adjacent taps of the left ear, lanes 32-63 of the right.
         // Two halves of 8 reads are in flight at any time; slot i - 1 = (IR i-1, IR i - IR i-1) is stored as soon
-        // as IR i is known: both ears of two taps per 16-byte LDS write.
+        // as IR i is known: both ears of two taps per 16-byte LDS write.  (A copy of the (h0, d) form of bas_render_fz_kernel's
+        // loop, which carries its h-only rows as a branch inside the same body and so stays whole.)
         {
             const int half = lane >> 5;
             const int m = seg0 + 4 * (lane & 31);
@@ -284,54 +213,25 @@ __global__ __launch_bounds__(256, 2) void bas_render_fq_kernel(
 
         // ---- FIR: the lane's row in every wave; this wave's share of the input rows rho' = 0..halo above/at it
         const int row_out = lane + halo;                     // window row holding the lane's outputs
-        const int pos = G.mo0 + 32 * row_out;
-        int sl = (int)((float)pos * A.invK);                 // chunk slot of that row (float estimate, corrected)
-        int m_in = pos - sl * A.K;                           // offset of the row inside its chunk
-        if (m_in < 0) { m_in += A.K; sl -= 1; }
-        if (m_in >= A.K) { m_in -= A.K; sl += 1; }
+        int sl, m_in;                                        // chunk slot of that row, its offset inside the chunk
+        win_row_slot(G.mo0 + 32 * row_out, A.K, A.invK, sl, m_in);
         const f32x4 *xrow = xs4 + row_out;
 #pragma unroll 1
         for (int rp = 0; rp <= halo; ++rp) {
             if ((rp & (NW - 1)) == wv) {                     // (uniform)
-                float al;
-                if (A.s_pow2) {
-                    al = (float)(m_in & ~(A.S - 1)) * A.invK;
-                } else {                                     // any multiple of 32: m_in / S by float estimate, corrected
-                    int q = (int)((float)m_in * A.invS);
-                    const int r = m_in - q * A.S;
-                    if (r < 0) q -= 1;
-                    if (r >= A.S) q += 1;
-                    al = (float)(q * A.S) * A.invK;
-                }
-                // octet i holds taps t0 = 32 rp - 32 + 8 i .. + 7 of the segment, live for 0 <= t0 < Lseg (a multiple of 8)
-                const int oct_lo = 4 - 4 * rp > 0 ? 4 - 4 * rp : 0;
-                int oct_hi = (Lseg + 32 - 32 * rp) >> 3;     // >= 1 for rp <= halo
-                oct_hi = oct_hi > 8 ? 8 : oct_hi;
-                const unsigned mk = ((1u << oct_hi) - 1u) & ~((1u << oct_lo) - 1u);
+                const float al = win_weight(m_in, A.S, A.s_pow2, A.invK, A.invS);
+                const unsigned mk = win_octet_mask(rp, Lseg);
                 ffa_row_step_asm<XR>(accA, accB, accB16, accP, (unsigned)reinterpret_cast<uintptr_t>(xrow),
                                      (unsigned)reinterpret_cast<uintptr_t>(hd + sl * HD_SLOT + (32 * rp - 32) * 4), al, mk);
             }
             xrow -= 1;
-            m_in -= 32;
-            if (m_in < 0) {
-                m_in += A.K;
-                sl -= 1;
-            }
+            win_row_up(A.K, sl, m_in);
         }
 
         // ---- next (tile, source, segment)
-        int n_sg = sg + 1;
-        long n_tile = tile;
-        if (n_sg == nseg) {
-            n_sg = 0;
-            if (++s == A.n_src) {
-                s = 0;
-                ++n_tile;
-            }
-        }
-        if (n_tile != tile || n_sg != sg) G = make_geo(n_tile, n_sg);
-        tile = n_tile;
-        sg = n_sg;
+        const WinPos N = win_next(tile, s, sg, W.nseg, A.n_src);
+        if (N.tile != tile || N.sg != sg) G = win_geo<TILE>(N.tile, N.sg, A.K, A.Lp);
+        tile = N.tile, s = N.s, sg = N.sg;
     }
     flush(open_tile);
     if (A.direct && A.tail_mode) bas_tail<THREADS>(fz_tail(A, y, peak_bits), __uint_as_float(wmax_bits));

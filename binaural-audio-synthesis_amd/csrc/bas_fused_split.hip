@@ -14,13 +14,10 @@
 // unit always runs under the FIR of the current one, and the filter (no staging state in its registers) can afford a row-step
 // block with 126 operand registers (bas_fir_asm.inc: ffa_unit_asm).  The price is LDS: two (x image, taps) buffers = 137 KB +
 // plans, one workgroup per CU; and a wave alone on its SIMD pays ~6 clocks for every LDS read and wait.
-// No MFMA: this is a 1-D FIR (BASELINE.json north_star).
+// The walk, the window geometry, the row-step setup and the flush are bas_window.h, shared with the other FIR kernels; what
+// the stagers keep to themselves says so where it stands.  No MFMA: this is a 1-D FIR (BASELINE.json north_star).
 #include "bas_fused.h"
 #include <stdlib.h>
-
-#ifndef FZ_NT_LOADS
-#define FZ_NT_LOADS 1
-#endif
 
 #ifndef FS_PSPLIT
 #define FS_PSPLIT 1             // unit blocks of subchunks >= 32: the half-rate product P split once more (0: round 4's first form)
@@ -72,7 +69,7 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
     constexpr int NX = (ROWS * 8 + THREADS - 1) / THREADS;   // float4 of x per stager thread (9)
     constexpr int XFLOATS = 8 * XR * 4;
     constexpr int MAXEV = BAS_FS_MAXEV;                      // chunk IRs one stager evaluates per unit
-    constexpr int PL4 = 2 * BAS_PLANS_WORDS / 4;             // float4 per chunk IR's pair of plans (18)
+    constexpr int PL4 = WIN_PL4;
     constexpr int NPV = (MAXEV * PL4 + 63) / 64;             // 16-byte plan pieces per lane
     static_assert(XR == 261, "bas_fir_asm.inc holds the row step for this x-image stride");
     extern __shared__ f32x4 lds4[];
@@ -89,11 +86,8 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
     const bool stager = wv8 >= NW;                           // (wave-uniform)
     const int wv = wv8 & (NW - 1);                           // wave index inside its role
 
-    const long unit0 = (long)blockIdx.x * A.units_per_wg;
-    long unit1 = unit0 + A.units_per_wg;
-    if (unit1 > A.units_total) unit1 = A.units_total;
-    const int nseg = (A.Lp + RT_SEG - 1) / RT_SEG;
-    const long n_pass = (unit1 - unit0) * nseg;
+    const WinWalk W = win_walk(A.units_total, A.units_per_wg, A.Lp);
+    const long n_pass = W.n_pass;
     if (!A.direct && peak_bits && blockIdx.x == 0 && tid0 == 0) *peak_bits = 0u;   // the reduce kernel maxes into it later
     if (n_pass <= 0) {
         if (A.direct && A.tail_mode) bas_tail<2 * THREADS>(fz_tail(A, y, peak_bits), 0.f);
@@ -103,42 +97,16 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
     if (tid0 < NW) flags[tid0] = 0u;                         // hand-over flags of the boundary IRs: no pass has id 0
     __syncthreads();
 
-    const long first_tile = unit0 / A.n_src;
+    const long first_tile = W.unit0 / A.n_src;
     // scalar state of the walk over (tile, source, tap segment): advanced by counters, never re-divided (both roles walk it)
     long tile = first_tile;
-    int s = (int)(unit0 - first_tile * A.n_src);
+    int s = (int)(W.unit0 - first_tile * A.n_src);
     int sg = 0;
-    struct Geo {
-        int seg0, Lseg, halo, nrows, c0, mo0;
-        long xbase;
-    };
-    auto make_geo = [&](long t, int g) {
-        Geo G;
-        G.seg0 = g * RT_SEG;
-        G.Lseg = A.Lp - G.seg0 < RT_SEG ? A.Lp - G.seg0 : RT_SEG;
-        G.halo = (G.Lseg + 31) >> 5;                         // input rows above the tile that matter
-        G.xbase = t * TILE - G.seg0 - 32L * G.halo;          // first input sample in LDS (multiple of 32)
-        G.nrows = TILE / 32 + G.halo;
-        long cf = G.xbase / A.K;                             // floor division, consistent across 0
-        if (cf * A.K > G.xbase) --cf;
-        G.c0 = (int)cf;
-        G.mo0 = (int)(G.xbase - cf * A.K);
-        return G;
-    };
-    Geo G = make_geo(tile, sg);
+    WinGeo G = win_geo<TILE>(tile, sg, A.K, A.Lp);
     auto advance = [&]() {
-        int n_sg = sg + 1;
-        long n_tile = tile;
-        if (n_sg == nseg) {
-            n_sg = 0;
-            if (++s == A.n_src) {
-                s = 0;
-                ++n_tile;
-            }
-        }
-        if (n_tile != tile || n_sg != sg) G = make_geo(n_tile, n_sg);
-        tile = n_tile;
-        sg = n_sg;
+        const WinPos N = win_next(tile, s, sg, W.nseg, A.n_src);
+        if (N.tile != tile || N.sg != sg) G = win_geo<TILE>(N.tile, N.sg, A.K, A.Lp);
+        tile = N.tile, s = N.s, sg = N.sg;
     };
 #ifdef BAS_STAMPS
     unsigned long long st_work = 0, st_wait = 0, st_clk = 0;
@@ -155,6 +123,7 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
         f32x2 accB16 = f32x2{0.f, 0.f};
         f32x16 accPA, accPB, accPP;                          // PSPLIT: P = (PA, PB[-1 .. 7], PP) at quarter rate
         f32x2 accPB8 = f32x2{0.f, 0.f};
+        // (win_zero_pinned written out: through the helper <128, 2> and <104, 2> take 251 VGPRs instead of 250)
 #pragma unroll
         for (int i = 0; i < 32; ++i) accA[i] = accB[i] = accP[i] = 0.f;
 #pragma unroll
@@ -173,17 +142,8 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                     accP[4 * r + 2] = po.x; accP[4 * r + 3] = po.y;
                 }
             }
-#pragma unroll
-            for (int p = 0; p < 16; ++p) {                   // y[2p] = A[p] + B[p-1];  y[2p+1] = P[p] - A[p] - B[p]
-                const f32x2 a = f32x2{accA[2 * p], accA[2 * p + 1]}, b0 = f32x2{accB[2 * p], accB[2 * p + 1]};
-                const f32x2 b1 = p < 15 ? f32x2{accB[2 * p + 2], accB[2 * p + 3]} : accB16;
-                const f32x2 pp = f32x2{accP[2 * p], accP[2 * p + 1]};
-                acc[2 * p] = a + b0;
-                acc[2 * p + 1] = (pp - a) - b1;
-            }
-#pragma unroll
-            for (int i = 0; i < 32; ++i) accA[i] = accB[i] = accP[i] = 0.f;
-            accB16 = f32x2{0.f, 0.f};
+            win_combine_pinned(acc, accA, accB, accB16, accP);
+            win_zero_pinned(accA, accB, accB16, accP);
             if constexpr (PSPLIT) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) accPA[i] = accPB[i] = accPP[i] = 0.f;
@@ -191,23 +151,17 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
             }
             if (A.direct) {                                  // uniform
                 const long n0 = t * TILE + 2048 * wv + 32 * lane0;       // this lane's first output
-                const float lmax = fz_store_row_direct(acc, y, A.T_out, n0, A.accumulate);
+                // (win_flush_row_direct written out: through the helper <128, 2> and <104, 2> take 251 VGPRs instead of 250)
+                const float lmax = win_store_row_direct(acc, y, A.T_out, n0, A.accumulate);
                 if (A.tail_mode) {
-                    const unsigned b = fz_wave_max_bits(lmax);
+                    const unsigned b = win_wave_max_bits(lmax);
                     wmax_bits = b > wmax_bits ? b : wmax_bits;
                 } else if (peak_bits) {
                     bas_wave_peak_max(lmax, peak_bits);
                 }
                 return;
             }
-            float *dst = slab_wg + (t - first_tile) * 2 * TILE + 2048 * wv + 32 * lane0;
-            f32x4 *l4 = reinterpret_cast<f32x4 *>(dst);
-            f32x4 *r4 = reinterpret_cast<f32x4 *>(dst + TILE);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                l4[i] = f32x4{acc[4 * i].x, acc[4 * i + 1].x, acc[4 * i + 2].x, acc[4 * i + 3].x};
-                r4[i] = f32x4{acc[4 * i].y, acc[4 * i + 1].y, acc[4 * i + 2].y, acc[4 * i + 3].y};
-            }
+            win_store_row_slab(acc, slab_wg + (t - first_tile) * 2 * TILE + 2048 * wv + 32 * lane0, TILE);
         };
         long open_tile = -1;                                 // tile whose partial sums the accumulators hold
         // Unit blocks: the lane's five tap rows, crossfade weights and x row depend on the TILE (where its window starts
@@ -234,17 +188,9 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                 if (open_tile >= 0) flush(open_tile);        // (in front of the barrier: under the stagers' work)
                 open_tile = tile;
             }
-            auto weight = [&](int m) {                       // crossfade weight of the subchunk that holds offset m of its chunk
-                if (A.s_pow2) return (float)(m & ~(A.S - 1)) * A.invK;
-                int q = (int)((float)m * A.invS);            // any multiple of 32: m / S by float estimate, corrected
-                const int r = m - q * A.S;
-                if (r < 0) q -= 1;
-                if (r >= A.S) q += 1;
-                return (float)(q * A.S) * A.invK;
-            };
             if constexpr (UNITLEN != 0) {
                 const int cur_buf = (int)(pid & 1);
-                const long akey = tile * nseg + sg;                          // (IRs of several segments: the window moves with the segment)
+                const long akey = tile * W.nseg + sg;                          // (IRs of several segments: the window moves with the segment)
                 if (akey == addr_tile && cur_buf != addr_buf) {              // (uniform) same rows, the other buffer: in place
                     const unsigned delta = cur_buf ? buf_bytes : 0u - buf_bytes;
 #pragma unroll
@@ -257,17 +203,14 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                     addr_buf = cur_buf;
                     const unsigned bufb = (unsigned)reinterpret_cast<uintptr_t>(lds4 + cur_buf * buf4);
                     const int row_out = 64 * wv + lane + G.halo;             // window row holding the lane's outputs
-                    const int pos = G.mo0 + 32 * row_out;
-                    int sl = (int)((float)pos * A.invK);                     // chunk slot of that row (float estimate, corrected)
-                    int m_in = pos - sl * A.K;                               // offset of the row inside its chunk
-                    if (m_in < 0) { m_in += A.K; sl -= 1; }
-                    if (m_in >= A.K) { m_in -= A.K; sl += 1; }
+                    int sl, m_in;                                            // chunk slot of that row, its offset inside the chunk
+                    win_row_slot(G.mo0 + 32 * row_out, A.K, A.invK, sl, m_in);
                     xrow4 = bufb + 16u * (unsigned)(row_out - 4);            // the x row of step 4 (step r reads 16 (4 - r) bytes above)
                     unsigned tap = bufb + 4u * (unsigned)(XFLOATS + sl * HD_SLOT - 32 * 4);   // tap row of step 0
 #pragma unroll
                     for (int r = 0; r < 5; ++r) {
-                        alv[r] = weight(m_in);
-                        if constexpr (NSUB == 2) blv[r] = weight(m_in + 16);   // inputs 16-31 of the row: the next subchunk
+                        alv[r] = win_weight(m_in, A.S, A.s_pow2, A.invK, A.invS);
+                        if constexpr (NSUB == 2) blv[r] = win_weight(m_in + 16, A.S, A.s_pow2, A.invK, A.invS);   // inputs 16-31 of the row: the next subchunk
                         tapv[r] = tap;
                         m_in -= 32;
                         const bool wrap = m_in < 0;                          // the next row up lies in the chunk before: one slot down
@@ -308,39 +251,17 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                 (void)hd; (void)Lseg; (void)halo;
             } else {
                 const int row_out = 64 * wv + lane + halo;   // window row holding the lane's outputs
-                const int pos = G.mo0 + 32 * row_out;
-                int sl = (int)((float)pos * A.invK);         // chunk slot of that row (float estimate, corrected)
-                int m_in = pos - sl * A.K;                   // offset of the row inside its chunk
-                if (m_in < 0) { m_in += A.K; sl -= 1; }
-                if (m_in >= A.K) { m_in -= A.K; sl += 1; }
+                int sl, m_in;                                // chunk slot of that row, its offset inside the chunk
+                win_row_slot(G.mo0 + 32 * row_out, A.K, A.invK, sl, m_in);
                 const f32x4 *xrow = xs4 + row_out;
 #pragma unroll 1
                 for (int rp = 0; rp <= halo; ++rp) {             // input rows rho' = 0..halo above/at the lane's output row
-                    float al;
-                    if (A.s_pow2) {
-                        al = (float)(m_in & ~(A.S - 1)) * A.invK;
-                    } else {                                     // any multiple of 32: m_in / S by float estimate, corrected
-                        int q = (int)((float)m_in * A.invS);
-                        const int r = m_in - q * A.S;
-                        if (r < 0) q -= 1;
-                        if (r >= A.S) q += 1;
-                        al = (float)(q * A.S) * A.invK;
-                    }
-                    // octet i holds taps t0 = 32 rp - 32 + 8 i .. + 7 of the segment and is live for 0 <= t0 < Lseg (a multiple of 8):
-                    // i in [lo, hi).  (Closed form: eight compare-and-or chains per row step were 60 scalar instructions, which a wave
-                    // that has its SIMD to itself pays ~6 clocks each for.)
-                    const int oct_lo = 4 - 4 * rp > 0 ? 4 - 4 * rp : 0;
-                    int oct_hi = (Lseg + 32 - 32 * rp) >> 3;         // >= 1 for rp <= halo
-                    oct_hi = oct_hi > 8 ? 8 : oct_hi;
-                    const unsigned mk = ((1u << oct_hi) - 1u) & ~((1u << oct_lo) - 1u);
+                    const float al = win_weight(m_in, A.S, A.s_pow2, A.invK, A.invS);
+                    const unsigned mk = win_octet_mask(rp, Lseg);
                     ffa_row_step_asm<XR>(accA, accB, accB16, accP, (unsigned)reinterpret_cast<uintptr_t>(xrow),
                                          (unsigned)reinterpret_cast<uintptr_t>(hd + sl * HD_SLOT + (32 * rp - 32) * 4), al, mk);
                     xrow -= 1;
-                    m_in -= 32;
-                    if (m_in < 0) {
-                        m_in += A.K;
-                        sl -= 1;
-                    }
+                    win_row_up(A.K, sl, m_in);
                 }
             }
 #ifdef BAS_STAMPS
@@ -361,7 +282,8 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
         const unsigned L4 = 4u * (unsigned)A.L;
         // this wave's share of the nslots + 1 chunk IRs: balanced contiguous ranges [slot_a, slot_b) - 5, 5, 4, 4 for the 18
         // IRs under a tile of 8192 at K = 512; it writes the slots [slot_a, slot_b): slot i holds (IR i, IR i+1 - IR i), so its
-        // LAST slot needs the FIRST IR of the next wave, which that wave leaves in LDS as soon as it has it (bnd / flags)
+        // LAST slot needs the FIRST IR of the next wave, which that wave leaves in LDS as soon as it has it (bnd / flags).
+        // (The deal of bas_render_fz_kernel and bas_render_fq_kernel; a copy because both ends go through readfirstlane here.)
         const int n_ir = A.nslots + 1, base = n_ir / NW, rem = n_ir - base * NW;
         const int slot_a = rfl(wv * base + (wv < rem ? wv : rem));     // (wave-uniform, and told so: the buffer loads below
         const int slot_b = rfl(slot_a + base + (wv < rem ? 1 : 0));    //  take scalar bases - a vector one costs a waterfall loop)
@@ -398,26 +320,16 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                         const_cast<f32x4 *>(pl_src + (long)c_first * PL4), 0, n_ev * PL4 * 16, 0x00020000);
 #pragma unroll
                     for (int r = 0; r < NPV; ++r)            // (pieces past the run read as zero and are not stored)
-                        pv[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, (int)l16, 1024 * r, FZ_NT_LOADS ? 2 : 0));
+                        pv[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pr, (int)l16, 1024 * r, 2));
                 } else {
 #pragma unroll
                     for (int r = 0; r < NPV; ++r) {
-                        int p = lane + 64 * r;                   // 16-byte piece of the wave's n_ev * 18
-                        p = p < n_ev * PL4 ? p : 0;
-                        const int i = (p * 3641) >> 16;          // p / 18 for p < 1000
-                        const int c = clampi(c_first + i, 0, A.n_chunks);
-#if FZ_NT_LOADS
-                        pv[r] = __builtin_nontemporal_load(pl_src + (long)c * PL4 + (p - i * PL4));
-#else
-                        pv[r] = pl_src[(long)c * PL4 + (p - i * PL4)];
-#endif
+                        pv[r] = __builtin_nontemporal_load(win_plan_piece(pl_src, lane, r, n_ev, c_first, A.n_chunks));
                     }
                 }
             }
-            const long lo_l = -xbase, hi_l = A.T_in - xbase;     // offsets of the signal's first sample / one past its last
-            const int x_lo = lo_l < -(1 << 30) ? -(1 << 30) : (lo_l > (1 << 30) ? (1 << 30) : (int)lo_l);
-            const int x_hi = hi_l < -(1 << 30) ? -(1 << 30) : (hi_l > (1 << 30) ? (1 << 30) : (int)hi_l);
-            const bool x_inside = x_lo <= 0 && x_hi >= 4 * NX * THREADS;   // whole window inside the signal
+            const WinXBounds XB = win_x_bounds(xbase, A.T_in);
+            const bool x_inside = win_x_inside<NX, THREADS>(XB);   // whole window inside the signal
             {
                 const float *xwin = x + (long)s * A.x_stride + xbase;
                 if (x_inside) {
@@ -425,19 +337,15 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                                                                                         16 * NX * THREADS, 0x00020000);
 #pragma unroll
                     for (int j = 0; j < NX; ++j)             // streamed once
-                        xv[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)v16, 16 * THREADS * j, FZ_NT_LOADS ? 2 : 0));
+                        xv[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)v16, 16 * THREADS * j, 2));
                 } else {
                     asm volatile("" ::: "memory");           // (keeps the two forms apart: merged, every load pays the clamps)
 #pragma unroll
                     for (int j = 0; j < NX; ++j) {
                         int i = 4 * (tid + j * THREADS);
-                        i = i < x_lo ? x_lo : i;
-                        i = i > x_hi - 4 ? x_hi - 4 : i;     // clamped into the row (T_in is a multiple of K >= 32)
-#if FZ_NT_LOADS
+                        i = i < XB.lo ? XB.lo : i;           // (win_fetch_x, apart: behind the barrier above the helper's form
+                        i = i > XB.hi - 4 ? XB.hi - 4 : i;   //  compiles to other scalar instructions)
                         xv[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xwin + i));
-#else
-                        xv[j] = *reinterpret_cast<const f32x4 *>(xwin + i);
-#endif
                     }
                 }
             }
@@ -452,8 +360,8 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                     asm volatile("" ::: "memory");
 #pragma unroll
                     for (int j = 0; j < NX; ++j) {
-                        const int e = 4 * (tid + j * THREADS);   // x_lo, x_hi are multiples of 4: all four in or out
-                        if (!(e >= x_lo && e < x_hi)) xv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        const int e = 4 * (tid + j * THREADS);   // the bounds are multiples of 4: all four in or out
+                        if (!(e >= XB.lo && e < XB.hi)) xv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
                     }
                 }
 #pragma unroll

@@ -25,7 +25,7 @@
 // workgroups share a CU.  No MFMA: this is a 1-D FIR (BASELINE.json north_star).
 #include "bas_internal.h"
 #include "bas_plan.h"
-#include "bas_fir.h"
+#include "bas_window.h"
 #include "bas_tail.h"
 #include <stdlib.h>
 #include <string.h>
@@ -455,11 +455,15 @@ __global__ __launch_bounds__(HD_THREADS, 2) void bas_render_hd_kernel(RenderArgs
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    const long unit0 = (long)blockIdx.x * A.units_per_wg;
-    long unit1 = unit0 + A.units_per_wg;
-    if (unit1 > A.units_total) unit1 = A.units_total;
-    const int nseg = (A.Lp + RT_SEG - 1) / RT_SEG;
-    const long n_pass = (unit1 - unit0) * nseg;
+    const WinWalk W = win_walk(A.units_total, A.units_per_wg, A.Lp);
+    const long unit0 = W.unit0, n_pass = W.n_pass;
+    const int nseg = W.nseg;
+    // (of bas_window.h this kernel takes the walk, the window geometry and the x bounds.  The rest stays written out below:
+    // on the shared helpers it computes the same values, but the compiled kernels change - win_store_row_slab: <2, true>
+    // gets 12 bytes of scratch and 2 spilled VGPRs, <4, *> 256 VGPRs for 254 and 20-24 bytes of scratch; win_octet_mask: one
+    // SGPR more in <2, true>, <4, true> and <4, false>; win_weight, win_row_up and a shared time slice: other branch senses,
+    // another encoding of v_subbrev inside the row-step loop, 31 more s_waitcnt.  The slot of a row by pos / K belongs to
+    // this kernel's per-pass setup.)
     if (n_pass <= 0) return;
 #ifdef BAS_STAMPS
     const unsigned long long st_begin = __builtin_amdgcn_s_memrealtime();
@@ -506,17 +510,11 @@ __global__ __launch_bounds__(HD_THREADS, 2) void bas_render_hd_kernel(RenderArgs
 
     for (long pid = 0; pid < n_pass; ++pid) {
         const long unit = unit0 + pid / nseg;
-        const int seg0 = (int)(pid % nseg) * RT_SEG;
         const long tile = unit / A.n_src;
         const int s = (int)(unit - tile * A.n_src);
-        const int Lseg = A.Lp - seg0 < RT_SEG ? A.Lp - seg0 : RT_SEG;
-        const int halo = (Lseg + 31) >> 5;                   // input rows above the tile that matter
-        const long xbase = tile * HD_TILE - seg0 - 32L * halo;   // first input sample in LDS (mult. of 32)
-        const int nrows = HD_TILE / 32 + halo;
-        long cf = xbase / A.K;                               // floor division, consistent across 0
-        if (cf * A.K > xbase) --cf;
-        const int c0 = (int)cf;
-        const int mo0 = (int)(xbase - cf * A.K);
+        const WinGeo G = win_geo<HD_TILE>(tile, (int)(pid % nseg), A.K, A.Lp);
+        const int seg0 = G.seg0, Lseg = G.Lseg, halo = G.halo, nrows = G.nrows, c0 = G.c0, mo0 = G.mo0;
+        const long xbase = G.xbase;
         if (tile != cur_tile) {
             flush(cur_tile);
             cur_tile = tile;
@@ -526,11 +524,10 @@ __global__ __launch_bounds__(HD_THREADS, 2) void bas_render_hd_kernel(RenderArgs
         // window offsets i = 4 (tid + 256 j) are per-thread constants; the signal's ends become two scalar
         // bounds on them (x rows are 16-byte aligned and T_in is a multiple of 4, so a float4 is all in or out)
         const float *xwin = A.x + (long)s * A.x_stride + xbase;
-        const long lo_l = -xbase, hi_l = A.T_in - xbase;     // offsets of the signal's first sample / one past its last
-        const int x_lo = lo_l < -(1 << 30) ? -(1 << 30) : (lo_l > (1 << 30) ? (1 << 30) : (int)lo_l);
-        const int x_hi = hi_l < -(1 << 30) ? -(1 << 30) : (hi_l > (1 << 30) ? (1 << 30) : (int)hi_l);
-        const bool x_inside = x_lo <= 0 && x_hi >= 4 * HD_NX * HD_THREADS;   // whole window inside the signal
-        // T_in % 4 != 0 (dual rows, odd chunk sizes): the float4 that straddles the signal's end is read whole -
+        const WinXBounds XB = win_x_bounds(xbase, A.T_in);
+        const int x_lo = XB.lo, x_hi = XB.hi;
+        const bool x_inside = win_x_inside<HD_NX, HD_THREADS>(XB);
+        // (not win_fetch_x:) T_in % 4 != 0 (dual rows, odd chunk sizes): the float4 that straddles the signal's end is read whole -
         // the row stride is a multiple of 4, so the floats exist - and masked element by element below
         const int x_hi4 = (x_hi + 3) & ~3;
         f32x4 xv[HD_NX];
@@ -631,6 +628,7 @@ __global__ __launch_bounds__(HD_THREADS, 2) void bas_render_hd_kernel(RenderArgs
         int m_in = pos - sl * A.K;                           // offset of the row inside its chunk
         const f32x4 *xrow = xs4 + row_out;
         // octet i of row step rp holds taps 32 rp - 32 + 8 i .. +7 (relative to seg0); live iff in [0, Lseg)
+        // (the loop form of win_octet_mask: same value)
         auto mask_of = [&](int rp) {
             unsigned mk = 0;
 #pragma unroll
