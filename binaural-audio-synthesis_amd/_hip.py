@@ -168,6 +168,12 @@ SIGNATURES = {
     "bas_limit_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_long,
                                _c_long, ctypes.c_double, _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p,
                                _c_void_p]),
+    # loudness and true-peak meter
+    "bas_meter_state_doubles": (_c_size_t, []),
+    "bas_meter_workspace_bytes": (_c_size_t, [_c_int, _c_long, _c_int]),
+    "bas_meter_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_int, _c_long, _c_int, _c_int, _c_void_p, _c_void_p,
+                               _c_long, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_void_p, _c_void_p, _c_size_t,
+                               _c_void_p]),
     # ambisonic beds
     "bas_ambi_matrices_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int,
                                        _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_void_p]),

@@ -23,7 +23,8 @@ limiter gives the bits of an offline one.
     limit                        a whole signal on the device (bas_limit_f32)
     StreamLimiter                the stream: process(block) is A samples late, finish() hands out the last A samples
 
-Not modelled: an exponential release, oversampled (true-peak) detection, unlinked ears, makeup gain.  Inputs must be
+Not modelled: an exponential release, oversampled (true-peak) detection (loudness.py meters the true peak and the
+programme loudness of what this stage hands out; it does not limit them), unlinked ears, makeup gain.  Inputs must be
 finite; the bit-for-bit claims hold for |y| <= 2^20 c.
 """
 import numpy as np

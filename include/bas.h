@@ -755,6 +755,52 @@ int bas_limit_f32(const float *y, long y_stride_g, long y_stride_t, long y_strid
                   int lookahead, int hold, float *state, long state_stride, float *reduction, float *peak,
                   bas_stream_t stream);
 
+/* ---- loudness meter (no reference counterpart) --------------------------------------------------------------
+ * How loud a stereo signal is, after ITU-R BS.1770 / EBU R128: the energies of the K-weighted signal per hop of 100 ms, from
+ * which the caller forms momentary, short-term and gated integrated loudness (loudness.py: readings), and the true peak, 4x
+ * oversampled.  A stage of its own behind a render, a stream or the limiter; it writes no audio.
+ *   K-weighting at fs (a multiple of 10 in 8000..192000; hop = fs / 10): two biquads per ear in binary64, transposed direct
+ *   form II, from rest at a signal's first sample and never reset.  With K = tan(pi f0 / fs), a0 = 1 + K/Q + K^2:
+ *     shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G/20),
+ *                Vb = Vh^0.4996667741545416:  b = (Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2) / a0,
+ *                a1 = 2 (K^2 - 1) / a0, a2 = (1 - K/Q + K^2) / a0;
+ *     high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773:  b = (1, -2, 1), a1 and a2 as above
+ *   (at 48 kHz the coefficients tabulated in BS.1770-4).  E[g][ear][h] = sum of z^2 over samples h hop .. (h + 1) hop - 1 of
+ *   the K-weighted signal z; a last partial hop is not counted.  The recursion is evaluated in parallel (runs from rest, a
+ *   scan with powers of the transition matrix, the runs again), so an energy is the definition's within rounding - 1e-9
+ *   relative is the tested bar - and the same call gives the same bits twice: fixed orders, no floating-point atomics.
+ *   True peak: phase 0 is the samples; phases p = 1..3 at time m + p/4 are sum_j x[m + j] taps[(p - 1) 12 + j + 5],
+ *   j = -5 .. 6: 36 binary32 taps in HOST memory, read before the launch.  The 12 products (exact in binary64) are added
+ *   one by one from +0 with j ascending and rounded to binary32 once; then |.| and the maximum, per ear, over every m whose
+ *   window touches the signal (zeros outside it).  Being a maximum it is exact whatever the order: bits do not depend on
+ *   blocks.  It travels as the bits of a binary32 value >= 0 through atomics that are sent only when they would raise it.
+ *   y at y + g y_stride_g + t y_stride_t + e y_stride_e: any strides >= 0, read without a copy.
+ *   energy at energy + g e_stride_g + e e_stride_e + h, h < max_hops, caller-owned; nothing is written at h >= max_hops.
+ *   state == NULL: a whole signal from rest; n_before must be 0; true_peak [n_sessions][2] (set to 0 by the caller; may be
+ *     NULL) takes the peak, the positions behind the end whose windows still touch the signal included.
+ *   state != NULL: a block of a stream.  state + g state_stride holds bas_meter_state_doubles() doubles per session, zeroed
+ *     before a stream's first block: per ear the sample count (on the device: a captured call replays correctly) and a copy
+ *     of it, the cascade's four states, the open hop's running sum, the last 11 input samples and a copy, the running true
+ *     peak (binary32 bits in the low half of word 13 and 33).  true_peak must be NULL.  n_before: the caller's own count of
+ *     the samples metered before this block, the largest over the sessions - used for the capacity check alone:
+ *     (n_before + T_in) / hop > max_hops is refused (BAS_E_SHAPE) before any launch.  T_in == 0 is the stream's end: the
+ *     true peak's last 11 positions; the state is not moved and the open hop is dropped.
+ *   T_in <= hop + 1 (every real-time block; it touches two hops at the most): ONE launch, one workgroup per (ear, session),
+ *     which moves the state itself.  Longer: three launches - every unit's end state from rest, the chain of the states,
+ *     the energies - with a workspace of bas_meter_workspace_bytes (0 for T_in <= hop + 1 or arguments out of range) that
+ *     need not be initialised.  No launch reads a word of the state that it writes.
+ * One stream, no allocation, no synchronisation (capturable).  Every check runs before any launch: fs, hop == fs / 10,
+ * n_sessions <= 65535, T_in < 2^30, max_hops < 2^31, strides >= 0, state_stride even and >= the state's size, the energy
+ * buffer's strides address no element twice, capacity, ws_bytes, and no two of input, energy buffer, state, true_peak and
+ * workspace overlap (BAS_E_SHAPE); taps, y (T_in > 0), energy (max_hops > 0), ws (T_in > hop + 1) required (BAS_E_NULL);
+ * y, true_peak 4-byte aligned, energy 8-byte, state and ws 16-byte (BAS_E_ALIGN). */
+size_t bas_meter_state_doubles(void);
+size_t bas_meter_workspace_bytes(int n_sessions, long T_in, int hop);
+int bas_meter_f32(const float *y, long y_stride_g, long y_stride_t, long y_stride_e, int n_sessions, long T_in, int fs,
+                  int hop, const float *taps, double *energy, long e_stride_g, long e_stride_e, long max_hops,
+                  long n_before, double *state, long state_stride, float *true_peak, void *ws, size_t ws_bytes,
+                  bas_stream_t stream);
+
 /* ---- ambisonic beds (no reference counterpart) --------------------------------------------------------
  * A bed is a sound field in real spherical harmonics: orders N = 1..3, C = (N + 1)^2 channels in ACN order, N3D inside
  * ((1 / 4 pi) int Y_a Y_b = delta_ab; no Condon-Shortley phase; SN3D input is a diagonal folded into the decoder by the
