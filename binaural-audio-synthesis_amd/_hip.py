@@ -197,6 +197,30 @@ class BasError(RuntimeError):
         self.code = code
 
 
+BAS_E_SHAPE = -2
+
+
+class _ShapeErrors:
+    """Inside, a BasError of code BAS_E_SHAPE leaves as ValueError with the same text (a layout or a size the caller chose:
+    an argument error, where the stage's own checks raise ValueError too); anything else passes."""
+
+    def __enter__(self):
+        return None
+
+    def __exit__(self, kind, e, tb):
+        if isinstance(e, BasError) and e.code == BAS_E_SHAPE:
+            raise ValueError(str(e)) from None
+        return False
+
+
+_SHAPE_ERRORS = _ShapeErrors()                 # (no state: one serves every call)
+
+
+def shape_errors():
+    """The context manager of the stages that report a refused layout as an argument error."""
+    return _SHAPE_ERRORS
+
+
 def _load(path):
     if not os.path.exists(path):
         raise RuntimeError(

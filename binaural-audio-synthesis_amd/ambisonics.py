@@ -23,6 +23,7 @@ import math
 import numpy as np
 
 from . import _hip, sphere
+from ._stage import is_device
 
 MAX_ORDER = 3
 MAX_CHANNELS = 16                                  # BAS_AMBI_MAX_CHANNELS
@@ -361,19 +362,13 @@ def encode(signals, K, E, base=None):
 
 
 # ---- the device side ------------------------------------------------------------------------------------------------------
-def _shape_error(e):
-    if e.code == -2:                                                   # BAS_E_SHAPE
-        raise ValueError(str(e)) from None
-    raise e
-
-
 def mixing_matrices_device(decoder, head, out=None):
     """One bas_ambi_matrices_f32 launch: head [nb, 4] or [G, nb, 4] (a float64 device tensor, checked for shape and dtype
     only; anything else goes through sphere.check_head and is uploaded) -> M float32 [.., nb, V, C] on the device.
     out: a float32 device tensor of that shape, any strides >= 0 over the leading axes that address every element once,
     [V, C] dense (a view with gaps keeps its gaps)."""
     import torch
-    if isinstance(head, torch.Tensor) and head.is_cuda:
+    if is_device(head):
         if head.dtype != torch.float64 or head.dim() not in (2, 3) or head.shape[-1] != 4:
             raise ValueError("head must be a float64 tensor [nb, 4] or [G, nb, 4]")
         q, dev = head, head.device
@@ -389,7 +384,7 @@ def mixing_matrices_device(decoder, head, out=None):
     shape = tuple(q.shape[:-1]) + (V, C)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+    elif not (is_device(out) and out.dtype == torch.float32 and tuple(out.shape) == shape
               and out.device == dev):
         raise ValueError(f"out must be a float32 tensor of shape {shape} on {dev}")
     if shape[-3] * (shape[0] if q.dim() == 3 else 1) == 0:
@@ -398,13 +393,10 @@ def mixing_matrices_device(decoder, head, out=None):
         raise ValueError("out: the [V, C] matrices must be dense")
     G, hs_g, ms_g = (q.shape[0], q.stride(0), out.stride(0)) if q.dim() == 3 else (1, 0, 0)
     D, Q, S, _ = decoder.on(dev)
-    try:
-        with _hip.on_device(dev):
-            _hip.call("bas_ambi_matrices_f32", _hip.ptr(q), hs_g, q.stride(-2), _hip.ptr(D), _hip.ptr(Q), _hip.ptr(S),
-                      int(S.shape[0]), decoder.order, V, G, int(q.shape[-2]), _hip.ptr(out), ms_g, out.stride(-3),
-                      _hip.current_stream(dev))
-    except _hip.BasError as e:
-        _shape_error(e)
+    with _hip.shape_errors(), _hip.on_device(dev):
+        _hip.call("bas_ambi_matrices_f32", _hip.ptr(q), hs_g, q.stride(-2), _hip.ptr(D), _hip.ptr(Q), _hip.ptr(S),
+                  int(S.shape[0]), decoder.order, V, G, int(q.shape[-2]), _hip.ptr(out), ms_g, out.stride(-3),
+                  _hip.current_stream(dev))
     return out
 
 
@@ -415,7 +407,7 @@ def decode_device(bed, K, M, out):
     [nb, V, C] (shared) or [G, nb, V, C] with nb >= (T - 1) // K + 2, or nb == 1: static.  [V, C] dense.  Returns out."""
     import torch
     for t, name in ((bed, "bed"), (M, "M"), (out, "out")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        if not (is_device(t) and t.dtype == torch.float32):
             raise ValueError(f"{name} must be a float32 device tensor")
     if out.dim() not in (2, 3) or bed.dim() not in (2, 3) or M.dim() not in (2, 3, 4):
         raise ValueError("out must be [V, T] or [G, V, T], bed [C, T] or [G, C, T], M [V, C], [nb, V, C] or [G, nb, V, C]")
@@ -438,12 +430,9 @@ def decode_device(bed, K, M, out):
     ms_g = M.stride(0) if M.dim() == 4 else 0
     ms_k = 0 if nb == 1 else M.stride(-3)
     ys_g = out.stride(0) if out.dim() == 3 else 0
-    try:
-        with _hip.on_device(dev):
-            _hip.call("bas_matrix_mix_f32", _hip.ptr(bed), xs_g, bed.stride(-2), _hip.ptr(M), ms_g, ms_k, C, V, G, T, int(K),
-                      _hip.ptr(out), ys_g, out.stride(-2), _hip.current_stream(dev))
-    except _hip.BasError as e:
-        _shape_error(e)
+    with _hip.shape_errors(), _hip.on_device(dev):
+        _hip.call("bas_matrix_mix_f32", _hip.ptr(bed), xs_g, bed.stride(-2), _hip.ptr(M), ms_g, ms_k, C, V, G, T, int(K),
+                  _hip.ptr(out), ys_g, out.stride(-2), _hip.current_stream(dev))
     return out
 
 
@@ -487,7 +476,7 @@ def render_bed(bed, chunksize, subchunksize, tbl, decoder, head=None, normalize=
     import torch
     tbl = as_device_table(tbl)
     x = _bed_to_device(bed, decoder.C, tbl.device)
-    if isinstance(head, torch.Tensor) and head.is_cuda and head.device != tbl.device:
+    if is_device(head) and head.device != tbl.device:
         head = head.to(tbl.device)
     feeds, elev, azim = bed_sources(x, chunksize, decoder, head)
     return render_sources(feeds, chunksize, subchunksize, elev, azim, tbl, normalize=normalize)
@@ -587,7 +576,7 @@ class BedStream:
         if self._B != B:
             self.prepare(B)
         nb = B // self.renderer.K + 1
-        if isinstance(bed_block, torch.Tensor) and bed_block.is_cuda and bed_block.dtype == torch.float32 \
+        if is_device(bed_block) and bed_block.dtype == torch.float32 \
                 and bed_block.device == self.device and bed_block.stride(-1) == 1:
             x = bed_block
         else:
@@ -611,7 +600,7 @@ def _angles_to_device(elev, azim, gain, dev=None):
     stride over the boundaries, and whether the caller's form had the group axis.  Device tensors are checked for shape
     and dtype only; host data is validated (finite) and uploaded."""
     import torch
-    on_dev = [isinstance(t, torch.Tensor) and t.is_cuda for t in (elev, azim)]
+    on_dev = [is_device(t) for t in (elev, azim)]
     if all(on_dev):
         if elev.dtype != torch.float64 or azim.dtype != torch.float64 or elev.dim() not in (2, 3) or elev.shape != azim.shape:
             raise ValueError("elev and azim must be float64 tensors of one shape [n_src, nb] or [G, n_src, nb]")
@@ -621,7 +610,7 @@ def _angles_to_device(elev, azim, gain, dev=None):
             e, a = e.contiguous(), a.contiguous()
         g = None
         if gain is not None:
-            if isinstance(gain, torch.Tensor) and gain.is_cuda:
+            if is_device(gain):
                 if gain.dtype != torch.float64 or gain.shape != e.shape:
                     raise ValueError(f"gain must be a float64 tensor of shape {tuple(e.shape)}")
                 g = gain if gain.stride(-1) == 1 and min(gain.stride()) >= 0 else gain.contiguous()
@@ -658,7 +647,7 @@ def encoding_gains_device(elev, azim, order, norm="sn3d", gain=None, out=None):
     shape = ((G,) if grouped else ()) + (nb, n_src, C)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+    elif not (is_device(out) and out.dtype == torch.float32 and tuple(out.shape) == shape
               and out.device == dev):
         raise ValueError(f"out must be a float32 tensor of shape {shape} on {dev}")
     if not 1 <= n_src <= ENCODE_MAX_SOURCES:
@@ -667,14 +656,11 @@ def encoding_gains_device(elev, azim, order, norm="sn3d", gain=None, out=None):
         return out
     if out.stride(-1) != 1 or out.stride(-2) != C:
         raise ValueError("out: the [n_src, C] banks must be dense")
-    try:
-        with _hip.on_device(dev):
-            _hip.call("bas_ambi_encode_gains_f32", _hip.ptr(e), _hip.ptr(a), e.stride(0) if grouped else 0, e.stride(1),
-                      _hip.ptr(g), 0 if g is None or not grouped else g.stride(0), 0 if g is None else g.stride(1),
-                      scale.ctypes.data, int(order), G, n_src, nb, _hip.ptr(out), out.stride(0) if grouped else 0,
-                      out.stride(-3), _hip.current_stream(dev))
-    except _hip.BasError as err:
-        _shape_error(err)
+    with _hip.shape_errors(), _hip.on_device(dev):
+        _hip.call("bas_ambi_encode_gains_f32", _hip.ptr(e), _hip.ptr(a), e.stride(0) if grouped else 0, e.stride(1),
+                  _hip.ptr(g), 0 if g is None or not grouped else g.stride(0), 0 if g is None else g.stride(1),
+                  scale.ctypes.data, int(order), G, n_src, nb, _hip.ptr(out), out.stride(0) if grouped else 0,
+                  out.stride(-3), _hip.current_stream(dev))
     return out
 
 
@@ -687,7 +673,7 @@ def encode_device(x, K, E, out, base=None):
     (in place) or a tensor that does not overlap it.  Returns out."""
     import torch
     for t, name in ((x, "x"), (E, "E"), (out, "out")) + (() if base is None else ((base, "base"),)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        if not (is_device(t) and t.dtype == torch.float32):
             raise ValueError(f"{name} must be a float32 device tensor")
     if out.dim() not in (2, 3) or x.dim() not in (2, 3) or E.dim() not in (2, 3, 4):
         raise ValueError("out must be [C, T] or [G, C, T], x [n_src, T] or [G, n_src, T], E [n_src, C], [nb, n_src, C] or "
@@ -716,12 +702,9 @@ def encode_device(x, K, E, out, base=None):
     es_k = 0 if nb == 1 else E.stride(-3)
     ys_g = out.stride(0) if out.dim() == 3 else 0
     bs_g, bs_c = (0, 0) if base is None else (base.stride(0) if base.dim() == 3 else 0, base.stride(-2))
-    try:
-        with _hip.on_device(dev):
-            _hip.call("bas_ambi_encode_f32", _hip.ptr(x), xs_g, x.stride(-2), _hip.ptr(E), es_g, es_k, n_src, C, G, T, K,
-                      _hip.ptr(base), bs_g, bs_c, _hip.ptr(out), ys_g, out.stride(-2), _hip.current_stream(dev))
-    except _hip.BasError as err:
-        _shape_error(err)
+    with _hip.shape_errors(), _hip.on_device(dev):
+        _hip.call("bas_ambi_encode_f32", _hip.ptr(x), xs_g, x.stride(-2), _hip.ptr(E), es_g, es_k, n_src, C, G, T, K,
+                  _hip.ptr(base), bs_g, bs_c, _hip.ptr(out), ys_g, out.stride(-2), _hip.current_stream(dev))
     return out
 
 
@@ -759,8 +742,8 @@ def encode_bed(signals, chunksize, elev, azim, order, norm="sn3d", gain=None, de
             if tuple(base.shape) != (C, T):
                 raise ValueError(f"base must be [{C}, {T}]")
         out = padded_rows(C, T, dev)
-        E = encoding_gains_device(*(t.to(dev) if isinstance(t, torch.Tensor) and t.is_cuda else t for t in (elev, azim)),
-                                  order, norm, gain.to(dev) if isinstance(gain, torch.Tensor) and gain.is_cuda else gain)
+        E = encoding_gains_device(*(t.to(dev) if is_device(t) else t for t in (elev, azim)),
+                                  order, norm, gain.to(dev) if is_device(gain) else gain)
         if T:
             encode_device(x, K, E, out, base)
     return out
@@ -838,7 +821,7 @@ class BedEncoder:
         import torch
         if arg is None:
             return buf
-        if isinstance(arg, torch.Tensor) and arg.is_cuda:
+        if is_device(arg):
             if arg.dtype != torch.float64 or tuple(arg.shape) != tuple(buf.shape) or arg.device != self.device:
                 raise ValueError(f"{name} must be a float64 tensor of shape {tuple(buf.shape)} on {self.device}")
             return arg
@@ -857,7 +840,7 @@ class BedEncoder:
         out."""
         import torch
         lead = () if self.G is None else (self.G,)
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
+        if not (is_device(out) and out.dtype == torch.float32
                 and out.dim() == len(lead) + 2 and tuple(out.shape[:-1]) == lead + (self.C,)):
             raise ValueError(f"out must be a float32 device tensor {list(lead + (self.C,))} x B")
         B = int(out.shape[-1])
@@ -866,7 +849,7 @@ class BedEncoder:
         self._ready(B)
         if block is None:
             x = self._x
-        elif isinstance(block, torch.Tensor) and block.is_cuda:              # read where it is: refused unless it can be
+        elif is_device(block):              # read where it is: refused unless it can be
             if block.dtype != torch.float32 or block.device != self.device or tuple(block.shape) != tuple(self._x.shape) \
                     or block.stride(-1) != 1:
                 raise ValueError(f"a device block must be float32 {list(self._x.shape)} on {self.device} with unit sample "

@@ -18,6 +18,7 @@ import math
 import numpy as np
 
 from . import _hip
+from ._stage import host_array, is_device
 from . import sphere
 
 
@@ -178,7 +179,7 @@ def interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=No
 # ---- per-source gain at chunk boundaries -----------------------------------------------------------
 def check_gain(gain, shape):
     """A host gain argument as a float64 numpy array of `shape`: ValueError for another shape or non-finite values."""
-    arr = np.asarray(gain.numpy() if hasattr(gain, "numpy") else gain, dtype=np.float64)
+    arr = np.asarray(host_array(gain), dtype=np.float64)
     if arr.shape != tuple(shape):
         raise ValueError(f"gain must have shape {tuple(shape)}, got {arr.shape}")
     if not np.isfinite(arr).all():
@@ -190,7 +191,7 @@ def is_device_arg(arg, shape, dtype, name):
     """A per-boundary argument (gain, delay) is a device tensor: checked for shape and dtype only (as device angles and
     heads are).  False for host data, which the argument's check_* function validates."""
     import torch
-    if not (isinstance(arg, torch.Tensor) and arg.is_cuda):
+    if not (is_device(arg)):
         return False
     if tuple(arg.shape) != tuple(shape) or arg.dtype != dtype:
         raise ValueError(f"{name} must be a {str(dtype).split('.')[-1]} tensor of shape {tuple(shape)}")
@@ -220,7 +221,7 @@ def _flat_device_gain(gain, n_q):
     import torch
     if gain is None:
         return None
-    if not (isinstance(gain, torch.Tensor) and gain.is_cuda and gain.dtype == torch.float64 and gain.is_contiguous()
+    if not (is_device(gain) and gain.dtype == torch.float64 and gain.is_contiguous()
             and gain.numel() == n_q):
         raise ValueError(f"gain must be a contiguous float64 device tensor of {n_q} values (one per chunk boundary)")
     return gain.reshape(-1)

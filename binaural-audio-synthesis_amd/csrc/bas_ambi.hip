@@ -168,11 +168,6 @@ __global__ __launch_bounds__(MM_THREADS) void bas_matrix_mix_kernel(
     }
 }
 
-static inline bool ambi_ranges_meet(const void *a, long na, const void *b, long nb, int bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uintptr_t)nb * bytes && b0 < a0 + (uintptr_t)na * bytes;
-}
-
 extern "C" int bas_ambi_matrices_f32(const double *head, long hs_g, long hs_c, const double *D, const double *Q,
                                      const double *S, int J, int order, int V, int n_groups, int nb, float *m, long ms_g,
                                      long ms_k, bas_stream_t stream) {
@@ -189,9 +184,7 @@ extern "C" int bas_ambi_matrices_f32(const double *head, long hs_g, long hs_c, c
     BAS_REQUIRE(bas_layout_one_to_one(n_groups, nb, (long)V * C, ms_g, ms_k), BAS_E_SHAPE,
                 "bas_ambi_matrices_f32: the output's strides address an element twice");
     BAS_REQUIRE(head && D && Q && S && m, BAS_E_NULL, "bas_ambi_matrices_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(head) & 7) == 0 && (reinterpret_cast<uintptr_t>(D) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(Q) & 7) == 0 && (reinterpret_cast<uintptr_t>(S) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(m) & 3) == 0,
+    BAS_REQUIRE(bas_aligned(head, 8) && bas_aligned(D, 8) && bas_aligned(Q, 8) && bas_aligned(S, 8) && bas_aligned(m, 4),
                 BAS_E_ALIGN, "bas_ambi_matrices_f32: head, D, Q, S must be 8-byte aligned, m 4-byte");
     hipLaunchKernelGGL(bas_ambi_matrices_kernel, dim3((unsigned)((long)n_groups * nb)), dim3(AMBI_THREADS), 0,
                        bas_stream(stream), head, hs_g, hs_c, D, Q, S, J, order, V, nb, m, ms_g, ms_k);
@@ -217,26 +210,27 @@ extern "C" int bas_matrix_mix_f32(const float *x, long xs_g, long xs_c, const fl
     BAS_REQUIRE(n_groups >= 0 && n_groups <= 65535 && T >= 0 && K > 0, BAS_E_SHAPE,
                 "bas_matrix_mix_f32: need 0 <= n_groups <= 65535, T >= 0 and K > 0");
     BAS_REQUIRE(T < (1L << 30), BAS_E_SHAPE, "bas_matrix_mix_f32: T (%ld) must be below 2^30", T);
-    BAS_REQUIRE(xs_g >= 0 && xs_c >= 0 && ms_g >= 0 && ms_k >= 0 && ys_g >= 0 && ys_v >= 0, BAS_E_SHAPE,
+    BAS_REQUIRE(bas_none_negative({xs_g, xs_c, ms_g, ms_k, ys_g, ys_v}), BAS_E_SHAPE,
                 "bas_matrix_mix_f32: strides must be >= 0");
-    BAS_REQUIRE(xs_g < (1L << 40) && xs_c < (1L << 40) && ms_g < (1L << 40) && ms_k < (1L << 40) && ys_g < (1L << 40) &&
-                    ys_v < (1L << 40),
-                BAS_E_SHAPE, "bas_matrix_mix_f32: strides must be below 2^40");
+    BAS_REQUIRE(bas_all_below(1L << 40, {xs_g, xs_c, ms_g, ms_k, ys_g, ys_v}), BAS_E_SHAPE,
+                "bas_matrix_mix_f32: strides must be below 2^40");
     BAS_REQUIRE(ms_k == 0 || ms_k >= (long)V * C, BAS_E_SHAPE,
                 "bas_matrix_mix_f32: ms_k must be 0 (static) or >= V C (the matrices of two boundaries overlap)");
     if (n_groups == 0 || T == 0) return 0;
     BAS_REQUIRE(bas_layout_one_to_one(n_groups, V, T, ys_g, ys_v), BAS_E_SHAPE,
                 "bas_matrix_mix_f32: the output's strides address an element twice");
     BAS_REQUIRE(x && m && y, BAS_E_NULL, "bas_matrix_mix_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(m) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(y) & 3) == 0,
-                BAS_E_ALIGN, "bas_matrix_mix_f32: x, m, y must be 4-byte aligned");
-    const long x_n = (n_groups - 1) * xs_g + (C - 1) * xs_c + T, y_n = (n_groups - 1) * ys_g + (V - 1) * ys_v + T;
-    BAS_REQUIRE(!ambi_ranges_meet(x, x_n, y, y_n, 4), BAS_E_SHAPE,
+    BAS_REQUIRE(bas_aligned(x, 4) && bas_aligned(m, 4) && bas_aligned(y, 4), BAS_E_ALIGN,
+                "bas_matrix_mix_f32: x, m, y must be 4-byte aligned");
+    const long x_ext[3] = {n_groups, C, T}, x_str[3] = {xs_g, xs_c, 1};
+    const long y_ext[3] = {n_groups, V, T}, y_str[3] = {ys_g, ys_v, 1};
+    const size_t y_bytes = 4 * (size_t)bas_view_extent(3, y_ext, y_str);
+    BAS_REQUIRE(!bas_ranges_meet(x, 4 * (size_t)bas_view_extent(3, x_ext, x_str), y, y_bytes), BAS_E_SHAPE,
                 "bas_matrix_mix_f32: input and output overlap (the mix does not run in place)");
     const long n_k = ms_k == 0 ? 1 : (T - 1) / K + 2;
-    const long m_n = (n_groups - 1) * ms_g + (n_k - 1) * ms_k + (long)V * C;
-    BAS_REQUIRE(!ambi_ranges_meet(m, m_n, y, y_n, 4), BAS_E_SHAPE, "bas_matrix_mix_f32: matrices and output overlap");
+    const long m_ext[3] = {n_groups, n_k, (long)V * C}, m_str[3] = {ms_g, ms_k, 1};
+    BAS_REQUIRE(!bas_ranges_meet(m, 4 * (size_t)bas_view_extent(3, m_ext, m_str), y, y_bytes), BAS_E_SHAPE,
+                "bas_matrix_mix_f32: matrices and output overlap");
     // a tile touches (tile - 1) / K + 3 boundaries at most, and LDS holds MM_LDS_FLOATS / (V CP) matrices (>= 8): whole
     // tiles where the chunks are long enough, shorter ones (a multiple of 4 samples) below
     const int CP = (C + 3) & ~3;
@@ -482,19 +476,17 @@ extern "C" int bas_ambi_encode_gains_f32(const double *elev, const double *azim,
     BAS_REQUIRE(n_groups >= 0 && nb >= 0 && (long)n_groups * nb <= (1L << 30) &&
                     (long)n_groups * nb * n_src <= (1L << 30),
                 BAS_E_SHAPE, "bas_ambi_encode_gains_f32: need n_groups, nb >= 0 and n_groups nb n_src <= 2^30");
-    BAS_REQUIRE(as_g >= 0 && as_s >= 0 && gs_g >= 0 && gs_s >= 0 && es_g >= 0 && es_k >= 0, BAS_E_SHAPE,
+    BAS_REQUIRE(bas_none_negative({as_g, as_s, gs_g, gs_s, es_g, es_k}), BAS_E_SHAPE,
                 "bas_ambi_encode_gains_f32: strides must be >= 0");
-    BAS_REQUIRE(as_g < (1L << 40) && as_s < (1L << 40) && gs_g < (1L << 40) && gs_s < (1L << 40) && es_g < (1L << 40) &&
-                    es_k < (1L << 40),
-                BAS_E_SHAPE, "bas_ambi_encode_gains_f32: strides must be below 2^40");
+    BAS_REQUIRE(bas_all_below(1L << 40, {as_g, as_s, gs_g, gs_s, es_g, es_k}), BAS_E_SHAPE,
+                "bas_ambi_encode_gains_f32: strides must be below 2^40");
     if ((long)n_groups * nb == 0) return 0;
     const int C = (order + 1) * (order + 1);
     BAS_REQUIRE(bas_layout_one_to_one(n_groups, nb, (long)n_src * C, es_g, es_k), BAS_E_SHAPE,
                 "bas_ambi_encode_gains_f32: the output's strides address an element twice");
     BAS_REQUIRE(elev && azim && scale && e, BAS_E_NULL, "bas_ambi_encode_gains_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(elev) & 7) == 0 && (reinterpret_cast<uintptr_t>(azim) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(gain) & 7) == 0 && (reinterpret_cast<uintptr_t>(scale) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(e) & 3) == 0,
+    BAS_REQUIRE(bas_aligned(elev, 8) && bas_aligned(azim, 8) && bas_aligned(gain, 8) && bas_aligned(scale, 8) &&
+                    bas_aligned(e, 4),
                 BAS_E_ALIGN, "bas_ambi_encode_gains_f32: elev, azim, gain, scale must be 8-byte aligned, e 4-byte");
     ambi_scale_t sc;
     for (int l = 0; l <= AMBI_MAX_ORDER; ++l) sc.v[l] = l <= order ? scale[l] : 0.0;   // (scale is host memory)
@@ -544,30 +536,32 @@ extern "C" int bas_ambi_encode_f32(const float *x, long xs_g, long xs_s, const f
     BAS_REQUIRE(n_groups >= 0 && n_groups <= 65535 && T >= 0 && K > 0, BAS_E_SHAPE,
                 "bas_ambi_encode_f32: need 0 <= n_groups <= 65535, T >= 0 and K > 0");
     BAS_REQUIRE(T < (1L << 30), BAS_E_SHAPE, "bas_ambi_encode_f32: T (%ld) must be below 2^30", T);
-    BAS_REQUIRE(xs_g >= 0 && xs_s >= 0 && es_g >= 0 && es_k >= 0 && bs_g >= 0 && bs_c >= 0 && ys_g >= 0 && ys_c >= 0,
-                BAS_E_SHAPE, "bas_ambi_encode_f32: strides must be >= 0");
-    BAS_REQUIRE(xs_g < (1L << 40) && xs_s < (1L << 40) && es_g < (1L << 40) && es_k < (1L << 40) && bs_g < (1L << 40) &&
-                    bs_c < (1L << 40) && ys_g < (1L << 40) && ys_c < (1L << 40),
-                BAS_E_SHAPE, "bas_ambi_encode_f32: strides must be below 2^40");
+    BAS_REQUIRE(bas_none_negative({xs_g, xs_s, es_g, es_k, bs_g, bs_c, ys_g, ys_c}), BAS_E_SHAPE,
+                "bas_ambi_encode_f32: strides must be >= 0");
+    BAS_REQUIRE(bas_all_below(1L << 40, {xs_g, xs_s, es_g, es_k, bs_g, bs_c, ys_g, ys_c}), BAS_E_SHAPE,
+                "bas_ambi_encode_f32: strides must be below 2^40");
     BAS_REQUIRE(es_k == 0 || es_k >= (long)n_src * C, BAS_E_SHAPE,
                 "bas_ambi_encode_f32: es_k must be 0 (static) or >= n_src C (the banks of two boundaries overlap)");
     if (n_groups == 0 || T == 0) return 0;
     BAS_REQUIRE(bas_layout_one_to_one(n_groups, C, T, ys_g, ys_c), BAS_E_SHAPE,
                 "bas_ambi_encode_f32: the output's strides address an element twice");
     BAS_REQUIRE(x && e && y, BAS_E_NULL, "bas_ambi_encode_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(e) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(base) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
-                BAS_E_ALIGN, "bas_ambi_encode_f32: x, e, base, y must be 4-byte aligned");
-    const long x_n = (n_groups - 1) * xs_g + (n_src - 1) * xs_s + T, y_n = (n_groups - 1) * ys_g + (C - 1) * ys_c + T;
-    BAS_REQUIRE(!ambi_ranges_meet(x, x_n, y, y_n, 4), BAS_E_SHAPE, "bas_ambi_encode_f32: signals and output overlap");
+    BAS_REQUIRE(bas_aligned(x, 4) && bas_aligned(e, 4) && bas_aligned(base, 4) && bas_aligned(y, 4), BAS_E_ALIGN,
+                "bas_ambi_encode_f32: x, e, base, y must be 4-byte aligned");
+    const long x_ext[3] = {n_groups, n_src, T}, x_str[3] = {xs_g, xs_s, 1};
+    const long y_ext[3] = {n_groups, C, T}, y_str[3] = {ys_g, ys_c, 1};
+    const size_t y_bytes = 4 * (size_t)bas_view_extent(3, y_ext, y_str);
+    BAS_REQUIRE(!bas_ranges_meet(x, 4 * (size_t)bas_view_extent(3, x_ext, x_str), y, y_bytes), BAS_E_SHAPE,
+                "bas_ambi_encode_f32: signals and output overlap");
     const long n_k = es_k == 0 ? 1 : (T - 1) / K + 2;
     BAS_REQUIRE(es_k <= (1L << 62) / n_k, BAS_E_SHAPE,
                 "bas_ambi_encode_f32: the banks of the %ld boundaries at es_k = %ld span more than 2^62 elements", n_k, es_k);
-    const long e_n = (n_groups - 1) * es_g + (n_k - 1) * es_k + (long)n_src * C;
-    BAS_REQUIRE(!ambi_ranges_meet(e, e_n, y, y_n, 4), BAS_E_SHAPE, "bas_ambi_encode_f32: banks and output overlap");
+    const long e_ext[3] = {n_groups, n_k, (long)n_src * C}, e_str[3] = {es_g, es_k, 1};
+    BAS_REQUIRE(!bas_ranges_meet(e, 4 * (size_t)bas_view_extent(3, e_ext, e_str), y, y_bytes), BAS_E_SHAPE,
+                "bas_ambi_encode_f32: banks and output overlap");
     if (base && !(base == y && bs_g == ys_g && bs_c == ys_c)) {              // (base == y with y's strides: in place)
-        const long b_n = (n_groups - 1) * bs_g + (C - 1) * bs_c + T;
-        BAS_REQUIRE(!ambi_ranges_meet(base, b_n, y, y_n, 4), BAS_E_SHAPE,
+        const long b_str[3] = {bs_g, bs_c, 1};
+        BAS_REQUIRE(!bas_ranges_meet(base, 4 * (size_t)bas_view_extent(3, y_ext, b_str), y, y_bytes), BAS_E_SHAPE,
                     "bas_ambi_encode_f32: base and output overlap (in place takes base == y with the same strides)");
     }
     const bool is_static = es_k == 0;

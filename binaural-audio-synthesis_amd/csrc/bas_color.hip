@@ -139,8 +139,7 @@ extern "C" int bas_color_rows_f32(const float *x, long x_stride_g, long x_stride
                 "bas_color_rows_f32: c_stride_k must be 0 (static) or >= M (the sets of two boundaries overlap)");
     if ((long)n_groups * n_src == 0 || T == 0) return 0;
     BAS_REQUIRE(x && color && y, BAS_E_NULL, "bas_color_rows_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(color) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(lengths) & 7) == 0,
+    BAS_REQUIRE(bas_aligned(x, 4) && bas_aligned(color, 4) && bas_aligned(y, 4) && bas_aligned(lengths, 8),
                 BAS_E_ALIGN, "bas_color_rows_f32: x, color, y must be 4-byte aligned, lengths 8-byte");
     // a tile touches (tile - 1) / K + 3 coefficient sets at most: whole tiles down to K = 32, shorter ones below
     const int tile = K >= 32 ? CL_TILE : (32 * K) & ~3;

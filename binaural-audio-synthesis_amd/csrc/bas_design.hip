@@ -53,7 +53,6 @@ __global__ __launch_bounds__(DS_THREADS) void bas_color_design_kernel(BasDesignA
     }
 }
 
-static bool ds_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 extern "C" int bas_color_design_f32(const double *logmag, long l_stride_g, long l_stride_s, long l_stride_k,
                                     const double *basis, int n_bands, int M, double logmag_floor, int n_groups, int n_src,
@@ -80,7 +79,7 @@ extern "C" int bas_color_design_f32(const double *logmag, long l_stride_g, long 
                 "%s: output strides (%ld, %ld, %ld, 1) overlap for [%d][%d][%d][%d] (c_stride_k must be >= M)", fn, c_stride_g,
                 c_stride_s, c_stride_k, n_groups, n_src, nb, M);
     BAS_REQUIRE(logmag && basis && color, BAS_E_NULL, "%s: null pointer", fn);
-    BAS_REQUIRE(ds_aligned(logmag, 8) && ds_aligned(basis, 8) && ds_aligned(color, 4), BAS_E_ALIGN,
+    BAS_REQUIRE(bas_aligned(logmag, 8) && bas_aligned(basis, 8) && bas_aligned(color, 4), BAS_E_ALIGN,
                 "%s: logmag and basis must be 8-byte aligned, color 4-byte", fn);
     BasDesignArgs A;
     A.logmag = logmag; A.l_g = l_stride_g; A.l_s = l_stride_s; A.l_k = l_stride_k;

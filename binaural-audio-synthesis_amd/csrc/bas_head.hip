@@ -27,7 +27,6 @@ __global__ __launch_bounds__(HR_THREADS) void bas_head_relative_kernel(
 // the written layout [G][n_src][nb] with strides (sg, ss, 1) addresses no element twice (bas_internal.h)
 static bool hr_one_to_one(int G, int n_src, int nb, long sg, long ss) { return bas_layout_one_to_one(G, n_src, nb, sg, ss); }
 
-static bool hr_aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 extern "C" int bas_head_relative_f64(const double *elev, const double *azim, long in_stride_g, long in_stride_s,
                                      const double *head, long head_stride_g, long head_stride_c, int n_groups, int n_src,
@@ -46,8 +45,8 @@ extern "C" int bas_head_relative_f64(const double *elev, const double *azim, lon
     BAS_REQUIRE(((elev_out != elev && azim_out != azim) || (out_stride_g == in_stride_g && out_stride_s == in_stride_s)),
                 BAS_E_SHAPE, "bas_head_relative_f64: in place needs the input strides (%ld, %ld) on the output (%ld, %ld)",
                 in_stride_g, in_stride_s, out_stride_g, out_stride_s);
-    BAS_REQUIRE(hr_aligned8(elev) && hr_aligned8(azim) && hr_aligned8(head) && hr_aligned8(elev_out) &&
-                hr_aligned8(azim_out), BAS_E_ALIGN, "bas_head_relative_f64: float64 arrays must be 8-byte aligned");
+    BAS_REQUIRE(bas_aligned(elev, 8) && bas_aligned(azim, 8) && bas_aligned(head, 8) && bas_aligned(elev_out, 8) &&
+                bas_aligned(azim_out, 8), BAS_E_ALIGN, "bas_head_relative_f64: float64 arrays must be 8-byte aligned");
     const long n_items = (long)n_groups * n_src * nb;
     const int blocks = bas_grid_for(n_items, 8 * bas_device_cus());
     hipLaunchKernelGGL(bas_head_relative_kernel, dim3(blocks), dim3(HR_THREADS), 0, bas_stream(stream), elev, azim,

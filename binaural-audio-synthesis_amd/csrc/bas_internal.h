@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include "../../include/bas.h"
+#include "bas_views.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -76,46 +77,6 @@ static inline bool bas_deal_units(long units, long slots, int n_src, int tile, i
     *n_wg = (int)((units + *units_per_wg - 1) / *units_per_wg);
     *parts_per_wg = (int)(((long)*units_per_wg + n_src - 2) / n_src + 1);
     *slab_bytes = (size_t)*n_wg * *parts_per_wg * 2 * tile * sizeof(float);
-    return true;
-}
-
-// A written layout [G][rows][nb] with element strides (sg, ss, 1), all >= 0, addresses no element twice.  Exact: two
-// elements share an address exactly when some (dr, dg) != (0, 0) with |dr| < rows, |dg| < G has |dr ss + dg sg| < nb.
-// The nested layouts every renderer uses pass the first test (every dimension of more than one element, in ascending stride
-// order, steps over the whole extent of the ones before it); the others - interleaved, non-nested - take the search: for
-// every dg the dr that brings dr ss + dg sg nearest to zero, min(G, rows) steps in 128-bit arithmetic.
-static inline bool bas_layout_one_to_one(long G, long rows, long nb, long sg, long ss) {
-    if (G <= 0 || rows <= 0 || nb <= 0 || sg < 0 || ss < 0) return false;
-    {
-        long st[3] = {1, ss, sg}, ex[3] = {nb, rows, G};
-        if (st[1] > st[2]) {
-            const long t = st[1], e = ex[1];
-            st[1] = st[2]; ex[1] = ex[2]; st[2] = t; ex[2] = e;
-        }
-        long span = 1;                                   // elements covered by the dimensions so far, stride 1 first
-        bool nested = true;
-        for (int k = 0; k < 3 && nested; ++k) {
-            if (ex[k] == 1) continue;
-            if (st[k] < span || __builtin_mul_overflow(st[k], ex[k], &span)) nested = false;
-        }
-        if (nested) return true;
-    }
-    if (G > rows) {                                      // the outer loop over the shorter dimension
-        const long t = G, u = sg;
-        G = rows; sg = ss; rows = t; ss = u;
-    }
-    if (rows > 1 && ss < nb) return false;               // dg = 0
-    for (long dg = 1; dg < G; ++dg) {
-        const __int128 v = (__int128)dg * sg;            // dr = -k: v - k ss, k = 0 .. rows - 1
-        if (ss == 0) {
-            if (v < nb) return false;
-            continue;
-        }
-        __int128 k = v / ss;
-        if (k > rows - 1) k = rows - 1;
-        if (v - k * ss < nb) return false;               // from above (>= 0)
-        if (k + 1 <= rows - 1 && (k + 1) * ss - v < nb) return false;   // from below
-    }
     return true;
 }
 

@@ -251,33 +251,6 @@ __global__ __launch_bounds__(LIM_THREADS) void bas_limit_carry_kernel(const floa
 
 static inline bool lim_params_ok(int A, int Hd) { return A >= 0 && A <= LIM_MAX_A && Hd >= 0 && Hd <= LIM_MAX_HD; }
 
-// A written layout of (G, T, 2) elements with strides (sg, st, se) >= 0 addresses no element twice when every dimension
-// of more than one element, in ascending stride order, steps over the whole extent of the ones before it.
-static inline bool lim_layout_nested(long G, long T, long sg, long st, long se) {
-    long s[3] = {se, st, sg}, e[3] = {2, T, G};
-    for (int a = 0; a < 3; ++a)
-        for (int b = a + 1; b < 3; ++b)
-            if (s[b] < s[a]) {
-                const long ts = s[a], te = e[a];
-                s[a] = s[b]; e[a] = e[b]; s[b] = ts; e[b] = te;
-            }
-    long span = 1;
-    for (int k = 0; k < 3; ++k) {
-        if (e[k] == 1) continue;
-        if (s[k] < span) return false;
-        span = s[k] * (e[k] - 1) + span;
-    }
-    return true;
-}
-
-// floats from the first to one past the last element of a (G, T, 2) view
-static inline long lim_extent(long G, long T, long sg, long st, long se) { return (G - 1) * sg + (T - 1) * st + se + 1; }
-
-static inline bool lim_ranges_meet(const float *a, long na, const float *b, long nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uintptr_t)nb * 4 && b0 < a0 + (uintptr_t)na * 4;
-}
-
 extern "C" size_t bas_limit_state_floats(int lookahead, int hold) {
     if (!lim_params_ok(lookahead, hold)) return 0;
     return (size_t)LIM_STATE_HEAD + 2 * (size_t)lim_history(lookahead, hold);
@@ -299,11 +272,11 @@ extern "C" int bas_limit_f32(const float *y, long y_stride_g, long y_stride_t, l
                 "bas_limit_f32: T_in and T_out must be in 0..2^30 - 1");
     BAS_REQUIRE(T_in == T_out || (state && T_in == 0), BAS_E_SHAPE,
                 "bas_limit_f32: T_in (%ld) must equal T_out (%ld), or be 0 with a state (the stream's end)", T_in, T_out);
-    BAS_REQUIRE(y_stride_g >= 0 && y_stride_t >= 0 && y_stride_e >= 0 && out_stride_g >= 0 && out_stride_t >= 0 &&
-                    out_stride_e >= 0 && state_stride >= 0,
+    BAS_REQUIRE(bas_none_negative({y_stride_g, y_stride_t, y_stride_e, out_stride_g, out_stride_t, out_stride_e,
+                                   state_stride}),
                 BAS_E_SHAPE, "bas_limit_f32: strides must be >= 0");
-    BAS_REQUIRE(y_stride_g < (1L << 40) && y_stride_t < (1L << 31) && y_stride_e < (1L << 40) && out_stride_g < (1L << 40) &&
-                    out_stride_t < (1L << 31) && out_stride_e < (1L << 40) && state_stride < (1L << 40),
+    BAS_REQUIRE(bas_all_below(1L << 40, {y_stride_g, y_stride_e, out_stride_g, out_stride_e, state_stride}) &&
+                    bas_all_below(1L << 31, {y_stride_t, out_stride_t}),
                 BAS_E_SHAPE, "bas_limit_f32: strides must be below 2^40 (session, ear) and 2^31 (sample)");
     const int H = lim_history(lookahead, hold);
     BAS_REQUIRE(!state || (state_stride >= LIM_STATE_HEAD + 2L * H && (state_stride & 3) == 0), BAS_E_SHAPE,
@@ -311,16 +284,18 @@ extern "C" int bas_limit_f32(const float *y, long y_stride_g, long y_stride_t, l
                 state_stride, LIM_STATE_HEAD + 2L * H);
     if (n_sessions == 0 || T_out == 0) return 0;
     BAS_REQUIRE(out && (y || T_in == 0), BAS_E_NULL, "bas_limit_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(reduction) & 3) == 0 && (reinterpret_cast<uintptr_t>(peak) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(state) & 15) == 0,
+    BAS_REQUIRE(bas_aligned(y, 4) && bas_aligned(out, 4) && bas_aligned(reduction, 4) && bas_aligned(peak, 4) &&
+                    bas_aligned(state, 16),
                 BAS_E_ALIGN, "bas_limit_f32: y, out, reduction, peak must be 4-byte aligned, state 16-byte");
-    BAS_REQUIRE(lim_layout_nested(n_sessions, T_out, out_stride_g, out_stride_t, out_stride_e), BAS_E_SHAPE,
+    const long in_extent[3] = {n_sessions, T_in, 2}, in_stride[3] = {y_stride_g, y_stride_t, y_stride_e};
+    const long out_extent[3] = {n_sessions, T_out, 2}, out_stride[3] = {out_stride_g, out_stride_t, out_stride_e};
+    BAS_REQUIRE(bas_layout_nested(3, out_extent, out_stride), BAS_E_SHAPE,
                 "bas_limit_f32: the output's strides address an element twice");
-    const long out_n = lim_extent(n_sessions, T_out, out_stride_g, out_stride_t, out_stride_e);
-    BAS_REQUIRE(T_in == 0 || !lim_ranges_meet(y, lim_extent(n_sessions, T_in, y_stride_g, y_stride_t, y_stride_e), out, out_n),
+    const size_t out_bytes = 4 * (size_t)bas_view_extent(3, out_extent, out_stride);
+    BAS_REQUIRE(T_in == 0 || !bas_ranges_meet(y, 4 * (size_t)bas_view_extent(3, in_extent, in_stride), out, out_bytes),
                 BAS_E_SHAPE, "bas_limit_f32: input and output overlap (the limiter does not run in place)");
-    BAS_REQUIRE(!state || !lim_ranges_meet(state, (n_sessions - 1) * state_stride + LIM_STATE_HEAD + 2L * H, out, out_n),
+    const long state_extent[2] = {n_sessions, LIM_STATE_HEAD + 2L * H}, state_strides[2] = {state_stride, 1};
+    BAS_REQUIRE(!bas_ranges_meet(state, 4 * (size_t)bas_view_extent(2, state_extent, state_strides), out, out_bytes),
                 BAS_E_SHAPE, "bas_limit_f32: state and output overlap");
     const hipStream_t st = bas_stream(stream);
     const unsigned tiles = (unsigned)((T_out + LIM_TILE - 1) / LIM_TILE);

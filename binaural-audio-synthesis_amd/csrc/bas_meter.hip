@@ -315,12 +315,6 @@ __global__ __launch_bounds__(64) void bas_meter_chain_kernel(MeterIo io, MeterPa
     }
 }
 
-static inline bool met_ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
-    if (!a || !b || na == 0 || nb == 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 extern "C" size_t bas_meter_state_doubles(void) { return MET_STATE_WORDS; }
 
 extern "C" size_t bas_meter_workspace_bytes(int n_sessions, long T_in, int hop) {
@@ -342,11 +336,10 @@ extern "C" int bas_meter_f32(const float *y, long y_stride_g, long y_stride_t, l
     BAS_REQUIRE(T_in >= 0 && T_in < (1L << 30), BAS_E_SHAPE, "bas_meter_f32: T_in (%ld) must be in 0..2^30 - 1", T_in);
     BAS_REQUIRE(max_hops >= 0 && max_hops < (1L << 31), BAS_E_SHAPE, "bas_meter_f32: max_hops (%ld) must be in 0..2^31 - 1",
                 max_hops);
-    BAS_REQUIRE(y_stride_g >= 0 && y_stride_t >= 0 && y_stride_e >= 0 && e_stride_g >= 0 && e_stride_e >= 0 &&
-                    state_stride >= 0,
-                BAS_E_SHAPE, "bas_meter_f32: strides must be >= 0");
-    BAS_REQUIRE(y_stride_g < (1L << 40) && y_stride_t < (1L << 31) && y_stride_e < (1L << 40) && e_stride_g < (1L << 40) &&
-                    e_stride_e < (1L << 40) && state_stride < (1L << 40),
+    BAS_REQUIRE(bas_none_negative({y_stride_g, y_stride_t, y_stride_e, e_stride_g, e_stride_e, state_stride}), BAS_E_SHAPE,
+                "bas_meter_f32: strides must be >= 0");
+    BAS_REQUIRE(bas_all_below(1L << 40, {y_stride_g, y_stride_e, e_stride_g, e_stride_e, state_stride}) &&
+                    y_stride_t < (1L << 31),
                 BAS_E_SHAPE, "bas_meter_f32: strides must be below 2^40 (session, ear) and 2^31 (sample)");
     BAS_REQUIRE(!state || (state_stride >= MET_STATE_WORDS && (state_stride & 1) == 0), BAS_E_SHAPE,
                 "bas_meter_f32: state_stride (%ld) must be even and >= bas_meter_state_doubles (%d)", state_stride,
@@ -368,20 +361,22 @@ extern "C" int bas_meter_f32(const float *y, long y_stride_g, long y_stride_t, l
     BAS_REQUIRE(!chained || ws, BAS_E_NULL, "bas_meter_f32: null workspace for a call of more than hop + 1 samples");
     BAS_REQUIRE(ws_bytes >= ws_need, BAS_E_SHAPE, "bas_meter_f32: workspace of %zu bytes, bas_meter_workspace_bytes is %zu",
                 ws_bytes, ws_need);
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(true_peak) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(energy) & 7) == 0 && (reinterpret_cast<uintptr_t>(state) & 15) == 0 &&
-                    (!chained || (reinterpret_cast<uintptr_t>(ws) & 15) == 0),
+    BAS_REQUIRE(bas_aligned(y, 4) && bas_aligned(true_peak, 4) && bas_aligned(energy, 8) && bas_aligned(state, 16) &&
+                    (!chained || bas_aligned(ws, 16)),
                 BAS_E_ALIGN, "bas_meter_f32: y, true_peak must be 4-byte aligned, energy 8-byte, state and ws 16-byte");
     {
-        const size_t y_n = T_in > 0 ? 4 * (size_t)((n_sessions - 1) * y_stride_g + (T_in - 1) * y_stride_t + y_stride_e + 1) : 0;
-        const size_t e_n = max_hops > 0 ? 8 * (size_t)((n_sessions - 1) * e_stride_g + e_stride_e + max_hops) : 0;
-        const size_t s_n = state ? 8 * (size_t)((n_sessions - 1) * state_stride + MET_STATE_WORDS) : 0;
+        const long y_ext[3] = {n_sessions, T_in, 2}, y_str[3] = {y_stride_g, y_stride_t, y_stride_e};
+        const long e_ext[3] = {n_sessions, 2, max_hops}, e_str[3] = {e_stride_g, e_stride_e, 1};
+        const long s_ext[2] = {n_sessions, MET_STATE_WORDS}, s_str[2] = {state_stride, 1};
+        const size_t y_n = T_in > 0 ? 4 * (size_t)bas_view_extent(3, y_ext, y_str) : 0;
+        const size_t e_n = max_hops > 0 ? 8 * (size_t)bas_view_extent(3, e_ext, e_str) : 0;
+        const size_t s_n = state ? 8 * (size_t)bas_view_extent(2, s_ext, s_str) : 0;
         const size_t p_n = true_peak ? 8 * (size_t)n_sessions : 0;
         const void *buf[5] = {y, energy, state, true_peak, chained ? ws : nullptr};
         const size_t len[5] = {y_n, e_n, s_n, p_n, ws_need};
         for (int i = 0; i < 5; ++i)
             for (int j = i + 1; j < 5; ++j)
-                BAS_REQUIRE(!met_ranges_meet(buf[i], len[i], buf[j], len[j]), BAS_E_SHAPE,
+                BAS_REQUIRE(!bas_ranges_meet(buf[i], len[i], buf[j], len[j]), BAS_E_SHAPE,
                             "bas_meter_f32: input, energy buffer, state, true_peak and workspace overlap");
     }
     MeterParams F;

@@ -85,8 +85,7 @@ extern "C" int bas_bus_mix_f32(const float *x, long x_stride_g, long x_stride_s,
     BAS_REQUIRE(n_groups <= 1 || bus_stride >= T, BAS_E_SHAPE, "bas_bus_mix_f32: bus_stride (%ld) must be >= T", bus_stride);
     if (n_groups == 0 || T == 0) return 0;
     BAS_REQUIRE(bus && (n_src == 0 || (x && send)), BAS_E_NULL, "bas_bus_mix_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(bus) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(send) & 7) == 0,
+    BAS_REQUIRE(bas_aligned(x, 4) && bas_aligned(bus, 4) && bas_aligned(send, 8),
                 BAS_E_ALIGN, "bas_bus_mix_f32: x and bus must be 4-byte aligned, send 8-byte");
     const long quads = (T + 3) >> 2;
     const long blocks = (quads + BM_THREADS - 1) / BM_THREADS;
@@ -148,7 +147,7 @@ extern "C" int bas_long_fir_tail_f32(const float *h, long h_stride, int Lr, int 
     BAS_REQUIRE(Lr >= 1 && Lr <= RV_MAX_LR, BAS_E_SHAPE, "bas_long_fir_tail_f32: Lr (%d) must be in 1..2^17", Lr);
     BAS_REQUIRE(h_stride >= Lr, BAS_E_SHAPE, "bas_long_fir_tail_f32: h_stride (%ld) must be >= Lr", h_stride);
     BAS_REQUIRE(h && tail, BAS_E_NULL, "bas_long_fir_tail_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(h) & 3) == 0 && (reinterpret_cast<uintptr_t>(tail) & 15) == 0, BAS_E_ALIGN,
+    BAS_REQUIRE(bas_aligned(h, 4) && bas_aligned(tail, 16), BAS_E_ALIGN,
                 "bas_long_fir_tail_f32: h must be 4-byte aligned, tail 16-byte");
     hipLaunchKernelGGL(bas_long_fir_tail_kernel, dim3((unsigned)rv_partitions(Lr, Np)), dim3(Np), 0, bas_stream(stream), h,
                        h_stride, Lr, Np, tail);
@@ -336,9 +335,8 @@ extern "C" int bas_long_fir_f32(const float *bus, long bus_stride, long Hb, long
                 "out_stride_e + T_out)");
     if (n_bus == 0 || T_out == 0) return 0;
     BAS_REQUIRE(tail && out && ws && (bus || Hb + T_bus == 0), BAS_E_NULL, "bas_long_fir_f32: null pointer");
-    BAS_REQUIRE((reinterpret_cast<uintptr_t>(bus) & 3) == 0 && (reinterpret_cast<uintptr_t>(y_in) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (reinterpret_cast<uintptr_t>(peak) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(tail) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
+    BAS_REQUIRE(bas_aligned(bus, 4) && bas_aligned(y_in, 4) && bas_aligned(out, 4) && bas_aligned(peak, 4) &&
+                    bas_aligned(tail, 16) && bas_aligned(ws, 16),
                 BAS_E_ALIGN, "bas_long_fir_f32: bus, y_in, out, peak must be 4-byte aligned, tail and ws 16-byte");
     const RvPlan pl = rv_plan(n_bus, T_out, Lr, Np);
     BAS_REQUIRE(ws_bytes >= pl.x_bytes + pl.y_bytes, BAS_E_WORKSPACE,

@@ -146,7 +146,6 @@ __global__ __launch_bounds__(SC_THREADS) void bas_scene_params_kernel(typename S
 // the written layout [G][rows][nb] with strides (sg, ss, 1) addresses no element twice (bas_internal.h)
 static bool sc_one_to_one(long G, long rows, long nb, long sg, long ss) { return bas_layout_one_to_one(G, rows, nb, sg, ss); }
 
-static bool sc_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // what bas_scene_params_bands_f64 adds to the argument list
 struct BasSceneBands {
@@ -196,9 +195,10 @@ static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long 
     BAS_REQUIRE(elev != azim && (!gain || (gain != elev && gain != azim)) &&
                 (!delay || (delay != elev && delay != azim && delay != gain)), BAS_E_SHAPE,
                 "%s: two outputs are one buffer", fn);
-    BAS_REQUIRE(sc_aligned(pos, 8) && sc_aligned(pos_prev, 8) && sc_aligned(lpos, 8) && sc_aligned(head, 8) && sc_aligned(src_gain, 8) &&
-                sc_aligned(room_size, 8) && sc_aligned(img_gain, 8) && sc_aligned(images, 4) && sc_aligned(elev, 8) &&
-                sc_aligned(azim, 8) && sc_aligned(gain, 8) && sc_aligned(delay, 8), BAS_E_ALIGN,
+    BAS_REQUIRE(bas_aligned(pos, 8) && bas_aligned(pos_prev, 8) && bas_aligned(lpos, 8) && bas_aligned(head, 8) &&
+                bas_aligned(src_gain, 8) && bas_aligned(room_size, 8) && bas_aligned(img_gain, 8) &&
+                bas_aligned(images, 4) && bas_aligned(elev, 8) && bas_aligned(azim, 8) && bas_aligned(gain, 8) &&
+                bas_aligned(delay, 8), BAS_E_ALIGN,
                 "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
     BasSceneOccArgs AO;
     memset(&AO, 0, sizeof AO);
@@ -223,8 +223,8 @@ static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long 
         BAS_REQUIRE(B->logmag, BAS_E_NULL, "%s: null pointer", fn);
         BAS_REQUIRE((void *)B->logmag != elev && (void *)B->logmag != azim && (void *)B->logmag != gain &&
                     (void *)B->logmag != delay, BAS_E_SHAPE, "%s: two outputs are one buffer", fn);
-        BAS_REQUIRE(sc_aligned(B->orient, 8) && sc_aligned(B->pattern, 8) && sc_aligned(B->air, 8) &&
-                    sc_aligned(B->img_logmag, 8) && sc_aligned(B->logmag, 8), BAS_E_ALIGN,
+        BAS_REQUIRE(bas_aligned(B->orient, 8) && bas_aligned(B->pattern, 8) && bas_aligned(B->air, 8) &&
+                    bas_aligned(B->img_logmag, 8) && bas_aligned(B->logmag, 8), BAS_E_ALIGN,
                     "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
         A.orient = B->orient; A.o_g = B->o_g; A.o_s = B->o_s; A.o_c = B->o_c;
         A.pattern = B->pattern; A.pt_s = B->pt_s; A.air = B->air; A.img_logmag = B->img_logmag;
@@ -236,7 +236,8 @@ static int sc_launch(const char *fn, const double *pos, long pos_stride_g, long 
             BAS_REQUIRE(B->t_s == 0 || B->t_s >= B->n_bands, BAS_E_SHAPE,
                         "%s: the transmission's screen stride (%ld) must be 0 (shared) or >= n_bands", fn, B->t_s);
             BAS_REQUIRE(B->screens && B->fresnel, BAS_E_NULL, "%s: null pointer (screens, fresnel)", fn);
-            BAS_REQUIRE(sc_aligned(B->screens, 8) && sc_aligned(B->transmission, 8) && sc_aligned(B->fresnel, 8), BAS_E_ALIGN,
+            BAS_REQUIRE(bas_aligned(B->screens, 8) && bas_aligned(B->transmission, 8) && bas_aligned(B->fresnel, 8),
+                        BAS_E_ALIGN,
                         "%s: float64 arrays must be 8-byte aligned (images: 4-byte)", fn);
             AO.scr.screens = B->screens; AO.scr.transmission = B->transmission; AO.scr.fresnel = B->fresnel;
             AO.scr.t_s = B->t_s; AO.scr.n_screens = B->n_screens; AO.scr.n_bands = B->n_bands;

@@ -30,11 +30,12 @@ finite; the bit-for-bit claims hold for |y| <= 2^20 c.
 import numpy as np
 
 from . import _hip
+from ._stage import (MAX_SESSIONS, check_n_sessions, overlap, session_indices, session_runs, stereo_device,
+                     stereo_host)
 
 TILE = 1024                    # output samples per workgroup (LIM_TILE of csrc/bas_limit.h)
 MAX_LOOKAHEAD = 1024           # BAS_LIMIT_MAX_LOOKAHEAD
 MAX_HOLD = 4096                # BAS_LIMIT_MAX_HOLD
-MAX_SESSIONS = 65535
 
 
 # ---- parameters -----------------------------------------------------------------------------------------------------
@@ -61,17 +62,6 @@ def check_params(ceiling, lookahead, hold):
 def history(lookahead, hold):
     """Input samples in front of an output that it depends on, and that a stream carries: 2 A + Hd."""
     return 2 * int(lookahead) + int(hold)
-
-
-def _stereo_host(y):
-    a = np.asarray(y)
-    if a.ndim not in (2, 3) or a.shape[-1] != 2:
-        raise ValueError(f"y must be [n, 2] or [G, n, 2], got {a.shape}")
-    with np.errstate(over="ignore"):                                       # (a value beyond binary32 becomes inf: refused)
-        y32 = np.ascontiguousarray(a, dtype=np.float32)
-    if not np.isfinite(y32).all():
-        raise ValueError("y must be finite")
-    return y32
 
 
 # ---- the numpy forms ------------------------------------------------------------------------------------------------
@@ -101,7 +91,7 @@ def limit_f64(y, ceiling, lookahead, hold, return_gain=False):
     """The definition: y float32 [n, 2] or [G, n, 2] -> float64 of the same shape (with return_gain also g [.., n]);
     steps 2 to 6 in binary64 on the float32 inputs, the ceiling rounded to binary32 first."""
     c32, A, Hd = check_params(ceiling, lookahead, hold)
-    y32 = _stereo_host(y)
+    y32 = stereo_host(y)
     c = float(c32)
     yd = y32.astype(np.float64)
     m = np.abs(yd).max(axis=-1)
@@ -118,7 +108,7 @@ def limit_f32_ref(y, ceiling, lookahead, hold, return_gain=False):
     one binary64 division by A + 1, one rounding to binary32; one float32 multiplication, then the clamp.  float32 out
     (with return_gain also g, float32 [.., n]).  bas_limit_f32 gives these bits."""
     c32, A, Hd = check_params(ceiling, lookahead, hold)
-    y32 = _stereo_host(y)
+    y32 = stereo_host(y)
     m = np.abs(y32).max(axis=-1)
     r = np.ones_like(m)
     np.divide(c32, m, out=r, where=m > c32)
@@ -131,47 +121,16 @@ def limit_f32_ref(y, ceiling, lookahead, hold, return_gain=False):
 
 
 # ---- the device form ------------------------------------------------------------------------------------------------
-def _span(t):
-    """[first, last + 1) byte addresses of a tensor's elements."""
-    lo = t.data_ptr()
-    return lo, lo + 4 * (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1)
-
-
-def _check_stereo_device(t, name, G=None, device=None):
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-        raise ValueError(f"{name} must be a float32 device tensor")
-    if t.dim() not in (2, 3) or t.shape[-1] != 2:
-        raise ValueError(f"{name} must be [n, 2] or [G, n, 2], got {tuple(t.shape)}")
-    t3 = t if t.dim() == 3 else t.unsqueeze(0)
-    if G is not None and t3.shape[0] != G:
-        raise ValueError(f"{name} must hold {G} session(s), got {tuple(t.shape)}")
-    if not 1 <= t3.shape[0] <= MAX_SESSIONS:
-        raise ValueError(f"{name}: 1..{MAX_SESSIONS} signals in one call")
-    if t3.shape[1] >= 1 << 30:
-        raise ValueError(f"{name}: fewer than 2^30 samples in one call")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name} is on {t.device}, not on {device}")
-    return t3
-
-
 def _launch(y3, o3, T_in, c32, A, Hd, state, reduction, peak):
     """One bas_limit_f32 call.  y3 None: the stream's end (T_in == 0)."""
-    if y3 is not None and o3.numel() and y3.numel():
-        (a0, a1), (b0, b1) = _span(y3), _span(o3)
-        if a0 < b1 and b0 < a1:
-            raise ValueError("input and output overlap: the limiter does not run in place")
+    if y3 is not None and o3.numel() and y3.numel() and overlap(y3, o3):
+        raise ValueError("input and output overlap: the limiter does not run in place")
     dev = o3.device
     ys = (0, 0, 0) if y3 is None else y3.stride()
-    try:
-        with _hip.on_device(dev):
-            _hip.call("bas_limit_f32", _hip.ptr(y3), *ys, _hip.ptr(o3), *o3.stride(), int(o3.shape[0]), int(T_in),
-                      int(o3.shape[1]), float(c32), A, Hd, _hip.ptr(state), 0 if state is None else state.stride(0),
-                      _hip.ptr(reduction), _hip.ptr(peak), _hip.current_stream(dev))
-    except _hip.BasError as e:
-        if e.code == -2:                                               # BAS_E_SHAPE: an output that addresses an element twice
-            raise ValueError(str(e)) from None
-        raise
+    with _hip.shape_errors(), _hip.on_device(dev):                         # (an output that addresses an element twice)
+        _hip.call("bas_limit_f32", _hip.ptr(y3), *ys, _hip.ptr(o3), *o3.stride(), int(o3.shape[0]), int(T_in),
+                  int(o3.shape[1]), float(c32), A, Hd, _hip.ptr(state), 0 if state is None else state.stride(0),
+                  _hip.ptr(reduction), _hip.ptr(peak), _hip.current_stream(dev))
     return o3
 
 
@@ -185,16 +144,16 @@ def limit(y, ceiling=0.98, lookahead=240, hold=960, out=None, return_meters=Fals
     c32, A, Hd = check_params(ceiling, lookahead, hold)
     host = not isinstance(y, torch.Tensor)
     if host:
-        y = torch.from_numpy(_stereo_host(y)).to(_hip.require_gpu())
+        y = torch.from_numpy(stereo_host(y)).to(_hip.require_gpu())
     elif not y.is_cuda:
         raise ValueError("y must be a device tensor (or a host array)")
-    y3 = _check_stereo_device(y, "y")
+    y3 = stereo_device(y, "y")
     dev = y.device
     if out is None:
         out = torch.empty(tuple(y.shape), dtype=torch.float32, device=dev)
     elif tuple(out.shape) != tuple(y.shape):
         raise ValueError(f"out must have y's shape {tuple(y.shape)}, got {tuple(out.shape)}")
-    o3 = _check_stereo_device(out, "out", device=dev)
+    o3 = stereo_device(out, "out", device=dev)
     G = int(y3.shape[0])
     reduction = peaks = None
     if return_meters:
@@ -230,9 +189,7 @@ class StreamLimiter:
     def __init__(self, n_sessions=1, ceiling=0.98, lookahead=240, hold=960, device=None):
         import torch
         self.ceiling, self.lookahead, self.hold = check_params(ceiling, lookahead, hold)
-        if isinstance(n_sessions, bool) or not isinstance(n_sessions, (int, np.integer)) or not 1 <= n_sessions <= MAX_SESSIONS:
-            raise ValueError(f"n_sessions must be an integer in 1..{MAX_SESSIONS}")
-        self.G = int(n_sessions)
+        self.G = check_n_sessions(n_sessions)
         self.history = history(self.lookahead, self.hold)
         self.device = _hip.require_gpu(device)
         floats = _hip.lib().bas_limit_state_floats(self.lookahead, self.hold)
@@ -265,42 +222,22 @@ class StreamLimiter:
         """y_block [B, 2] (n_sessions == 1) or [G, B, 2], a float32 device tensor of any strides, B >= 1 -> the limited
         samples of times [t0 - A, t0 + B - A), in a fresh tensor or in out= (y_block's shape, not overlapping it)."""
         import torch
-        y3 = _check_stereo_device(y_block, "y_block", self.G, self.device)
+        y3 = stereo_device(y_block, "y_block", self.G, self.device)
         if y3.shape[1] < 1:
             raise ValueError("a block holds at least one sample")
         if out is None:
             out = torch.empty(tuple(y_block.shape), dtype=torch.float32, device=self.device)
         elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(y_block.shape):
             raise ValueError(f"out must have y_block's shape {tuple(y_block.shape)}")
-        o3 = _check_stereo_device(out, "out", self.G, self.device)
+        o3 = stereo_device(out, "out", self.G, self.device)
         _launch(y3, o3, y3.shape[1], self.ceiling, self.lookahead, self.hold, self._state, self._reduction, self._peaks)
         return out
 
     # ---- per-session state --------------------------------------------------------------------------------------------
-    def _sessions(self, sessions):
-        if sessions is None:
-            return list(range(self.G))
-        idx = sorted({int(g) for g in np.asarray(sessions, dtype=np.int64).reshape(-1)})
-        if idx and not (0 <= idx[0] and idx[-1] < self.G):
-            raise ValueError(f"session index out of range [0, {self.G})")
-        if len(idx) != np.asarray(sessions).size:
-            raise ValueError("sessions must not repeat")
-        return idx
-
-    @staticmethod
-    def _runs(idx):
-        runs = []
-        for g in idx:
-            if runs and runs[-1][1] == g:
-                runs[-1][1] = g + 1
-            else:
-                runs.append([g, g + 1])
-        return runs
-
     def reset(self, sessions=None):
         """Drop the streams of these slots (None: all): history zeroed, meters back to 1 and 0 (slice ops on the current
         stream).  The other sessions are not touched."""
-        for g0, g1 in self._runs(self._sessions(sessions)):
+        for g0, g1 in session_runs(session_indices(sessions, self.G)):
             self._state[g0:g1].zero_()
             self._reduction[g0:g1].fill_(1.0)
             self._peaks[g0:g1].zero_()
@@ -311,11 +248,11 @@ class StreamLimiter:
         in ascending session order; with return_meters=True also (reduction, peaks), float32 [len(sessions)] on the host:
         the finished streams' final meters."""
         import torch
-        idx = self._sessions(sessions)
+        idx = session_indices(sessions, self.G)
         A = self.lookahead
         tails = torch.zeros((len(idx), A, 2), dtype=torch.float32, device=self.device)
         pos = 0
-        for g0, g1 in self._runs(idx):
+        for g0, g1 in session_runs(idx):
             if A:
                 _launch(None, tails[pos:pos + g1 - g0], 0, self.ceiling, A, self.hold, self._state[g0:g1],
                         self._reduction[g0:g1], self._peaks[g0:g1])

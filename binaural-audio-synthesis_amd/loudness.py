@@ -29,9 +29,10 @@ LIMITER (the oversampled peak is not fed into limiter.py), command-line flags.
 import numpy as np
 
 from . import _hip
+from ._stage import (MAX_SESSIONS, check_n_sessions, session_indices, session_runs, span, stereo_device,
+                     stereo_host)
 
 FS_MIN, FS_MAX = 8000, 192000
-MAX_SESSIONS = 65535
 TAPS = 12                      # MET_TAPS of csrc/bas_meter.h: j = -5 .. 6
 CONTEXT = TAPS - 1             # input samples a stream carries for the true peak
 ABSOLUTE_GATE = -70.0
@@ -46,17 +47,6 @@ def check_fs(fs):
     if not np.isfinite(fs) or int(fs) != fs or not FS_MIN <= int(fs) <= FS_MAX or int(fs) % 10:
         raise ValueError(f"fs must be a multiple of 10 in {FS_MIN}..{FS_MAX}, got {fs}")
     return int(fs)
-
-
-def _stereo_host(y):
-    a = np.asarray(y)
-    if a.ndim not in (2, 3) or a.shape[-1] != 2:
-        raise ValueError(f"y must be [n, 2] or [G, n, 2], got {a.shape}")
-    with np.errstate(over="ignore"):
-        y32 = np.ascontiguousarray(a, dtype=np.float32)
-    if not np.isfinite(y32).all():
-        raise ValueError("y must be finite")
-    return y32
 
 
 # ---- the definitions ------------------------------------------------------------------------------------------------
@@ -101,7 +91,7 @@ def _lfilter(b, a, x):
 def kweighted_f64(y, fs):
     """The K-weighted signal: y float32 [n, 2] or [G, n, 2] -> float64 of the same shape."""
     (b1, a1), (b2, a2) = kweighting(fs)
-    x = np.moveaxis(_stereo_host(y).astype(np.float64), -2, -1)
+    x = np.moveaxis(stereo_host(y).astype(np.float64), -2, -1)
     return np.moveaxis(_lfilter(b2, a2, _lfilter(b1, a1, x)), -1, -2)
 
 
@@ -179,7 +169,7 @@ def true_peak_taps():
 def true_peak_ref(y):
     """The device arithmetic of the true peak: float32 [2] or [G, 2], the maximum per ear over the samples and the three
     interpolated phases at every position whose window touches the signal.  bas_meter_f32 gives these bits."""
-    y32 = _stereo_host(y)
+    y32 = stereo_host(y)
     n = y32.shape[-2]
     taps = true_peak_taps().astype(np.float64)
     lead = y32.shape[:-2]
@@ -224,50 +214,22 @@ def _taps_host():
     return _TAPS_HOST
 
 
-def _span(t):
-    lo = t.data_ptr()
-    return lo, lo + t.element_size() * (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1)
-
-
-def _check_stereo_device(t, name, G=None, device=None):
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-        raise ValueError(f"{name} must be a float32 device tensor")
-    if t.dim() not in (2, 3) or t.shape[-1] != 2:
-        raise ValueError(f"{name} must be [n, 2] or [G, n, 2], got {tuple(t.shape)}")
-    t3 = t if t.dim() == 3 else t.unsqueeze(0)
-    if G is not None and t3.shape[0] != G:
-        raise ValueError(f"{name} must hold {G} session(s), got {tuple(t.shape)}")
-    if not 1 <= t3.shape[0] <= MAX_SESSIONS:
-        raise ValueError(f"{name}: 1..{MAX_SESSIONS} signals in one call")
-    if t3.shape[1] >= 1 << 30:
-        raise ValueError(f"{name}: fewer than 2^30 samples in one call")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name} is on {t.device}, not on {device}")
-    return t3
-
-
 def _launch(y3, G, T_in, fs, energy, n_before, state, true_peak, ws):
     """One bas_meter_f32 call.  y3 None: the stream's end (T_in == 0)."""
     dev = energy.device
     if y3 is not None and y3.numel():
-        a0, a1 = _span(y3)
+        a0, a1 = span(y3)
         for other in (energy, state, true_peak, ws):
             if other is not None and other.numel():
-                b0, b1 = _span(other)
+                b0, b1 = span(other)
                 if a0 < b1 and b0 < a1:
                     raise ValueError("the input overlaps the meter's own buffers")
     ys = (0, 0, 0) if y3 is None else y3.stride()
-    try:
-        with _hip.on_device(dev):
-            _hip.call("bas_meter_f32", _hip.ptr(y3), *ys, int(G), int(T_in), fs, fs // 10, _taps_host().ctypes.data,
-                      _hip.ptr(energy), energy.stride(0), energy.stride(1), int(energy.shape[2]), int(n_before),
-                      _hip.ptr(state), 0 if state is None else state.stride(0), _hip.ptr(true_peak), _hip.ptr(ws),
-                      0 if ws is None else ws.numel(), _hip.current_stream(dev))
-    except _hip.BasError as e:
-        if e.code == -2:
-            raise ValueError(str(e)) from None
-        raise
+    with _hip.shape_errors(), _hip.on_device(dev):
+        _hip.call("bas_meter_f32", _hip.ptr(y3), *ys, int(G), int(T_in), fs, fs // 10, _taps_host().ctypes.data,
+                  _hip.ptr(energy), energy.stride(0), energy.stride(1), int(energy.shape[2]), int(n_before),
+                  _hip.ptr(state), 0 if state is None else state.stride(0), _hip.ptr(true_peak), _hip.ptr(ws),
+                  0 if ws is None else ws.numel(), _hip.current_stream(dev))
 
 
 def _workspace(G, T_in, fs, device):
@@ -364,10 +326,10 @@ def measure(y, fs):
     fs = check_fs(fs)
     host = not isinstance(y, torch.Tensor)
     if host:
-        y = torch.from_numpy(_stereo_host(y)).to(_hip.require_gpu())
+        y = torch.from_numpy(stereo_host(y)).to(_hip.require_gpu())
     elif not y.is_cuda:
         raise ValueError("y must be a device tensor (or a host array)")
-    y3 = _check_stereo_device(y, "y")
+    y3 = stereo_device(y, "y")
     dev, hop = y.device, fs // 10
     G, n = int(y3.shape[0]), int(y3.shape[1])
     hops = n // hop
@@ -391,7 +353,7 @@ def normalize_loudness(y, fs, target=-23.0, max_true_peak=-1.0):
         g_db = torch.where(torch.isfinite(L), g_db, torch.zeros_like(g_db))
         g = (10.0 ** (g_db / 20.0)).float()
         return y * (g if y.dim() == 2 else g[:, None, None]), g_db
-    y32 = _stereo_host(y)
+    y32 = stereo_host(y)
     g_db = gain_db_for(m.integrated, m.true_peak_db, target, max_true_peak)
     g = (10.0 ** (g_db / 20.0)).astype(np.float32)
     if y32.ndim == 2:
@@ -425,12 +387,10 @@ class StreamMeter:
         import torch
         self.fs = check_fs(fs)
         self.hop = self.fs // 10
-        if isinstance(n_sessions, bool) or not isinstance(n_sessions, (int, np.integer)) or not 1 <= n_sessions <= MAX_SESSIONS:
-            raise ValueError(f"n_sessions must be an integer in 1..{MAX_SESSIONS}")
+        self.G = check_n_sessions(n_sessions)
         if isinstance(max_seconds, bool) or not isinstance(max_seconds, (int, float, np.integer, np.floating)) or \
                 not np.isfinite(max_seconds) or not 0.1 <= max_seconds <= 1e6:
             raise ValueError("max_seconds must be a number in 0.1..1e6")
-        self.G = int(n_sessions)
         self.max_hops = int(np.ceil(float(max_seconds) * 10.0 - 1e-9))
         self.device = _hip.require_gpu(device)
         words = _hip.lib().bas_meter_state_doubles()
@@ -443,7 +403,7 @@ class StreamMeter:
     def process(self, y_block):
         """Meter y_block: [B, 2] (n_sessions == 1) or [G, B, 2], a float32 device tensor of any strides, B >= 1."""
         import torch
-        y3 = _check_stereo_device(y_block, "y_block", self.G, self.device)
+        y3 = stereo_device(y_block, "y_block", self.G, self.device)
         B = int(y3.shape[1])
         if B < 1:
             raise ValueError("a block holds at least one sample")
@@ -460,31 +420,10 @@ class StreamMeter:
         self._count += B
 
     # ---- per-session state --------------------------------------------------------------------------------------------
-    def _sessions(self, sessions):
-        if sessions is None:
-            return list(range(self.G))
-        arr = np.asarray(sessions, dtype=np.int64).reshape(-1)
-        idx = sorted({int(g) for g in arr})
-        if idx and not (0 <= idx[0] and idx[-1] < self.G):
-            raise ValueError(f"session index out of range [0, {self.G})")
-        if len(idx) != arr.size:
-            raise ValueError("sessions must not repeat")
-        return idx
-
-    @staticmethod
-    def _runs(idx):
-        runs = []
-        for g in idx:
-            if runs and runs[-1][1] == g:
-                runs[-1][1] = g + 1
-            else:
-                runs.append([g, g + 1])
-        return runs
-
     def reset(self, sessions=None):
         """Drop the streams of these slots (None: all): state and energies zeroed (slice ops on the current stream).  The
         other sessions are not touched."""
-        for g0, g1 in self._runs(self._sessions(sessions)):
+        for g0, g1 in session_runs(session_indices(sessions, self.G)):
             self._state[g0:g1].zero_()
             self._energy[g0:g1].zero_()
             self._count[g0:g1] = 0
@@ -513,8 +452,8 @@ class StreamMeter:
         is dropped, the slots restart (reset).  Returns the finished streams' Loudness (numpy; sample_peak is not metered
         by a stream: None), one value per session in ascending session order - scalars for n_sessions == 1 and sessions
         None; .energies then holds the longest stream's hops, zero behind a shorter one's."""
-        idx = self._sessions(sessions)
-        for g0, g1 in self._runs(idx):
+        idx = session_indices(sessions, self.G)
+        for g0, g1 in session_runs(idx):
             _launch(None, g1 - g0, 0, self.fs, self._energy[g0:g1], int(self._count[g0:g1].max()), self._state[g0:g1],
                     None, None)
         hops, rd, E, tp = self._readings(idx)
@@ -529,7 +468,7 @@ class StreamMeter:
 
     def energies(self, session=0):
         """The hop energies of one session so far: float64 [hops, 2] on the host."""
-        idx = self._sessions([session])
+        idx = session_indices([session], self.G)
         counts, E, _ = self._download(idx)
         return np.ascontiguousarray(E[0, :, :min(int(counts[0]) // self.hop, self.max_hops)].T)
 

@@ -18,6 +18,7 @@ device kernel (bas_delay_rows_f32), which every render and stream path shares.
 import numpy as np
 
 from . import _hip
+from ._stage import host_array, is_device
 
 INTERPS = {"linear": 0, "cubic": 1}
 D_MIN = {"linear": 1.0, "cubic": 2.0}
@@ -53,7 +54,7 @@ def check_max_delay(max_delay, interp):
 def check_delay(delay, shape, interp, max_delay=None):
     """A host delay argument as a float64 numpy array of `shape`: ValueError for another shape, non-finite values, values
     below the interpolator's d_min or (with a bound) above max_delay."""
-    arr = np.asarray(delay.numpy() if hasattr(delay, "numpy") else delay, dtype=np.float64)
+    arr = np.asarray(host_array(delay), dtype=np.float64)
     if arr.shape != tuple(shape):
         raise ValueError(f"delay must have shape {tuple(shape)}, got {arr.shape}")
     if not np.isfinite(arr).all():
@@ -204,7 +205,7 @@ def _color_dims(shape, rows, n_q, taps):
 def check_color(color, rows, n_q, taps=None):
     """A host colour argument as a float32 numpy array [rows, n_q, M] or [rows, M] (static): ValueError for another
     shape, M outside 1..64 (or other than `taps`) or non-finite values."""
-    arr = np.asarray(color.numpy() if hasattr(color, "numpy") else color)
+    arr = np.asarray(host_array(color))
     _color_dims(arr.shape, rows, n_q, taps)
     arr = arr.astype(np.float32)
     if not np.isfinite(arr).all():
@@ -216,7 +217,7 @@ def is_device_color(color, rows, n_q, taps=None):
     """color is a device tensor: checked for shape and float32 dtype only (as the other primitives are).  False for host
     data."""
     import torch
-    if not (isinstance(color, torch.Tensor) and color.is_cuda):
+    if not (is_device(color)):
         return False
     _color_dims(color.shape, rows, n_q, taps)
     if color.dtype != torch.float32:
@@ -404,11 +405,11 @@ def design_colors_device(logmag, basis, out=None):
     device tensor of that shape with the taps contiguous - a StreamRenderer's color_view(B) is taken in place.  ValueError
     for other shapes or dtypes, before any device work."""
     import torch
-    if not (isinstance(logmag, torch.Tensor) and logmag.is_cuda and logmag.dtype == torch.float64 and logmag.dim() in (3, 4)):
+    if not (is_device(logmag) and logmag.dtype == torch.float64 and logmag.dim() in (3, 4)):
         raise ValueError("logmag must be a float64 device tensor [(G,) rows, nb, n_bands]")
     dev = logmag.device
     n_bands = int(logmag.shape[-1])
-    on_dev = isinstance(basis, torch.Tensor) and basis.is_cuda
+    on_dev = is_device(basis)
     bshape = tuple(basis.shape) if on_dev else np.shape(basis)
     if len(bshape) != 2 or bshape[0] != n_bands or not 1 <= n_bands <= MAX_BANDS or not 1 <= bshape[1] <= MAX_TAPS:
         raise ValueError(f"basis must be [{n_bands}, M] with 1 <= M <= {MAX_TAPS} and at most {MAX_BANDS} bands, got {bshape}")
@@ -416,7 +417,7 @@ def design_colors_device(logmag, basis, out=None):
         raise ValueError("a device basis must be float64")
     M = int(bshape[1])
     shape = tuple(logmag.shape[:-1]) + (M,)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.float32
+    if out is not None and not (is_device(out) and out.device == dev and out.dtype == torch.float32
                                 and tuple(out.shape) == shape and out.stride(-1) == 1
                                 and all(s >= 0 for s in out.stride())):
         raise ValueError(f"out must be a float32 tensor of shape {shape} on {dev} with contiguous taps")

@@ -19,6 +19,7 @@ import math
 import numpy as np
 
 from . import _hip
+from ._stage import host_array, is_device
 
 MAX_TAPS = 1 << 17
 MAX_LAG = 1 << 20
@@ -243,11 +244,11 @@ def send_to_device(send, n_src, n_q, dev):
     """send (None, host [n_src] or [n_src, n_q], or a float64 device tensor of either shape) as a float64 device tensor;
     host values validated (ValueError), device tensors checked for shape and dtype only."""
     import torch
-    if isinstance(send, torch.Tensor) and send.is_cuda:
+    if is_device(send):
         if send.dtype != torch.float64 or tuple(send.shape) not in ((n_src,), (n_src, n_q)):
             raise ValueError(f"send must be a float64 tensor of shape ({n_src},) or ({n_src}, {n_q})")
         return send
-    return torch.from_numpy(_send_array(send.numpy() if hasattr(send, "numpy") else send, n_src, n_q)).to(dev)
+    return torch.from_numpy(_send_array(host_array(send), n_src, n_q)).to(dev)
 
 
 def bus_mix_device(x, send, K, out, groups=None):

@@ -45,6 +45,7 @@ those of the straight path.
 import numpy as np
 
 from . import _hip, sphere, propagation, reverb
+from ._stage import host_array, is_device
 
 MAX_ORDER = 3
 SPEED_OF_SOUND = 343.0
@@ -173,15 +174,10 @@ def _scalars(fs, c, r_ref, interp, max_delay):
     return fs / c, r_ref, propagation.D_MIN[interp], d_max
 
 
-def _is_device(a):
-    import torch
-    return isinstance(a, torch.Tensor) and a.is_cuda
-
-
 def _host_array(name, a, shape, room=None):
     """Host data as a float64 array of `shape`: ValueError for another shape, non-finite values or, with a room,
     positions outside it."""
-    arr = np.asarray(a.numpy() if hasattr(a, "numpy") else a, dtype=np.float64)
+    arr = np.asarray(host_array(a), dtype=np.float64)
     if arr.shape != tuple(shape):
         raise ValueError(f"{name} must have shape {tuple(shape)}, got {arr.shape}")
     if not np.isfinite(arr).all():
@@ -215,7 +211,7 @@ def check_scene_args(pos_shape, pos, listener_pos, head, src_gain, room):
             if name == "pos":
                 raise ValueError("pos is required")
             out.append(None)
-        elif _is_device(a):
+        elif is_device(a):
             if tuple(a.shape) != shape or a.dtype != torch.float64:
                 raise ValueError(f"{name} must be a float64 tensor of shape {shape}")
             out.append(a)
@@ -241,7 +237,7 @@ def _check_motion(chunksize, pos_prev, pos_shape, room):
     if pos_prev is None:
         return spc, None
     shape = tuple(pos_shape[:-2]) + (3,)
-    if _is_device(pos_prev):
+    if is_device(pos_prev):
         if tuple(pos_prev.shape) != shape or pos_prev.dtype != torch.float64:
             raise ValueError(f"pos_prev must be a float64 tensor of shape {shape}")
         return spc, pos_prev
@@ -267,9 +263,9 @@ def _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
     of step 2 (before the head turns it) and the path's ends q and l themselves, float64 (..., n_src, n_img, nb) and three
     times (..., n_src, n_img, nb, 3)."""
     spm, r_ref, d_min, d_max = _scalars(fs, c, r_ref, interp, max_delay)
-    if any(_is_device(a) for a in (pos, listener_pos, head, src_gain)):
+    if any(is_device(a) for a in (pos, listener_pos, head, src_gain)):
         raise ValueError("scene_params takes host arrays (scene_params_device takes device tensors)")
-    if _is_device(pos_prev):
+    if is_device(pos_prev):
         raise ValueError("scene_params takes host arrays (scene_params_device takes device tensors)")
     p, l, q, sg = check_scene_args(np.shape(pos), pos, listener_pos, head, src_gain, room)
     spc, prev = _check_motion(chunksize, pos_prev, p.shape, room)
@@ -644,7 +640,7 @@ def _check_orient(orient, pos_shape):
     if orient is None:
         return None
     shape = tuple(pos_shape[:-1]) + (4,)
-    if _is_device(orient):
+    if is_device(orient):
         if tuple(orient.shape) != shape or orient.dtype != torch.float64:
             raise ValueError(f"orient must be a float64 tensor of shape {shape}")
         return orient
@@ -667,7 +663,7 @@ def scene_color_params(pos, fs, listener_pos=None, head=None, room=None, src_gai
     without them nothing is added: the bits of a colour that never had any).  Returns (elev, azim, gain, delay, logmag): scene_params' four, bit for bit, and logmag
     float64 (..., n_src n_img, nb, n_bands)."""
     lnw = _check_color(color, room, np.shape(pos)[-3] if len(np.shape(pos)) >= 3 else 0)
-    if _is_device(orient):
+    if is_device(orient):
         raise ValueError("scene_color_params takes host arrays (scene_color_params_device takes device tensors)")
     el, az, gain, delay, r, v, q, l = _scene_params(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
                                                     max_delay, chunksize, pos_prev)
@@ -750,9 +746,9 @@ def _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
     spc, prev = _check_motion(chunksize, pos_prev, pos_shape, room)
     n_img = _n_img(room)
     n_out = 4 if color is None else 5
-    tensors = [t for t in args + (prev, orient) + tuple(out or ()) if _is_device(t)]
+    tensors = [t for t in args + (prev, orient) + tuple(out or ()) if is_device(t)]
     dev = tensors[0].device if tensors else _hip.require_gpu()
-    p, l, q, sg, prev, orient = (None if a is None else _unit_last(a.to(dev) if _is_device(a) else torch.from_numpy(a).to(dev))
+    p, l, q, sg, prev, orient = (None if a is None else _unit_last(a.to(dev) if is_device(a) else torch.from_numpy(a).to(dev))
                                  for a in args + (prev, orient))
     batched = len(pos_shape) == 4
     G = pos_shape[0] if batched else 1
@@ -769,10 +765,10 @@ def _scene_device(pos, fs, listener_pos, head, room, src_gain, c, r_ref, interp,
         raise ValueError("out must be (elev, azim, gain, delay" + (")" if color is None else ", logmag)") +
                          "; gain and delay may be None")
     for t in out[:4]:
-        if t is not None and not (_is_device(t) and t.device == dev and t.dtype == torch.float64 and tuple(t.shape) == shape
+        if t is not None and not (is_device(t) and t.device == dev and t.dtype == torch.float64 and tuple(t.shape) == shape
                                   and t.stride(-1) == 1):
             raise ValueError(f"out tensors must be float64 of shape {shape} on {dev} with unit stride on the last axis")
-    if color is not None and not (_is_device(out[4]) and out[4].device == dev and out[4].dtype == torch.float64
+    if color is not None and not (is_device(out[4]) and out[4].device == dev and out[4].dtype == torch.float64
                                   and tuple(out[4].shape) == lshape and out[4].stride(-1) == 1
                                   and all(s >= 0 for s in out[4].stride())):
         raise ValueError(f"out's logmag must be float64 of shape {lshape} on {dev} with unit stride along the bands")
@@ -866,14 +862,14 @@ def render_scene(signals, chunksize, subchunksize, pos, tbl, fs, listener_pos=No
         orient = _check_orient(orient, (n_src, n_q, 3))
     tbl = as_device_table(tbl)
     dev = tbl.device
-    args = tuple(a.to(dev) if _is_device(a) else a for a in args)
-    if not any(_is_device(a) for a in args):
+    args = tuple(a.to(dev) if is_device(a) else a for a in args)
+    if not any(is_device(a) for a in args):
         args = (torch.from_numpy(args[0]).to(dev),) + args[1:]        # (so that the scene runs on the table's device)
     taps = None
     if color is None:
         el, az, g, d = scene_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp, chunksize=K)
     else:                                                              # the bands with the geometry, then every row's taps
-        orient = orient.to(dev) if _is_device(orient) else orient
+        orient = orient.to(dev) if is_device(orient) else orient
         el, az, g, d, lm = scene_color_params_device(args[0], fs, args[1], args[2], room, args[3], c, r_ref, interp,
                                                      chunksize=K, color=color, orient=orient)
         taps = propagation.design_colors_device(lm, color.device_arrays(dev, fs, room)[3])
@@ -995,8 +991,8 @@ class SceneStreamRenderer:
         orient = _check_orient(orient, (self.n_src, B // self.K + 1, 3))
         st, dev = self.inner, self.inner.tbl.device
         out = st.trajectory_views(B) + (st.gain_view(B), st.delay_view(B))
-        args = tuple(a.to(dev) if _is_device(a) else a for a in args)
-        p = args[0] if _is_device(args[0]) else torch.from_numpy(args[0]).to(dev)
+        args = tuple(a.to(dev) if is_device(a) else a for a in args)
+        p = args[0] if is_device(args[0]) else torch.from_numpy(args[0]).to(dev)
         taps = self._bank
         if self.color is None:
             el, az, g, d = scene_params_device(p, self.fs, args[1], args[2], self.room, args[3], self.c, self.r_ref,
@@ -1006,7 +1002,7 @@ class SceneStreamRenderer:
             lshape = (self.n_src * self.n_img, B // self.K + 1, self.color.bands.size)
             if self._logmag is None or tuple(self._logmag.shape) != lshape:
                 self._logmag = torch.empty(lshape, dtype=torch.float64, device=dev)
-            orient = orient.to(dev) if _is_device(orient) else orient
+            orient = orient.to(dev) if is_device(orient) else orient
             el, az, g, d, lm = scene_color_params_device(p, self.fs, args[1], args[2], self.room, args[3], self.c,
                                                          self.r_ref, self.interp, self.max_delay, out=out + (self._logmag,),
                                                          chunksize=self.K, pos_prev=self._prev, color=self.color,

@@ -31,8 +31,8 @@ from . import _hip, sphere, propagation
 from .batch import MAX_RENDER_SAMPLES, render_batch
 from .apply_hrtf import check_gain, gain_to_device
 from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views, stage
+from ._stage import MAX_SESSIONS, session_indices, session_runs
 
-MAX_SESSIONS = 65535             # the epilogue and pack kernels have one row of workgroups per session (gridDim.y)
 
 
 @dataclass(frozen=True)
@@ -110,17 +110,6 @@ def plan_stream_layout(n_sessions, n_src, K, L, B):
         raise ValueError(f"{G} sessions x {n_src} sources x blocks of {B}: n_src * T_in = {n_src * lay.T_in} exceeds "
                          f"{MAX_RENDER_SAMPLES} samples of one render")
     return lay
-
-
-def _session_runs(idx):
-    """[(g0, g1), ...]: maximal runs of consecutive session indices (one slice op per run: no index tensor, no copy)."""
-    runs = []
-    for g in idx:
-        if runs and runs[-1][1] == g:
-            runs[-1][1] = g + 1
-        else:
-            runs.append([g, g + 1])
-    return [tuple(r) for r in runs]
 
 
 class StreamBatchRenderer(_BlockStream):
@@ -356,18 +345,15 @@ class StreamBatchRenderer(_BlockStream):
         return self._peaks
 
     def _sessions(self, sessions):
-        idx = sorted({int(g) for g in np.asarray(sessions, dtype=np.int64).reshape(-1)})
-        if idx and not (0 <= idx[0] and idx[-1] < self.G):
-            raise ValueError(f"session index out of range [0, {self.G})")
-        if len(idx) != np.asarray(sessions).size:
-            raise ValueError("sessions must not repeat")
-        return idx
+        if sessions is None:                              # (None is "all" to the stages behind a render; a renderer's
+            raise TypeError("sessions must be a list of session indices")   # reset and finish take the list alone)
+        return session_indices(sessions, self.G)
 
     def reset(self, sessions):
         """Drop the streams of these slots without a tail: their halo inputs, halo angles, end angles, peaks and raw delay
         histories are zeroed on the device (slice ops on the current stream, no synchronisation), their carried gains set
         to one.  Their next block starts fresh."""
-        for g0, g1 in _session_runs(self._sessions(sessions)):
+        for g0, g1 in session_runs(self._sessions(sessions)):
             if self._lay is not None:
                 self._x3()[:, g0:g1, :self.halo].zero_()
                 self._a3(self._elev_all)[:, g0:g1, :self.nh].zero_()

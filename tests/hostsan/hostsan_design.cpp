@@ -10,36 +10,12 @@
 //   3. `hostsan_design design IN OUT`: the same host build as a filter bank for the Python tests - IN holds int32 n_bands,
 //      M, n, then float64 floor, basis [n_bands][M], logmag [n][n_bands]; OUT receives float32 taps [n][M].
 // Exits 77 where a GPU is visible.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
-#include "../../include/bas.h"
+#define HOSTSAN_NAME "hostsan_design"
+#include "hostsan_common.h"
 #include "../../binaural-audio-synthesis_amd/csrc/bas_design.h"
-
-static int g_fail = 0, g_checks = 0;
-
-static void expect(int line, const char *what, int rc, int want, const char *entry) {
-    ++g_checks;
-    const char *text = bas_last_error();
-    bool ok = want > 0 ? rc > 0 : rc == want;
-    if (ok && want != 0) ok = text && strstr(text, entry) != nullptr;      // every failure leaves a text naming the entry
-    if (!ok && ++g_fail <= 40)
-        fprintf(stderr, "hostsan_design: FAIL line %d: %s: returned %d, want %s%d, text \"%s\"\n", line, what, rc,
-                want > 0 ? "> " : "", want > 0 ? 0 : want, text ? text : "(null)");
-}
-#define EXPECT(what, call, want, entry) expect(__LINE__, what, (call), (want), entry)
-
-static const int E_NULL = -1, E_SHAPE = -2, E_ALIGN = -3, NO_DEVICE = 1;
-
-template <class T>
-static T *at(uintptr_t base, long bytes) {
-    return reinterpret_cast<T *>(base + bytes);
-}
 
 struct Bands {
     const double *pos;
@@ -209,11 +185,6 @@ static void restated(const double *logmag, const double *basis, int n_bands, int
     }
 }
 
-static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-static double uniform() {                                                   // xorshift64*, in [0, 1)
-    g_rng ^= g_rng >> 12; g_rng ^= g_rng << 25; g_rng ^= g_rng >> 27;
-    return (double)((g_rng * 0x2545f4914f6cdd1dull) >> 11) / 9007199254740992.0;
-}
 
 static double filter_section() {
     const double floor = std::log(1e-6);
@@ -286,14 +257,7 @@ static int design_file(const char *in_path, const char *out_path) {
 }
 
 int main(int argc, char **argv) {
-    int n_dev = 0;
-    const hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e == hipSuccess && n_dev > 0) {
-        printf("hostsan_design: refused: %d GPU device(s) visible - sanitized host code never drives a GPU; hide them "
-               "(HIP_VISIBLE_DEVICES=-1)\n", n_dev);
-        return 77;
-    }
-    (void)hipGetLastError();
+    if (hostsan_gpu_visible("hostsan_design")) return 77;
     if (argc == 4 && strcmp(argv[1], "design") == 0) return design_file(argv[2], argv[3]);
     bands_section();
     const int after_bands = g_checks;

@@ -4,28 +4,9 @@
 // bas_ambi_encode_f32: one valid argument list, which with no device to run on returns a positive hipError_t, and its
 // violations, each of which returns the code bas.h documents and leaves a text naming the entry point.  The pointers are
 // never dereferenced by the host code (scale is: it is host memory by contract).  Exits 77 where a GPU is visible.
-#include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-
-#include "../../include/bas.h"
-
-static int g_fail = 0, g_checks = 0;
-
-static void expect(int line, const char *what, int rc, int want, const char *entry) {
-    ++g_checks;
-    const char *text = bas_last_error();
-    bool ok = want > 0 ? rc > 0 : rc == want;
-    if (ok && want != 0) ok = text && strstr(text, entry) != nullptr;      // every failure leaves a text naming the entry
-    if (!ok && ++g_fail <= 40)
-        fprintf(stderr, "hostsan_encode: FAIL line %d: %s: returned %d, want %s%d, text \"%s\"\n", line, what, rc,
-                want > 0 ? "> " : "", want > 0 ? 0 : want, text ? text : "(null)");
-}
-#define EXPECT(what, call, want, entry) expect(__LINE__, what, (call), (want), entry)
-
-static const int E_NULL = -1, E_SHAPE = -2, E_ALIGN = -3, NO_DEVICE = 1;
+#define HOSTSAN_NAME "hostsan_encode"
+#include "hostsan_common.h"
 
 struct Gains {
     const double *elev, *azim;
@@ -58,11 +39,6 @@ struct Mix {
         return bas_ambi_encode_f32(x, xs_g, xs_s, e, es_g, es_k, n_src, C, G, T, K, base, bs_g, bs_c, y, ys_g, ys_c, nullptr);
     }
 };
-
-template <class T>
-static T *at(uintptr_t base, long bytes) {
-    return reinterpret_cast<T *>(base + bytes);
-}
 
 static void gains_section() {
     static const char *N = "bas_ambi_encode_gains_f32";
@@ -182,14 +158,7 @@ static void mix_section() {
 }
 
 int main() {
-    int n_dev = 0;
-    const hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e == hipSuccess && n_dev > 0) {
-        printf("hostsan_encode: refused: %d GPU device(s) visible - sanitized host code never drives a GPU; hide them "
-               "(HIP_VISIBLE_DEVICES=-1)\n", n_dev);
-        return 77;
-    }
-    (void)hipGetLastError();
+    if (hostsan_gpu_visible("hostsan_encode")) return 77;
     gains_section();
     const int after_gains = g_checks;
     mix_section();

@@ -23,9 +23,11 @@
 #include <functional>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/bas.h"
+#include "../../binaural-audio-synthesis_amd/csrc/bas_views.h"
 #ifdef HOSTSAN_ORACLE
 #include "../../oracle/bas_oracle_fir.h"
 #endif
@@ -252,6 +254,78 @@ static bool repeats(int G, int n_src, int nb, long sg, long ss) {   // does [G][
     return false;
 }
 
+// the limiter's nested test restated with no overflow guard: a (G, T, 2) view with strides (sg, st, se)
+static bool lim_layout_nested(long G, long T, long sg, long st, long se) {
+    long s[3] = {se, st, sg}, e[3] = {2, T, G};
+    for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b)
+            if (s[b] < s[a]) {
+                std::swap(s[a], s[b]);
+                std::swap(e[a], e[b]);
+            }
+    long span = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (e[k] == 1) continue;
+        if (s[k] < span) return false;
+        span = s[k] * (e[k] - 1) + span;
+    }
+    return true;
+}
+
+// bas_views.h against the enumeration of every address: all extents 1..3 in three dimensions, all strides 0..9
+static long views_cases() {
+    long n_cases = 0;
+    long ext[3], str[3];
+    for (ext[0] = 1; ext[0] <= 3; ++ext[0])
+        for (ext[1] = 1; ext[1] <= 3; ++ext[1])
+            for (ext[2] = 1; ext[2] <= 3; ++ext[2])
+                for (str[0] = 0; str[0] <= 9; ++str[0])
+                    for (str[1] = 0; str[1] <= 9; ++str[1])
+                        for (str[2] = 0; str[2] <= 9; ++str[2]) {
+                            int hits[3 * 2 * 9 + 1] = {0};
+                            long last = 0;
+                            bool rep = false;
+                            for (long i = 0; i < ext[0]; ++i)
+                                for (long j = 0; j < ext[1]; ++j)
+                                    for (long k = 0; k < ext[2]; ++k) {
+                                        const long at = i * str[0] + j * str[1] + k * str[2];
+                                        rep |= hits[at]++ > 0;
+                                        last = at > last ? at : last;
+                                    }
+                            const bool nested = bas_layout_nested(3, ext, str);
+                            CHECK(bas_view_extent(3, ext, str) == last + 1, "bas_view_extent [%ld][%ld][%ld] at (%ld, %ld, %ld): %ld, last address %ld",
+                                  ext[0], ext[1], ext[2], str[0], str[1], str[2], bas_view_extent(3, ext, str), last);
+                            CHECK(!nested || !rep, "bas_layout_nested [%ld][%ld][%ld] at (%ld, %ld, %ld) passes a layout that repeats an address", ext[0],
+                                  ext[1], ext[2], str[0], str[1], str[2]);
+                            n_cases += 2;
+                            if (ext[2] == 2) {                           // the limiter's (G, T, 2) form
+                                CHECK(nested == lim_layout_nested(ext[0], ext[1], str[0], str[1], str[2]),
+                                      "bas_layout_nested [%ld][%ld][2] at (%ld, %ld, %ld) is %d, the limiter's own test said otherwise", ext[0], ext[1],
+                                      str[0], str[1], str[2], (int)nested);
+                                ++n_cases;
+                            }
+                            if (str[2] == 1) {                           // stride-1 innermost: the exact predicate
+                                CHECK(bas_layout_one_to_one(ext[0], ext[1], ext[2], str[0], str[1]) == !rep,
+                                      "bas_layout_one_to_one [%ld][%ld][%ld] at (%ld, %ld): brute force %s", ext[0], ext[1], ext[2], str[0], str[1],
+                                      rep ? "finds a repeat" : "finds none");
+                                ++n_cases;
+                            }
+                        }
+    // bas_ranges_meet: byte ranges that touch, overlap by one byte, nest; null pointers and empty ranges meet nothing
+    const unsigned char *b = g_buf[0];
+    const struct { const void *a; size_t na; const void *b; size_t nb; bool meet; } R[] = {
+        {b, 16, b + 16, 16, false},   {b + 16, 16, b, 16, false},  {b, 17, b + 16, 16, true},  {b + 16, 16, b, 17, true},
+        {b, 64, b + 8, 8, true},      {b + 8, 8, b, 64, true},     {b, 16, b, 16, true},       {b, 1, b, 1, true},
+        {nullptr, 16, b, 16, false},  {b, 16, nullptr, 16, false}, {nullptr, 16, nullptr, 16, false},
+        {b + 4, 0, b, 16, false},     {b, 16, b + 4, 0, false},    {b, 0, b, 0, false},
+    };
+    for (const auto &r : R) {
+        CHECK(bas_ranges_meet(r.a, r.na, r.b, r.nb) == r.meet, "bas_ranges_meet(%p, %zu, %p, %zu) is not %d", r.a, r.na, r.b, r.nb, (int)r.meet);
+        ++n_cases;
+    }
+    return n_cases;
+}
+
 static int section_d() {
     double *in_e = (double *)buf(0), *in_a = (double *)buf(1), *head = (double *)buf(2), *out_e = (double *)buf(3), *out_a = (double *)buf(4);
     long n_cases = 0;
@@ -355,6 +429,7 @@ static int section_d() {
             const bool ok = (interp == 0 || interp == 1) && md == 0.0;
             CHECK((rc == BAS_E_SHAPE) == !ok, "bas_delay_rows_f32 interp = %d max_delay = %g: rc %d", interp, md, rc);
         }
+    n_cases += views_cases();
     printf("hostsan: section d: %ld cases\n", n_cases);
     return g_fail;
 }

@@ -8,36 +8,12 @@
 //      A^(R 2^i) and A^hop, which the kernels take by value - against a restatement in long double: the coefficients from
 //      tanl, the powers by multiplying n times (the library squares), and the matrix itself by stepping the two biquads sample by sample.
 // Exits 77 where a GPU is visible.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
-#include "../../include/bas.h"
+#define HOSTSAN_NAME "hostsan_meter"
+#include "hostsan_common.h"
 #include "../../binaural-audio-synthesis_amd/csrc/bas_meter.h"
-
-static int g_fail = 0, g_checks = 0;
-
-static void expect(int line, const char *what, int rc, int want, const char *entry) {
-    ++g_checks;
-    const char *text = bas_last_error();
-    bool ok = want > 0 ? rc > 0 : rc == want;
-    if (ok && want != 0) ok = text && strstr(text, entry) != nullptr;      // every failure leaves a text naming the entry
-    if (!ok && ++g_fail <= 40)
-        fprintf(stderr, "hostsan_meter: FAIL line %d: %s: returned %d, want %s%d, text \"%s\"\n", line, what, rc,
-                want > 0 ? "> " : "", want > 0 ? 0 : want, text ? text : "(null)");
-}
-#define EXPECT(what, call, want) expect(__LINE__, what, (call), (want), "bas_meter_f32")
-
-static const int E_NULL = -1, E_SHAPE = -2, E_ALIGN = -3, NO_DEVICE = 1;
-
-template <class T>
-static T *at(uintptr_t base, long bytes) {
-    return reinterpret_cast<T *>(base + bytes);
-}
 
 struct Meter {
     const float *y;
@@ -60,6 +36,7 @@ struct Meter {
 };
 
 static void entry_section() {
+    static const char *N = "bas_meter_f32";
     const uintptr_t p = uintptr_t(1) << 32;                                  // made-up device addresses, 64-byte aligned
     static float taps[MET_PHASES * MET_TAPS];
     for (int i = 0; i < MET_PHASES * MET_TAPS; ++i) taps[i] = (i % MET_TAPS == 5) ? 1.f : 0.f;
@@ -77,70 +54,70 @@ static void entry_section() {
         ++g_fail;
         fprintf(stderr, "hostsan_meter: FAIL bas_meter_workspace_bytes\n");
     }
-    EXPECT("a stream block, no device", ok.call(), NO_DEVICE);
+    EXPECT("a stream block, no device", ok.call(), NO_DEVICE, N);
     a = ok; a.T = hop + 1;
-    EXPECT("the longest one-launch block, no device", a.call(), NO_DEVICE);
+    EXPECT("the longest one-launch block, no device", a.call(), NO_DEVICE, N);
     a = ok; a.T = 3 * hop + 5;
-    EXPECT("a chained block, no device", a.call(), NO_DEVICE);
+    EXPECT("a chained block, no device", a.call(), NO_DEVICE, N);
     a = ok; a.T = 0; a.y = nullptr;
-    EXPECT("a stream's end, no device", a.call(), NO_DEVICE);
+    EXPECT("a stream's end, no device", a.call(), NO_DEVICE, N);
     a = ok; a.state = nullptr; a.tp = at<float>(p, 4 << 20); a.T = 19999;
-    EXPECT("a whole signal, no device", a.call(), NO_DEVICE);
+    EXPECT("a whole signal, no device", a.call(), NO_DEVICE, N);
     a = ok; a.state = nullptr; a.ss = 0;
-    EXPECT("a whole signal without a peak, no device", a.call(), NO_DEVICE);
+    EXPECT("a whole signal without a peak, no device", a.call(), NO_DEVICE, N);
     a = ok; a.y_g = 2; a.y_t = 2 * G; a.y_e = 1;
-    EXPECT("sessions interleaved, no device", a.call(), NO_DEVICE);
+    EXPECT("sessions interleaved, no device", a.call(), NO_DEVICE, N);
     a = ok; a.y_t = 1; a.y_e = 600; a.y_g = 1300;
-    EXPECT("planar, no device", a.call(), NO_DEVICE);
+    EXPECT("planar, no device", a.call(), NO_DEVICE, N);
     a = ok; a.fs = 192000; a.hop = 19200; a.T = 19201;
-    EXPECT("192 kHz, the largest LDS, no device", a.call(), NO_DEVICE);
+    EXPECT("192 kHz, the largest LDS, no device", a.call(), NO_DEVICE, N);
     a = ok; a.fs = 8000; a.hop = 800; a.before = 99 * 800 + 288;
-    EXPECT("the last hop that fits, no device", a.call(), NO_DEVICE);
+    EXPECT("the last hop that fits, no device", a.call(), NO_DEVICE, N);
     a = ok; a.G = 0; a.y = nullptr; a.energy = nullptr; a.state = nullptr;
-    EXPECT("no sessions", a.call(), 0);
+    EXPECT("no sessions", a.call(), 0, N);
     a = ok; a.state = nullptr; a.T = 0; a.y = nullptr; a.taps = nullptr;
-    EXPECT("an empty whole signal", a.call(), 0);
+    EXPECT("an empty whole signal", a.call(), 0, N);
     // ---- shapes
-    for (int fs : {7990, 192010, 44101, 48001, 0, -48000}) { a = ok; a.fs = fs; a.hop = fs / 10; EXPECT("fs", a.call(), E_SHAPE); }
-    for (int h : {4799, 4801, 4410, 0, -4800}) { a = ok; a.hop = h; EXPECT("hop", a.call(), E_SHAPE); }
-    for (int n : {-1, 65536}) { a = ok; a.G = n; EXPECT("n_sessions", a.call(), E_SHAPE); }
-    for (long t : {-1L, 1L << 30}) { a = ok; a.T = t; EXPECT("T_in", a.call(), E_SHAPE); }
-    for (long m : {-1L, 1L << 31}) { a = ok; a.max_hops = m; EXPECT("max_hops", a.call(), E_SHAPE); }
+    for (int fs : {7990, 192010, 44101, 48001, 0, -48000}) { a = ok; a.fs = fs; a.hop = fs / 10; EXPECT("fs", a.call(), E_SHAPE, N); }
+    for (int h : {4799, 4801, 4410, 0, -4800}) { a = ok; a.hop = h; EXPECT("hop", a.call(), E_SHAPE, N); }
+    for (int n : {-1, 65536}) { a = ok; a.G = n; EXPECT("n_sessions", a.call(), E_SHAPE, N); }
+    for (long t : {-1L, 1L << 30}) { a = ok; a.T = t; EXPECT("T_in", a.call(), E_SHAPE, N); }
+    for (long m : {-1L, 1L << 31}) { a = ok; a.max_hops = m; EXPECT("max_hops", a.call(), E_SHAPE, N); }
     for (int i = 0; i < 6; ++i) {
         a = ok;
         long *f[6] = {&a.y_g, &a.y_t, &a.y_e, &a.e_g, &a.e_e, &a.ss};
         *f[i] = -2;
-        EXPECT("negative stride", a.call(), E_SHAPE);
+        EXPECT("negative stride", a.call(), E_SHAPE, N);
     }
-    a = ok; a.y_g = 1L << 40; EXPECT("session stride too large", a.call(), E_SHAPE);
-    a = ok; a.y_t = 1L << 31; EXPECT("sample stride too large", a.call(), E_SHAPE);
-    a = ok; a.ss = words - 2; EXPECT("state stride too small", a.call(), E_SHAPE);
-    a = ok; a.ss = words + 1; EXPECT("state stride odd", a.call(), E_SHAPE);
-    a = ok; a.before = -1; EXPECT("n_before negative", a.call(), E_SHAPE);
-    a = ok; a.state = nullptr; a.before = 7; EXPECT("a whole signal starts at 0", a.call(), E_SHAPE);
-    a = ok; a.tp = at<float>(p, 4 << 20); EXPECT("true_peak with a state", a.call(), E_SHAPE);
-    a = ok; a.before = 101L * hop - 512; EXPECT("energy buffer full", a.call(), E_SHAPE);
-    a = ok; a.max_hops = 0; a.before = hop - 1; EXPECT("no room for any hop", a.call(), E_SHAPE);
-    a = ok; a.e_g = 2 * max_hops - 1; EXPECT("energy sessions overlap", a.call(), E_SHAPE);
-    a = ok; a.e_e = max_hops - 1; EXPECT("energy ears overlap", a.call(), E_SHAPE);
-    a = ok; a.e_g = 0; EXPECT("energy session stride 0", a.call(), E_SHAPE);
-    a = ok; a.T = 3 * hop + 5; a.wsb = bas_meter_workspace_bytes(G, a.T, hop) - 1; EXPECT("workspace too small", a.call(), E_SHAPE);
-    a = ok; a.energy = at<double>(p, 8); EXPECT("energy inside y", a.call(), E_SHAPE);
-    a = ok; a.state = at<double>(p, 64); EXPECT("state inside y", a.call(), E_SHAPE);
-    a = ok; a.state = at<double>(p, (1 << 20) + 64); EXPECT("state inside the energies", a.call(), E_SHAPE);
-    a = ok; a.T = 3 * hop + 5; a.ws = at<void>(p, (1 << 20) + 256); EXPECT("workspace inside the energies", a.call(), E_SHAPE);
-    a = ok; a.T = 3 * hop + 5; a.ws = at<void>(p, 2 << 20); EXPECT("workspace on the state", a.call(), E_SHAPE);
-    a = ok; a.state = nullptr; a.tp = at<float>(p, (1 << 20) + 8); EXPECT("true_peak inside the energies", a.call(), E_SHAPE);
+    a = ok; a.y_g = 1L << 40; EXPECT("session stride too large", a.call(), E_SHAPE, N);
+    a = ok; a.y_t = 1L << 31; EXPECT("sample stride too large", a.call(), E_SHAPE, N);
+    a = ok; a.ss = words - 2; EXPECT("state stride too small", a.call(), E_SHAPE, N);
+    a = ok; a.ss = words + 1; EXPECT("state stride odd", a.call(), E_SHAPE, N);
+    a = ok; a.before = -1; EXPECT("n_before negative", a.call(), E_SHAPE, N);
+    a = ok; a.state = nullptr; a.before = 7; EXPECT("a whole signal starts at 0", a.call(), E_SHAPE, N);
+    a = ok; a.tp = at<float>(p, 4 << 20); EXPECT("true_peak with a state", a.call(), E_SHAPE, N);
+    a = ok; a.before = 101L * hop - 512; EXPECT("energy buffer full", a.call(), E_SHAPE, N);
+    a = ok; a.max_hops = 0; a.before = hop - 1; EXPECT("no room for any hop", a.call(), E_SHAPE, N);
+    a = ok; a.e_g = 2 * max_hops - 1; EXPECT("energy sessions overlap", a.call(), E_SHAPE, N);
+    a = ok; a.e_e = max_hops - 1; EXPECT("energy ears overlap", a.call(), E_SHAPE, N);
+    a = ok; a.e_g = 0; EXPECT("energy session stride 0", a.call(), E_SHAPE, N);
+    a = ok; a.T = 3 * hop + 5; a.wsb = bas_meter_workspace_bytes(G, a.T, hop) - 1; EXPECT("workspace too small", a.call(), E_SHAPE, N);
+    a = ok; a.energy = at<double>(p, 8); EXPECT("energy inside y", a.call(), E_SHAPE, N);
+    a = ok; a.state = at<double>(p, 64); EXPECT("state inside y", a.call(), E_SHAPE, N);
+    a = ok; a.state = at<double>(p, (1 << 20) + 64); EXPECT("state inside the energies", a.call(), E_SHAPE, N);
+    a = ok; a.T = 3 * hop + 5; a.ws = at<void>(p, (1 << 20) + 256); EXPECT("workspace inside the energies", a.call(), E_SHAPE, N);
+    a = ok; a.T = 3 * hop + 5; a.ws = at<void>(p, 2 << 20); EXPECT("workspace on the state", a.call(), E_SHAPE, N);
+    a = ok; a.state = nullptr; a.tp = at<float>(p, (1 << 20) + 8); EXPECT("true_peak inside the energies", a.call(), E_SHAPE, N);
     // ---- NULLs and alignment
-    a = ok; a.y = nullptr; EXPECT("y null", a.call(), E_NULL);
-    a = ok; a.taps = nullptr; EXPECT("taps null", a.call(), E_NULL);
-    a = ok; a.energy = nullptr; EXPECT("energy null", a.call(), E_NULL);
-    a = ok; a.T = 3 * hop + 5; a.ws = nullptr; EXPECT("workspace null", a.call(), E_NULL);
-    a = ok; a.y = at<const float>(p, 2); EXPECT("y misaligned", a.call(), E_ALIGN);
-    a = ok; a.energy = at<double>(p, (1 << 20) + 4); EXPECT("energy misaligned", a.call(), E_ALIGN);
-    a = ok; a.state = at<double>(p, (2 << 20) + 8); EXPECT("state misaligned", a.call(), E_ALIGN);
-    a = ok; a.state = nullptr; a.tp = at<float>(p, (4 << 20) + 2); EXPECT("true_peak misaligned", a.call(), E_ALIGN);
-    a = ok; a.T = 3 * hop + 5; a.ws = at<void>(p, (3 << 20) + 8); EXPECT("workspace misaligned", a.call(), E_ALIGN);
+    a = ok; a.y = nullptr; EXPECT("y null", a.call(), E_NULL, N);
+    a = ok; a.taps = nullptr; EXPECT("taps null", a.call(), E_NULL, N);
+    a = ok; a.energy = nullptr; EXPECT("energy null", a.call(), E_NULL, N);
+    a = ok; a.T = 3 * hop + 5; a.ws = nullptr; EXPECT("workspace null", a.call(), E_NULL, N);
+    a = ok; a.y = at<const float>(p, 2); EXPECT("y misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.energy = at<double>(p, (1 << 20) + 4); EXPECT("energy misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.state = at<double>(p, (2 << 20) + 8); EXPECT("state misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.state = nullptr; a.tp = at<float>(p, (4 << 20) + 2); EXPECT("true_peak misaligned", a.call(), E_ALIGN, N);
+    a = ok; a.T = 3 * hop + 5; a.ws = at<void>(p, (3 << 20) + 8); EXPECT("workspace misaligned", a.call(), E_ALIGN, N);
 }
 
 // ---- part 2: the host arithmetic against a restatement ---------------------------------------------------------------------
@@ -290,14 +267,7 @@ static void powers_section(double *worst_coef, double *worst_pow) {
 }
 
 int main() {
-    int n_dev = 0;
-    const hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e == hipSuccess && n_dev > 0) {
-        printf("hostsan_meter: refused: %d GPU device(s) visible - sanitized host code never drives a GPU; hide them "
-               "(HIP_VISIBLE_DEVICES=-1)\n", n_dev);
-        return 77;
-    }
-    (void)hipGetLastError();
+    if (hostsan_gpu_visible("hostsan_meter")) return 77;
     entry_section();
     const int after_entry = g_checks;
     double worst_coef = 0.0, worst_pow = 0.0;

@@ -12,36 +12,12 @@
 //      [n_screens][n_bands] (if any), q [n_paths][3], l [n_paths][3], then int32 images [n_paths][3]; OUT receives float64
 //      sums [n_paths][n_bands] and signed detours of the first screen's copy in cell 0 [n_paths] (NaN: not crossed).
 // Exits 77 where a GPU is visible.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <vector>
 
-#include "../../include/bas.h"
+#define HOSTSAN_NAME "hostsan_occlude"
+#include "hostsan_common.h"
 #include "../../binaural-audio-synthesis_amd/csrc/bas_occlude.h"
-
-static int g_fail = 0, g_checks = 0;
-
-static void expect(int line, const char *what, int rc, int want, const char *entry) {
-    ++g_checks;
-    const char *text = bas_last_error();
-    bool ok = want > 0 ? rc > 0 : rc == want;
-    if (ok && want != 0) ok = text && strstr(text, entry) != nullptr;      // every failure leaves a text naming the entry
-    if (!ok && ++g_fail <= 40)
-        fprintf(stderr, "hostsan_occlude: FAIL line %d: %s: returned %d, want %s%d, text \"%s\"\n", line, what, rc,
-                want > 0 ? "> " : "", want > 0 ? 0 : want, text ? text : "(null)");
-}
-#define EXPECT(what, call, want, entry) expect(__LINE__, what, (call), (want), entry)
-
-static const int E_NULL = -1, E_SHAPE = -2, E_ALIGN = -3, NO_DEVICE = 1;
-
-template <class T>
-static T *at(uintptr_t base, long bytes) {
-    return reinterpret_cast<T *>(base + bytes);
-}
 
 struct Occluded {
     const double *pos;
@@ -205,12 +181,6 @@ static void reflect_axis(ld L, int i, ld *c, ld *e1, ld *e2) {
     }
 }
 
-static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-static double uniform() {                                                   // xorshift64*, in [0, 1)
-    g_rng ^= g_rng >> 12; g_rng ^= g_rng << 25; g_rng ^= g_rng >> 27;
-    return (double)((g_rng * 0x2545f4914f6cdd1dull) >> 11) / 9007199254740992.0;
-}
-static double between(double a, double b) { return a + (b - a) * uniform(); }
 
 static void note(bool ok, const char *what, int i, double got, double want) {
     ++g_checks;
@@ -370,14 +340,7 @@ static int paths_file(const char *in_path, const char *out_path) {
 }
 
 int main(int argc, char **argv) {
-    int n_dev = 0;
-    const hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e == hipSuccess && n_dev > 0) {
-        printf("hostsan_occlude: refused: %d GPU device(s) visible - sanitized host code never drives a GPU; hide them "
-               "(HIP_VISIBLE_DEVICES=-1)\n", n_dev);
-        return 77;
-    }
-    (void)hipGetLastError();
+    if (hostsan_gpu_visible("hostsan_occlude")) return 77;
     if (argc == 4 && strcmp(argv[1], "paths") == 0) return paths_file(argv[2], argv[3]);
     entry_section();
     const int after_entry = g_checks;

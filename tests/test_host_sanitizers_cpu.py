@@ -16,12 +16,7 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "binaural-audio-synthesis_amd", "csrc")
-OUT = os.path.join(ROOT, "build", "hostsan")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-REFUSED = 77
+from hostsan_support import HIPCC, REFUSED, REPORT, build_program, child_env    # (HIPCC: imported from here too)
 
 # Section a (the plan and size queries over the whole grid) took 8.7 s in the sanitized program on the machine this was
 # written on (profiles/hostsan.json; the slowest of ten runs).  Five times that is its limit: a hang guard - before the
@@ -30,31 +25,18 @@ SECTION_A_SECONDS = 8.7
 SECTION_A_LIMIT = 5 * SECTION_A_SECONDS
 OTHER_LIMIT = 300.0
 
-REPORT = re.compile(r"runtime error:|ERROR: AddressSanitizer|WARNING: ThreadSanitizer|ERROR: LeakSanitizer|"
-                    r"SUMMARY: (UndefinedBehavior|Address|Thread)Sanitizer|==\d+==\s*(ERROR|WARNING)")
-
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc here")
 
 
 @pytest.fixture(scope="module")
 def programs():
     """Both programs, built incrementally (a second run compiles nothing)."""
-    env = dict(os.environ, HIPCC=HIPCC)
-    r = subprocess.run(["make", "-C", CSRC, "-j16", "hostsan"], env=env, capture_output=True, text=True, timeout=3000)
-    assert r.returncode == 0, f"make hostsan failed:\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    paths = {"asan": os.path.join(OUT, "hostsan_asan"), "tsan": os.path.join(OUT, "hostsan_tsan")}
-    for p in paths.values():
-        assert os.access(p, os.X_OK), p
-    return paths
+    return {"asan": build_program("hostsan_asan"), "tsan": build_program("hostsan_tsan")}
 
 
 def run_section(program, section, limit):
-    env = dict(os.environ)
-    env.update(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1",     # no GPU for the child
-               ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
-               TSAN_OPTIONS="halt_on_error=1")
     try:
-        r = subprocess.run([program, section], env=env, capture_output=True, text=True, timeout=limit)
+        r = subprocess.run([program, section], env=child_env(), capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired as e:
         pytest.fail(f"section {section} did not finish within {limit:.1f} s:\n{(e.stdout or b'')[-2000:]}\n{(e.stderr or b'')[-4000:]}")
     tail = f"stdout:\n{r.stdout[-3000:]}\nstderr:\n{r.stderr[-6000:]}"

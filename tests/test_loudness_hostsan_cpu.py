@@ -10,25 +10,18 @@ where a device is visible.  Nothing here loads sanitized code into python, nothi
 """
 import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-from test_host_sanitizers_cpu import CSRC, OUT, HIPCC
-from test_scene_color_hostsan_cpu import run_program
+import hostsan_support
+from hostsan_support import ROOT, HIPCC, run_program
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc here")
 
 
 def build_program():
     """make hostsan_meter; returns the program's path."""
-    env = dict(os.environ, HIPCC=HIPCC)
-    r = subprocess.run(["make", "-C", CSRC, "-j16", "hostsan_meter"], env=env, capture_output=True, text=True, timeout=3000)
-    assert r.returncode == 0, f"make hostsan_meter failed:\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    program = os.path.join(OUT, "hostsan_meter")
-    assert os.access(program, os.X_OK), program
-    return program
+    return hostsan_support.build_program("hostsan_meter")
 
 
 def test_argument_checks_and_the_matrix_powers_of_the_meter():

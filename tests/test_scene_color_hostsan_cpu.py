@@ -10,37 +10,18 @@ nothing sets LD_PRELOAD, nothing runs on a GPU.
 """
 import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-from test_host_sanitizers_cpu import CSRC, OUT, HIPCC, REFUSED, REPORT
+import hostsan_support
+from hostsan_support import ROOT, HIPCC, run_program    # (run_program: imported from here too)
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc here")
-
-CHILD_ENV = dict(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1",      # no GPU for the child
-                 ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 
 
 def build_program():
     """make hostsan_design; returns the program's path."""
-    env = dict(os.environ, HIPCC=HIPCC)
-    r = subprocess.run(["make", "-C", CSRC, "-j16", "hostsan_design"], env=env, capture_output=True, text=True, timeout=3000)
-    assert r.returncode == 0, f"make hostsan_design failed:\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    program = os.path.join(OUT, "hostsan_design")
-    assert os.access(program, os.X_OK), program
-    return program
-
-
-def run_program(program, *args):
-    """The program as a fresh child without a GPU: (CompletedProcess, a tail of its output); sanitizer reports and a
-    refusal fail here."""
-    r = subprocess.run([program, *args], env=dict(os.environ, **CHILD_ENV), capture_output=True, text=True, timeout=300)
-    tail = f"stdout:\n{r.stdout[-3000:]}\nstderr:\n{r.stderr[-6000:]}"
-    assert r.returncode != REFUSED and "refused" not in r.stdout, f"the program saw a GPU and refused to run:\n{tail}"
-    assert not REPORT.search(r.stderr) and not REPORT.search(r.stdout), f"sanitizer report\n{tail}"
-    return r, tail
+    return hostsan_support.build_program("hostsan_design")
 
 
 def test_argument_checks_and_the_filter_function_of_scene_colour():
