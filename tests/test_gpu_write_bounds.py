@@ -1,0 +1,991 @@
+"""No kernel writes outside its outputs or its declared workspace (DESIGN.md "Guard bands"; helper: tests/guards.py).
+
+Every case runs its entry points twice: once with plain aligned buffers of exactly their size (the baseline), once with every
+buffer the library writes inside a patterned arena - outputs with 4 KiB in front and behind, strided rows with 1 .. 7 pattern
+floats between them, workspaces, plan buffers and states of EXACTLY the size their query returns (that size is what the call
+is given) with 1 MiB behind.  Then: the guarded result has the baseline's bits, every guard word is intact, every input is
+unchanged.  Only legal calls are made; the arenas exist so that a real overshoot lands in memory the test owns.
+
+entry point                                   guarded buffers
+--------------------------------------------  ----------------------------------------------------------------------------
+bas_table_pack_f32                            packed (exactly bas_table_packed_floats)
+bas_delay_signal_f32                          y
+bas_ring_interp_f32                           out, delays
+bas_traj_params_f64, _branch_f64              idx, w
+bas_interp2d_f32, _gain_f32                   H (every residue), ws (exactly bas_interp2d_workspace_bytes)
+bas_interp2d_plan_f32, _gain_f32,             plans (exactly bas_interp2d_workspace_bytes; block-staged and wave-staged form)
+  _plan_angles_f32, _plan_angles_gain_f32
+bas_render_mix_f32, _profiled_f32             H (from bas_interp2d_f32), y, peak, ws (exactly bas_render_workspace_bytes)
+bas_render_mix_fused_f32, _profiled_f32,      packed, plans, y (both alignments), peak, ws (exactly
+  bas_render_fused_fir_f32 + _reduce_f32        bas_render_fused_workspace_bytes, control block zeroed)
+bas_render_stream_block_f32, _profiled_f32,   x rows, y, ws, plans, elev / azim / gain rows, last, gain_last, running peak
+  _gain_f32
+bas_stream_epilogue_f32, _gain_f32            x rows, elev / azim / gain rows, last, gain_last, running peak
+bas_stream_batch_epilogue_gain_f32            x rows, elev / azim / gain rows, last, gain_last, peaks
+bas_stream_batch_pack_gain_f32, _delay_f32    x rows, elev_out / azim_out / gain_out rows, raw history rows
+bas_batch_pack_f32, _gain_f32, _delay_f32    x rows, elev_out / azim_out / gain_out
+bas_peak_normalize_f32, bas_scale_by_peak_f32 y, peak
+bas_mix_partials_f32, bas_mix_finish_f32      y, peak, ws (exactly bas_mix_workspace_bytes)
+bas_delay_rows_f32, bas_color_rows_f32        y rows (groups, gaps, every residue)
+bas_delay_carry_f32                           the rows themselves: only row[0, H) may change
+bas_bus_mix_f32                               bus rows
+bas_long_fir_tail_f32                         tail (exactly bas_long_fir_tail_floats)
+bas_long_fir_f32                              out rows (ear and group gaps), peak slice, ws (exactly bas_long_fir_workspace_bytes)
+bas_limit_f32                                 out (planar, sample strides 2 and 4), state records, reduction and peak slices
+bas_meter_f32                                 energy slice, state records, true peak, ws (exactly bas_meter_workspace_bytes)
+bas_ambi_matrices_f32, _encode_gains_f32,     m / e banks, y rows
+  bas_ambi_encode_f32
+bas_head_relative_f64                         elev_out, azim_out rows
+bas_scene_params_f64, _bands_f64,             elev, azim, gain, delay, logmag rows
+  _occluded_f64
+bas_resample_up_f64, bas_delaydiffs_f64       y; diffs, status
+
+Adding a case: write a function of one Run `r` (and its variant's parameters) that takes inputs with r.inp, written buffers
+with r.out / r.rows / r.ws, calls through r.call, and decorate it with @case(name, entry points, variants).
+tests/test_guards_cpu.py fails until every `int bas_*(` of include/bas.h is in a case here, in COVERED_ELSEWHERE (with the
+existing sentinel test) or in NOTHING_TO_WRITE (with the reason).
+"""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+import guards
+import binaural_audio_synthesis_amd as bas
+from binaural_audio_synthesis_amd import limiter, loudness, sphere
+
+pytestmark = pytest.mark.gpu
+
+F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+
+# entry points whose sentinel test already exists: "module::test"
+COVERED_ELSEWHERE = {
+    "bas_batch_finish_f32": "test_gpu_batch_edges.py::test_finish_kernel_bitwise",
+    "bas_stream_batch_pack_f32": "test_gpu_stream_batch.py::test_pack_kernel_bitwise",
+    "bas_stream_batch_epilogue_f32": "test_gpu_stream_batch.py::test_epilogue_kernel_bitwise",
+    "bas_stream_batch_pack_head_f32": "test_gpu_head.py::test_pack_head_kernel_bitwise",
+    "bas_matrix_mix_f32": "test_gpu_ambisonics.py::test_mix_writes_nothing_outside_its_rows",
+    "bas_color_design_f32": "test_gpu_scene_color.py::test_design_kernel_into_strided_views",
+}
+# entry points that return an int and write no device memory
+NOTHING_TO_WRITE = {
+    "bas_version": "returns BAS_ABI_VERSION, takes no buffer",
+    "bas_render_fused_supported": "a pure query of the planner: sizes in, 0 / 1 out",
+    "bas_render_status": "reads the control block of a workspace and clears its error record; the fused cases call it "
+                         "on their exact-size workspace",
+}
+
+CASES = {}          # name -> ((entry points), function, [variants])
+
+
+def case(name, entry_points, variants=((),)):
+    def deco(fn):
+        CASES[name] = (tuple(entry_points), fn, [v if isinstance(v, tuple) else (v,) for v in variants])
+        return fn
+    return deco
+
+
+def P(t):
+    return None if t is None else t.data_ptr()
+
+
+def lib():
+    return bas._hip.lib()
+
+
+class Run:
+    """The buffers of one run of a case: plain and exactly sized (guarded=False) or inside arenas."""
+
+    def __init__(self, guarded, device, dry=False):
+        self.guarded, self.dev, self.dry = guarded, torch.device(device), dry
+        self.outs, self.guards, self.inputs, self.rcs = {}, [], [], []
+        self.stream = None if dry or self.dev.type != "cuda" else bas._hip.current_stream(self.dev)
+
+    def inp(self, name, a, dtype=None):
+        """A read-only input on the device; compared with its copy after the call."""
+        t = torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a)
+        t = (t if dtype is None else t.to(dtype)).to(self.dev).contiguous()
+        self.inputs.append((name, t, t.clone()))
+        return t
+
+    def watch(self, name, t):
+        """A view that the call only reads (a slice of a written buffer's allocation): compared like an input."""
+        self.inputs.append((name, t, t.clone()))
+        return t
+
+    def _done(self, name, t, init, compare):
+        if init is not None:
+            t.copy_(torch.as_tensor(init).to(t.dtype).to(self.dev).reshape(t.shape))
+        self.guards.append((name, t))
+        if compare:
+            assert name not in self.outs, name
+            self.outs[name] = t
+        return t
+
+    def out(self, name, shape, dtype=F32, offset=0, init=None, back=guards.BACK, compare=True, control=False):
+        """A buffer the call writes: the pattern (or `init`) inside, guards around in the guarded run."""
+        if self.guarded:
+            t = guards.arena(shape, dtype, self.dev, guards.FRONT, back, offset, zero_control=control)
+        else:
+            t = guards.arena(shape, dtype, self.dev, 0, 0, 0, zero_control=control)
+        return self._done(name, t, init, compare)
+
+    def ws(self, name, nbytes, control=False, compare=False):
+        """A workspace, plan buffer or state of exactly nbytes, 16-byte aligned, 1 MiB of guard behind."""
+        return self.out(name, int(nbytes), U8, 0, back=guards.WS_BACK, compare=compare, control=control)
+
+    def rows(self, name, n_rows, T, offset=0, groups=None, ears=None, lead=0, init=None, dtype=F32, compare=True,
+             lead_init=None, gap=None):
+        """Strided rows [groups][n_rows][ears][T]: gaps of 1 .. 7 elements (cycling; `gap`: that many) and a base `offset`
+        bytes past a 16-byte boundary in the guarded run, dense and aligned in the baseline."""
+        if self.guarded:
+            t = guards.rows(n_rows, T, gap, offset, dtype, self.dev, groups, ears, None, lead=lead)
+        else:
+            t = guards.rows(n_rows, T, 0, 0, dtype, self.dev, groups, ears, 0, front=0, back=0, lead=lead)
+        if lead:
+            t.lead.copy_(torch.as_tensor(lead_init).to(dtype).to(self.dev).reshape(t.lead.shape))
+        return self._done(name, t, init, compare)
+
+    def strided(self, name, shape, strides, dtype=F32, offset=0, init=None, compare=True, back=guards.BACK):
+        """A view with the layout's own strides in both runs (interleaved frames, a slice of a longer array)."""
+        if self.guarded:
+            t = guards.strided(shape, strides, dtype, self.dev, guards.FRONT, back, offset)
+        else:
+            t = guards.strided(shape, strides, dtype, self.dev, 0, 0, 0)
+        return self._done(name, t, init, compare)
+
+    def call(self, fn, *args):
+        if self.dry:                                     # no device: the argument checks alone (they run before any launch)
+            rc = getattr(lib(), fn)(*args)
+            assert rc >= 0, (fn, rc, lib().bas_last_error().decode())
+            self.rcs.append(rc)
+            return
+        with bas._hip.on_device(self.dev):
+            bas._hip.call(fn, *args)
+
+
+def check(fn, params, device="cuda", dry=False):
+    """The case twice - baseline, guarded - then the three assertions."""
+    runs = []
+    for guarded in (False, True):
+        r = Run(guarded, device, dry)
+        fn(r, *params)
+        if r.dev.type == "cuda":
+            torch.cuda.synchronize()
+        runs.append(r)
+    base, g = runs
+    assert list(base.outs) == list(g.outs) and g.outs, "a case must compare at least one output"
+    for name, t in g.guards:
+        guards.assert_intact(t, f"{name} (guarded run)")
+    for r in runs:
+        for name, t, saved in r.inputs:
+            guards.assert_unchanged(t, saved, f"input {name}")
+    if dry:
+        return
+    for name in g.outs:
+        a, b = base.outs[name], g.outs[name]
+        if not guards.same_bits(a, b):
+            size = a.element_size()
+            ai, bi = a.contiguous().view(guards._INT_OF[size]).reshape(-1), b.contiguous().view(guards._INT_OF[size]).reshape(-1)
+            bad = torch.nonzero(ai != bi).reshape(-1)
+            raise AssertionError(f"{name}: {bad.numel()} of {ai.numel()} elements differ from the baseline, first at {int(bad[0])}")
+
+
+# ---- shared inputs --------------------------------------------------------------------------------------------------------
+_HOST_TABLES = {}
+
+
+def host_table(L, U):
+    if U not in _HOST_TABLES:
+        _HOST_TABLES[U] = bas.synth.make_table("consistent", 0, upsampling=U)
+    return _HOST_TABLES[U].truncated(L)
+
+
+class Table:
+    pass
+
+
+def table(r, L, U, name="packed"):
+    """The synthetic table packed by bas_table_pack_f32 into exactly bas_table_packed_floats floats (guarded)."""
+    h = host_table(L, U)
+    t = Table()
+    t.L, t.U, t.ndir, t.M = L, U, h.irs_left.shape[0], L * U
+    irs = r.inp(name + ".irs", np.stack([h.irs_left, h.irs_right]).astype(np.float32))
+    t.diffs = r.inp(name + ".diffs", np.stack([h.diffs_left, h.diffs_right]).astype(np.float64))
+    n = lib().bas_table_packed_floats(t.ndir, t.M, U)
+    assert n > 0
+    t.packed = r.out(name, n)
+    r.call("bas_table_pack_f32", P(irs), t.ndir, t.M, U, P(t.packed), r.stream)
+    r.watch(name + " (read by the later calls)", t.packed)
+    return t
+
+
+def angles(rng, shape):
+    return rng.uniform(-0.9, 1.6, shape), rng.uniform(-7.0, 7.0, shape)
+
+
+def ring_args(r):
+    """(ring_elev, ring_start, ring_count) host pointers and the node azimuths on the device."""
+    nodes = r.inp("node_az", np.ascontiguousarray(sphere.index_elev_azim[:, 2]).astype(np.float32))
+    return sphere._ring_args(), nodes
+
+
+def wave_staged_from():
+    src = open(os.path.join(ROOT, "binaural-audio-synthesis_amd", "csrc", "bas_interp.hip")).read()
+    return int(re.search(r"#define\s+BAS_PLAN_WAVE_STAGED_FROM\s+(\d+)", src).group(1))
+
+
+# ---- a1, a4, a5, a3 --------------------------------------------------------------------------------------------------------
+@case("table_pack", ["bas_table_pack_f32"], [(5, 1, 8), (5, 2, 3), (3, 7, 6), (7, 5, 4), (187, 100, 8), (4, 129, 5)])
+def table_pack(r, ndir, L, U):
+    M = L * U
+    rng = np.random.default_rng(ndir + L + U)
+    irs = r.inp("irs", rng.standard_normal((2, ndir, M)).astype(np.float32))
+    n = lib().bas_table_packed_floats(ndir, M, U)
+    assert n >= 2 * ndir * U * (L + 4)
+    packed = r.out("packed", n)
+    r.call("bas_table_pack_f32", P(irs), ndir, M, U, P(packed), r.stream)
+
+
+@case("delay_signal", ["bas_delay_signal_f32"], [(n, M, down) for n in (1, 3) for M in (1, 255, 256, 257) for down in (1, 3)])
+def delay_signal(r, n, M, down):
+    rng = np.random.default_rng(n * 1000 + M + down)
+    x = r.inp("x", rng.standard_normal((n, M)).astype(np.float32))
+    s = r.inp("shifts", rng.uniform(-2.0 * M, 2.0 * M, n))
+    y = r.out("y", (n, -(-M // down)), offset=4 * ((n + M + down) % 4))
+    r.call("bas_delay_signal_f32", P(x), P(s), n, M, down, P(y), r.stream)
+
+
+@case("ring_interp", ["bas_ring_interp_f32"], [(n, up) for n in (1, 255, 256, 257) for up in (0, 1)])
+def ring_interp(r, n, up):
+    t = table(r, 33, 8)
+    rng = np.random.default_rng(n + up)
+    pq = r.inp("pq", rng.integers(0, t.ndir, (n, 2)).astype(np.int32))
+    al = r.inp("alpha", rng.random(n))
+    out = r.out("out", (n, 2, t.M if up else t.L), offset=4 * (n % 4))
+    delays = r.out("delays", (n, 2), F64, offset=8 * (n % 2))
+    r.call("bas_ring_interp_f32", P(t.packed), P(t.diffs), P(pq), P(al), n, t.ndir, t.L, t.U, up, P(out), P(delays), r.stream)
+
+
+@case("traj_params", ["bas_traj_params_f64", "bas_traj_params_branch_f64"],
+      [(n, b) for n in (1, 255, 256, 257) for b in (None, 0, 1)])
+def traj_params(r, n, branch):
+    rng = np.random.default_rng(n)
+    e, a = angles(rng, n)
+    elev, azim = r.inp("elev", e), r.inp("azim", a)
+    (re_, rs, rc), nodes = ring_args(r)
+    idx = r.out("idx", (n, 4), I32, offset=4 * (n % 4))
+    w = r.out("w", (n, 3), F64, offset=8 * (n % 2))
+    if branch is None:
+        r.call("bas_traj_params_f64", P(elev), P(azim), n, re_, rs, rc, P(nodes), P(idx), P(w), r.stream)
+    else:
+        r.call("bas_traj_params_branch_f64", P(elev), P(azim), n, re_, rs, rc, P(nodes), P(idx), P(w), branch, r.stream)
+
+
+# ---- a6: chunk IRs and read plans --------------------------------------------------------------------------------------------
+def queries(r, rng, n):
+    e, a = angles(rng, n)
+    idx, w = sphere.interpolation_params_batch(e, a)
+    return r.inp("idx", idx.reshape(-1, 4).astype(np.int32)), r.inp("w", w.reshape(-1, 3).astype(np.float64)), e, a
+
+
+@case("interp2d", ["bas_interp2d_f32", "bas_interp2d_gain_f32"],
+      [(L, U, g) for L in (1, 2, 3, 5, 100, 127, 128, 129, 131) for U in (8, 2) for g in (0, 1)])
+def interp2d(r, L, U, gained):
+    t = table(r, L, U)
+    for n in (1, 3, 4, 5, 9):
+        rng = np.random.default_rng(L * 10 + n)
+        idx, w, _, _ = queries(r, rng, n)
+        H = r.out(f"H{n}", (n, 2, L), offset=4 * ((n + L) % 4))
+        nb = lib().bas_interp2d_workspace_bytes(n)
+        ws = r.ws(f"ws{n}", nb)
+        if gained:
+            gain = r.inp("gain", rng.uniform(-2.0, 2.0, n))
+            r.call("bas_interp2d_gain_f32", P(t.packed), P(t.diffs), P(idx), P(w), P(gain), n, t.ndir, L, U, P(H), P(ws), nb,
+                   r.stream)
+        else:
+            r.call("bas_interp2d_f32", P(t.packed), P(t.diffs), P(idx), P(w), n, t.ndir, L, U, P(H), P(ws), nb, r.stream)
+
+
+PLAN_NS = (1, 63, 127, 128, 129, 32768 + 37)
+
+
+@case("interp2d_plan", ["bas_interp2d_plan_f32", "bas_interp2d_plan_gain_f32", "bas_interp2d_plan_angles_f32",
+                        "bas_interp2d_plan_angles_gain_f32"],
+      [(n, form) for n in PLAN_NS for form in ("params", "params-gain", "angles-f64", "angles-pyfloat", "angles-gain")])
+def interp2d_plan(r, n, form):
+    big = wave_staged_from()
+    assert (n >= big) == (n == PLAN_NS[-1]) and (2 * PLAN_NS[-1]) % 64 != 0       # the wave-staged form, a partial last wave
+    L, U = 128, 8
+    h = host_table(L, U)
+    ndir = h.irs_left.shape[0]
+    diffs = r.inp("diffs", np.stack([h.diffs_left, h.diffs_right]).astype(np.float64))
+    rng = np.random.default_rng(n)
+    idx, w, e, a = queries(r, rng, n)
+    gain = r.inp("gain", rng.uniform(-2.0, 2.0, n))
+    nb = lib().bas_interp2d_workspace_bytes(n)
+    plans = r.ws("plans", nb, compare=True)
+    # (the last 16 bytes of the buffer are its own: not every form writes them, so both runs start from zeros there)
+    plans[nb - 16:].zero_()
+    if form == "params":
+        r.call("bas_interp2d_plan_f32", P(diffs), P(idx), P(w), n, ndir, L, U, P(plans), nb, r.stream)
+    elif form == "params-gain":
+        r.call("bas_interp2d_plan_gain_f32", P(diffs), P(idx), P(w), P(gain), n, ndir, L, U, P(plans), nb, r.stream)
+    else:
+        elev, azim = r.inp("elev", e), r.inp("azim", a)
+        (re_, rs, rc), nodes = ring_args(r)
+        branch = 1 if form == "angles-pyfloat" else 0
+        if form == "angles-gain":
+            r.call("bas_interp2d_plan_angles_gain_f32", P(diffs), P(elev), P(azim), P(gain), n, re_, rs, rc, P(nodes), branch,
+                   ndir, L, U, P(plans), nb, r.stream)
+        else:
+            r.call("bas_interp2d_plan_angles_f32", P(diffs), P(elev), P(azim), n, re_, rs, rc, P(nodes), branch, ndir, L, U,
+                   P(plans), nb, r.stream)
+
+
+# ---- a7: the FIR renders ---------------------------------------------------------------------------------------------------
+_HOST = {}
+
+
+def host_scene(n_src, T_in, K, loud, seed):
+    """x [n_src, T_in rounded up to 4] float32 (the pad zero) and angles [n_src, T_in / K + 1]; loud: the mix passes 1."""
+    key = (n_src, T_in, K, loud, seed)
+    if key not in _HOST:
+        rng = np.random.default_rng(seed)
+        x = np.zeros((n_src, -(-T_in // 4) * 4), np.float32)
+        x[:, :T_in] = rng.standard_normal((n_src, T_in)) * ((8.0 if loud else 0.25) / n_src ** 0.5)
+        _HOST.clear()                                    # (one scene at a time: the big ones are 10 MB)
+        _HOST[key] = (x,) + angles(rng, (n_src, T_in // K + 1))
+    return _HOST[key]
+
+
+_DIAG = []
+
+
+def fused_site(n_src, T_in, K, S, L):
+    """Where the fused render of this shape sums its tiles: the diagnostic build's plan code (a host query)."""
+    if not _DIAG:
+        _DIAG.append(bas._hip._load(bas._hip.DIAG_LIB_PATH))
+        _DIAG[0].bas_debug_fused_plan.argtypes = [ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    code = _DIAG[0].bas_debug_fused_plan(n_src, T_in, K, S, L)
+    assert code & 15, code
+    return "direct" if code & 128 else "wide" if code & 256 else "slab"
+
+
+HD, ROWS32, GENERIC = "bas_render_hd_kernel", "bas_render_rows32_kernel", "bas_render_generic_kernel"
+# n_src, T_in (a few chunks past whole tiles), K, S, L, kernel
+STORED = {
+    "hd": (3, 2 * 2048 + 2 * 512, 512, 4, 128, HD),
+    "hd-multipart": (3, 5000, 200, 40, 100, HD),
+    "hd-L300": (3, 2048 + 3 * 128, 128, 16, 300, HD),
+    "rows32": (3, 2048 + 3 * 64, 64, 32, 128, ROWS32),
+    "generic": (3, 2070, 30, 10, 128, GENERIC),
+}
+
+
+@case("render_mix", ["bas_render_mix_f32", "bas_render_mix_profiled_f32"],
+      [(name, acc, prof) for name in sorted(STORED) for acc in (0, 1) for prof in ((0, 1) if name == "hd" else (0,))])
+def render_mix(r, name, accumulate, profiled):
+    n_src, T_in, K, S, L, kernel = STORED[name]
+    assert lib().bas_render_kernel_name(n_src, T_in, K, S, L).decode() == kernel
+    hx, e, a = host_scene(n_src, T_in, K, False, 11)
+    t = table(r, L, 8)
+    x = r.inp("x", hx)
+    nq = T_in // K + 1
+    n = n_src * nq
+    idx, w = sphere.interpolation_params_batch(e, a)
+    idx, w = r.inp("idx", idx.reshape(-1, 4).astype(np.int32)), r.inp("w", w.reshape(-1, 3).astype(np.float64))
+    H = r.out("H", (n_src, nq, 2, L))
+    pb = lib().bas_interp2d_workspace_bytes(n)
+    r.call("bas_interp2d_f32", P(t.packed), P(t.diffs), P(idx), P(w), n, t.ndir, L, 8, P(H), P(r.ws("ws_interp", pb)), pb, r.stream)
+    r.watch("H (read by the render)", H)
+    T_out = T_in + L - 1
+    for yoff in (0, 4):
+        y0 = np.random.default_rng(5).standard_normal((2, T_out)).astype(np.float32)
+        y = r.out(f"y{yoff}", (2, T_out), offset=yoff, init=y0)
+        peak = r.out(f"peak{yoff}", (1,), init=[0.0])
+        wb = lib().bas_render_workspace_bytes(n_src, T_in, K, S, L)
+        ws = r.ws(f"ws{yoff}", wb, control=True)
+        args = (P(x), x.stride(0), P(H), n_src, T_in, K, S, L, P(y), accumulate, P(peak), P(ws), wb, r.stream)
+        if profiled:
+            r.call("bas_render_mix_profiled_f32", *args, None, None)
+        else:
+            r.call("bas_render_mix_f32", *args)
+
+
+FQ, FS128, FS104, FS0 = "bas_render_fq_kernel", "bas_render_fs_kernel<128>", "bas_render_fs_kernel<104>", "bas_render_fs_kernel<0>"
+T8 = 4 * 8192 + 3 * 512
+# n_src, T_in, K, S, L, kernel, where the tiles are summed
+FUSED = {
+    "fq-direct": (1, 2 * 2048 + 512, 512, 32, 128, FQ, "direct"),
+    "fq-slab": (3, 2 * 2048 + 512, 512, 32, 128, FQ, "slab"),
+    "fq-wide": (40, 2 * 2048 + 512, 512, 32, 128, FQ, "wide"),
+    "fs128": (96, T8, 512, 32, 128, FS128, "wide"),
+    "fs128-slab": (64, 8 * 8192 + 3 * 512, 512, 32, 128, FS128, "slab"),
+    "fs104": (96, T8, 512, 32, 100, FS104, "wide"),
+    "fs0": (96, T8, 512, 32, 300, FS0, "wide"),
+    "fs128-2": (96, T8, 512, 16, 128, "bas_render_fs_kernel<128,2>", "wide"),
+    "fs128-4": (96, T8, 512, 8, 128, "bas_render_fs_kernel<128,4>", "wide"),
+    "fz40": (96, 77 * 448, 448, 32, 128, "bas_render_fz_kernel<4,0>", "wide"),
+    "fz41": (256, 8192 + 3 * 256, 256, 32, 300, "bas_render_fz_kernel<4,1>", "wide"),
+    "fz10": (1024, 2048 + 512, 512, 32, 100, "bas_render_fz_kernel<1,0>", "wide"),
+}
+
+
+def fused_plans(r, t, e, a, gain=None):
+    """The read plans of a scene's angles, in a plan buffer of exactly bas_interp2d_workspace_bytes."""
+    n = e.size
+    elev, azim = r.inp("elev", e.reshape(-1)), r.inp("azim", a.reshape(-1))
+    (re_, rs, rc), nodes = ring_args(r)
+    pb = lib().bas_interp2d_workspace_bytes(n)
+    plans = r.ws("plans", pb)
+    if gain is None:
+        r.call("bas_interp2d_plan_angles_f32", P(t.diffs), P(elev), P(azim), n, re_, rs, rc, P(nodes), 0, t.ndir, t.L, t.U,
+               P(plans), pb, r.stream)
+    else:
+        r.call("bas_interp2d_plan_angles_gain_f32", P(t.diffs), P(elev), P(azim), P(gain), n, re_, rs, rc, P(nodes), 0, t.ndir,
+               t.L, t.U, P(plans), pb, r.stream)
+    r.watch("plans (read by the render)", plans)
+    return plans
+
+
+@case("render_fused", ["bas_render_mix_fused_f32", "bas_render_mix_fused_profiled_f32", "bas_render_fused_fir_f32",
+                       "bas_render_fused_reduce_f32"],
+      [(name, form) for name in sorted(FUSED) for form in (("one", "two", "profiled") if name == "fq-wide" else ("one", "two"))])
+def render_fused(r, name, form):
+    n_src, T_in, K, S, L, kernel, site = FUSED[name]
+    shape = (n_src, T_in, K, S, L)
+    assert lib().bas_render_fused_supported(*shape) == 1
+    assert lib().bas_render_fused_kernel_name(*shape).decode() == kernel and fused_site(*shape) == site
+    hx, e, a = host_scene(n_src, T_in, K, True, 12)
+    t = table(r, L, 8)
+    x = r.inp("x", hx)
+    plans = fused_plans(r, t, e, a)
+    T_out = T_in + L - 1
+    wb = lib().bas_render_fused_workspace_bytes(*shape)
+    for normalize in (0, 1):
+        for yoff in (0, 4):                              # aligned: the rule rides in the kernel tail; else bas_scale_by_peak_f32
+            tag = f"{normalize}{yoff}"
+            y = r.out("y" + tag, (2, T_out), offset=yoff)
+            peak = r.out("peak" + tag, (1,), init=[0.0])
+            ws = r.ws("ws" + tag, wb, control=True)
+            args = (P(x), x.stride(0), P(t.packed), P(plans), n_src, T_in, K, S, L, t.U, t.ndir, P(y), 0, P(peak), normalize,
+                    P(ws), wb, r.stream)
+            if form == "one":
+                r.call("bas_render_mix_fused_f32", *args)
+            elif form == "profiled":
+                r.call("bas_render_mix_fused_profiled_f32", *args, None, None)
+            else:
+                r.call("bas_render_fused_fir_f32", *args)
+                r.call("bas_render_fused_reduce_f32", *args)
+            r.call("bas_render_status", P(ws), wb, r.stream)
+            if not r.dry:
+                assert float(peak[0]) > 1.0 and float(y.abs().max()) <= (1.0 if normalize else float(peak[0])), tag
+
+
+# ---- streams: one block in one call, the carried state ------------------------------------------------------------------
+STREAM_BLOCKS = {"direct": 1, "slab": 3, "wide": 40}
+
+
+@case("render_stream_block", ["bas_render_stream_block_f32", "bas_render_stream_block_profiled_f32",
+                              "bas_render_stream_block_gain_f32"],
+      [(site, form) for site in sorted(STREAM_BLOCKS) for form in ("plain", "gain")] + [("wide", "profiled")])
+def render_stream_block(r, site, form):
+    n_src, K, S, L, halo, B = STREAM_BLOCKS[site], 512, 32, 128, 512, 4096
+    T_in = halo + B
+    shape = (n_src, T_in, K, S, L)
+    assert lib().bas_render_fused_kernel_name(*shape).decode() == FQ and fused_site(*shape) == site
+    nh, nb = halo // K, B // K + 1
+    hx, e, a = host_scene(n_src, T_in, K, False, 13)
+    rng = np.random.default_rng(14)
+    g = rng.uniform(0.5, 1.5, e.shape)
+    t = table(r, L, 8)
+    gain_in = r.inp("gain_in", g.reshape(-1)) if form == "gain" else None
+    plans = fused_plans(r, t, e, a, gain_in)
+    x = r.rows("x", n_src, T_in, gap=4 if r.guarded else 0, init=hx[:, :T_in])
+    assert x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
+    elev = r.rows("elev", n_src, nh + nb, dtype=F64, init=e)
+    azim = r.rows("azim", n_src, nh + nb, dtype=F64, init=a, gap=elev.stride(0) - (nh + nb))
+    gain = r.rows("gain", n_src, nh + nb, dtype=F64, init=g, gap=elev.stride(0) - (nh + nb))
+    T_out = T_in + L - 1
+    y = r.out("y", (2, T_out))
+    last = r.out("last", (2, n_src), F64)
+    gain_last = r.out("gain_last", (n_src,), F64, init=np.zeros(n_src))
+    rpeak = r.out("running_peak", (1,), init=[0.001])
+    wb = lib().bas_render_fused_workspace_bytes(*shape)
+    ws = r.ws("ws", wb, control=True)
+    head = (P(x), x.stride(0), P(t.packed), P(plans), n_src, T_in, K, S, L, t.U, t.ndir, P(y), P(ws), wb, halo, P(elev), P(azim))
+    if form == "gain":
+        r.call("bas_render_stream_block_gain_f32", *head, P(gain), elev.stride(0), nh, nb, P(last), P(gain_last), P(rpeak), r.stream)
+    elif form == "profiled":
+        r.call("bas_render_stream_block_profiled_f32", *head, elev.stride(0), nh, nb, P(last), P(rpeak), r.stream, None, None)
+    else:
+        r.call("bas_render_stream_block_f32", *head, elev.stride(0), nh, nb, P(last), P(rpeak), r.stream)
+
+
+EPILOGUES = [(2, 512, 512, 512), (3, 96, 384, 96), (2, 6, 12, 18), (2, 512, 0, 1024), (1, 448, 896, 896)]
+
+
+@case("stream_epilogue", ["bas_stream_epilogue_f32", "bas_stream_epilogue_gain_f32"],
+      [c + (g,) for c in EPILOGUES for g in (0, 1)])
+def stream_epilogue(r, n_src, K, halo, B, gained):
+    nh, nb = halo // K, B // K + 1
+    rng = np.random.default_rng(n_src + K + halo)
+    x = r.rows("x", n_src, halo + B, offset=4 * (K % 4), init=rng.standard_normal((n_src, halo + B)))
+    ang = rng.standard_normal((3, n_src, nh + nb))
+    elev = r.rows("elev", n_src, nh + nb, dtype=F64, init=ang[0])
+    gap = elev.stride(0) - (nh + nb)
+    azim = r.rows("azim", n_src, nh + nb, dtype=F64, init=ang[1], gap=gap)
+    gain = r.rows("gain", n_src, nh + nb, dtype=F64, init=ang[2], gap=gap)
+    y = r.inp("y", rng.standard_normal((2, halo + B + 7)).astype(np.float32))
+    last = r.out("last", (2, n_src), F64)
+    gain_last = r.out("gain_last", (n_src,), F64, init=np.zeros(n_src))
+    rpeak = r.out("running_peak", (1,), init=[0.25])
+    if gained:
+        r.call("bas_stream_epilogue_gain_f32", P(x), x.stride(0), n_src, halo, B, P(elev), P(azim), P(gain), elev.stride(0), nh,
+               nb, P(last), P(gain_last), P(y), y.stride(0), P(rpeak), r.stream)
+    else:
+        r.call("bas_stream_epilogue_f32", P(x), x.stride(0), n_src, halo, B, P(elev), P(azim), elev.stride(0), nh, nb, P(last),
+               P(y), y.stride(0), P(rpeak), r.stream)
+
+
+@case("stream_batch_epilogue_gain", ["bas_stream_batch_epilogue_gain_f32"],
+      [(3, 2, 512, 512, 512), (4, 3, 96, 384, 96), (2, 2, 6, 12, 18), (3, 2, 512, 0, 1024)])
+def stream_batch_epilogue_gain(r, G, n_src, K, halo, B):
+    W, nh, nb = halo + B + K, halo // K, B // K + 1
+    T_in, Q = G * W - K, G * (nh + nb)
+    rng = np.random.default_rng(G + K + halo)
+    x = r.rows("x", n_src, T_in, offset=4 * (G % 4), init=rng.standard_normal((n_src, T_in)))
+    ang = rng.standard_normal((3, n_src, Q))
+    elev = r.rows("elev", n_src, Q, dtype=F64, init=ang[0])
+    gap = elev.stride(0) - Q
+    azim = r.rows("azim", n_src, Q, dtype=F64, init=ang[1], gap=gap)
+    gain = r.rows("gain", n_src, Q, dtype=F64, init=ang[2], gap=gap)
+    y = r.inp("y", rng.standard_normal((2, T_in + 7)).astype(np.float32))
+    last = r.out("last", (G, 2, n_src), F64)
+    gain_last = r.out("gain_last", (G, n_src), F64)
+    peaks = r.out("peaks", (G,), init=np.abs(rng.standard_normal(G)))
+    r.call("bas_stream_batch_epilogue_gain_f32", P(x), x.stride(0), G, n_src, halo, B, K, P(elev), P(azim), P(gain),
+           elev.stride(0), P(last), P(gain_last), P(y), y.stride(0), P(peaks), r.stream)
+
+
+@case("stream_batch_pack", ["bas_stream_batch_pack_gain_f32", "bas_stream_batch_pack_delay_f32"],
+      [c + (f,) for c in [(3, 2, 512, 512, 512), (5, 3, 6, 12, 18), (4, 1, 96, 384, 96), (2, 4, 512, 0, 1024), (2, 3, 8, 8, 16)]
+       for f in ("gain", "gain-head", "delay-linear", "delay-cubic-head")])
+def stream_batch_pack(r, G, n_src, K, halo, B, form):
+    W, nh, nb = halo + B + K, halo // K, B // K + 1
+    T_in, Q = G * W - K, G * (nh + nb)
+    rng = np.random.default_rng(G * 100 + K)
+    blocks = r.inp("blocks", rng.standard_normal((G, n_src, B)).astype(np.float32))
+    ang = rng.standard_normal((3, G, n_src, nb))
+    e, a, g = r.inp("elev", ang[0]), r.inp("azim", ang[1]), r.inp("gain", ang[2])
+    head = r.inp("head", rng.standard_normal((G, nb, 4))) if "head" in form else None
+    x = r.rows("x", n_src, T_in, offset=4 * ((G + K) % 4), init=rng.standard_normal((n_src, T_in)))
+    out0 = rng.standard_normal((3, n_src, Q))
+    eo = r.rows("elev_out", n_src, Q, dtype=F64, init=out0[0])
+    gap = eo.stride(0) - Q
+    ao = r.rows("azim_out", n_src, Q, dtype=F64, init=out0[1], gap=gap)
+    go = r.rows("gain_out", n_src, Q, dtype=F64, init=out0[2], gap=gap)
+    if form.startswith("gain"):
+        r.call("bas_stream_batch_pack_gain_f32", P(blocks), P(e), P(a), P(head), P(g), G, n_src, B, K, halo, P(x), x.stride(0),
+               P(eo), P(ao), P(go), eo.stride(0), r.stream)
+        return
+    interp = 1 if "cubic" in form else 0
+    Hh = 40
+    delay = r.inp("delay", rng.uniform(0.0, 50.0, (G, n_src, nb)))
+    raw = r.rows("raw", n_src, Hh + B, groups=G, init=rng.standard_normal((G, n_src, Hh + B)))
+    r.call("bas_stream_batch_pack_delay_f32", P(blocks), P(e), P(a), P(head), P(g), P(delay), interp, float(Hh - 2), P(raw),
+           raw.stride(0), raw.stride(1), Hh, G, n_src, B, K, halo, P(x), x.stride(0), P(eo), P(ao), P(go), eo.stride(0), r.stream)
+
+
+@case("batch_pack", ["bas_batch_pack_f32", "bas_batch_pack_gain_f32", "bas_batch_pack_delay_f32"],
+      [(K, L, f) for K, L in ((3, 100), (75, 128), (512, 128), (5, 1)) for f in ("plain", "gain", "delay-linear", "delay-cubic")])
+def batch_pack(r, K, L, form):
+    from binaural_audio_synthesis_amd import batch
+    lengths = np.array([0, 1, K - 1, K, K + 1, 2 * K + 3, 1, 0])
+    lay = batch.plan_layout(lengths, K, K, L)
+    n_items, n_src, N = len(lengths), 3, 2 * K + 3
+    n_q_max = -(-N // K) + 2
+    rng = np.random.default_rng(K + L)
+    sig = r.inp("sig", (rng.standard_normal((n_items, n_src, N)) + 1.0).astype(np.float32))
+    meta = r.inp("meta", np.stack([lay.lengths, lay.offsets]).astype(np.int64))
+    ang = rng.standard_normal((3, n_items, n_src, n_q_max))
+    e, a, g = r.inp("elev", ang[0]), r.inp("azim", ang[1]), r.inp("gain", ang[2])
+    x_stride = -(-lay.T_in // 4) * 4 + 4
+    x = r.out("x", (n_src, x_stride))
+    nq = lay.T_in // K + 1
+    assert nq == lay.n_q
+    eo, ao = r.out("elev_out", (n_src, nq), F64), r.out("azim_out", (n_src, nq), F64)
+    go = r.out("gain_out", (n_src, nq), F64, init=np.zeros((n_src, nq)))
+    if form == "plain":
+        r.call("bas_batch_pack_f32", P(sig), n_items, n_src, N, P(meta[0]), P(meta[1]), P(e), P(a), n_q_max, K, lay.T_in, P(x),
+               x_stride, P(eo), P(ao), r.stream)
+    elif form == "gain":
+        r.call("bas_batch_pack_gain_f32", P(sig), n_items, n_src, N, P(meta[0]), P(meta[1]), P(e), P(a), P(g), n_q_max, K,
+               lay.T_in, P(x), x_stride, P(eo), P(ao), P(go), r.stream)
+    else:
+        delay = r.inp("delay", rng.uniform(0.0, 2.0 * K, (n_items, n_src, n_q_max)))
+        r.call("bas_batch_pack_delay_f32", P(sig), n_items, n_src, N, P(meta[0]), P(meta[1]), P(e), P(a), P(g), P(delay),
+               1 if "cubic" in form else 0, n_q_max, K, lay.T_in, P(x), x_stride, P(eo), P(ao), P(go), r.stream)
+
+
+# ---- peak rule and the multi-GPU combine -----------------------------------------------------------------------------------
+FLAT_NS = (1, 2, 3, 4, 5, 7, 1023, 1024, 1025, 1027, 70001, 70002)
+
+
+@case("peak_rule", ["bas_peak_normalize_f32", "bas_scale_by_peak_f32"], [(n,) for n in FLAT_NS])
+def peak_rule(r, n):
+    rng = np.random.default_rng(n)
+    y0 = (rng.standard_normal(n) * 3.0).astype(np.float32)
+    known = r.inp("known peak", np.array([2.5], np.float32))
+    for res in range(4):
+        for apply in (0, 1):
+            y = r.out(f"y{res}{apply}", (n,), offset=4 * res, init=y0)
+            peak = r.out(f"peak{res}{apply}", (1,), init=[0.0])
+            r.call("bas_peak_normalize_f32", P(y), n, P(peak), apply, r.stream)
+        y = r.out(f"scaled{res}", (n,), offset=4 * res, init=y0)
+        r.call("bas_scale_by_peak_f32", P(y), n, P(known), r.stream)
+
+
+@case("mix_partials", ["bas_mix_partials_f32", "bas_mix_finish_f32"], [(n,) for n in FLAT_NS])
+def mix_partials(r, n):
+    rng = np.random.default_rng(n + 1)
+    n_parts, stride = 3, n + 5
+    parts = r.inp("parts", rng.standard_normal((n_parts, stride)).astype(np.float32))
+    for res in range(4):
+        y = r.out(f"y{res}", (n,), offset=4 * res)
+        peak = r.out(f"peak{res}", (1,), init=[0.0])
+        r.call("bas_mix_partials_f32", P(parts), n_parts, stride, n, P(y), P(peak), r.stream)
+    wb = lib().bas_mix_workspace_bytes()
+    for normalize in (0, 1):
+        y = r.out(f"finish{normalize}", (n,))
+        peak = r.out(f"finish peak{normalize}", (1,), init=[0.0])
+        ws = r.ws(f"ws{normalize}", wb, control=True)
+        r.call("bas_mix_finish_f32", P(parts), n_parts, stride, n, P(y), P(peak), normalize, P(ws), wb, r.stream)
+
+
+# ---- row primitives ------------------------------------------------------------------------------------------------------------
+ROW_TS = (1, 2, 3, 4, 5, 7, 1023, 1024, 1025, 1027)
+
+
+def ragged(rng, n, T):
+    lengths = rng.integers(0, T + 1, n)
+    lengths[0] = T
+    return lengths.astype(np.int64)
+
+
+@case("delay_rows", ["bas_delay_rows_f32"], [(i, h, rg) for i in (0, 1) for h in (0, 16) for rg in (0, 1)])
+def delay_rows(r, interp, Hh, use_lengths):
+    G, n_src, K = 2, 3, 64
+    for T in ROW_TS:
+        rng = np.random.default_rng(T + interp)
+        nbnd = (T - 1) // K + 2
+        xs = Hh + T + 3
+        x = r.inp("x", rng.standard_normal((G, n_src, xs)).astype(np.float32))
+        delay = r.inp("delay", rng.uniform(0.0, 20.0, (G, n_src, nbnd)))
+        lengths = r.inp("lengths", ragged(rng, G * n_src, T)) if use_lengths else None
+        for res in range(4):
+            y = r.rows(f"y{T}_{res}", n_src, T, offset=4 * res, groups=G)
+            r.call("bas_delay_rows_f32", P(x) + 4 * Hh, x.stride(0), x.stride(1), Hh, P(lengths), P(delay), delay.stride(0),
+                   delay.stride(1), G, n_src, T, K, interp, float(Hh - 2) if Hh else 0.0, P(y), y.stride(0), y.stride(1), r.stream)
+
+
+@case("delay_carry", ["bas_delay_carry_f32"], [(300, 100), (300, 300), (300, 700), (256, 512), (1, 1), (255, 257), (257, 3)])
+def delay_carry(r, Hh, B):
+    G, n_src = 2, 3
+    rng = np.random.default_rng(Hh + B)
+    x0 = rng.standard_normal((G, n_src, Hh + B)).astype(np.float32)
+    for res in range(4):
+        x = r.rows(f"x{res}", n_src, Hh + B, offset=4 * res, groups=G, init=x0)
+        r.call("bas_delay_carry_f32", P(x), x.stride(0), x.stride(1), G, n_src, Hh, B, r.stream)
+        if not r.dry:                                    # only row[0, H) may change
+            assert torch.equal(x[..., Hh:].cpu(), torch.from_numpy(x0[..., Hh:])), (Hh, B, res)
+            assert torch.equal(x[..., :Hh].cpu(), torch.from_numpy(x0[..., B:B + Hh])), (Hh, B, res)
+
+
+@case("color_rows", ["bas_color_rows_f32"], [(M, st, rg) for M in (1, 5, 64) for st in (0, 1) for rg in (0, 1)])
+def color_rows(r, M, static, use_lengths):
+    G, n_src, K = 2, 3, 64
+    Hc = M - 1 if static else 0
+    for T in ROW_TS:
+        rng = np.random.default_rng(T + M)
+        nbnd = (T - 1) // K + 2
+        x = r.inp("x", rng.standard_normal((G, n_src, Hc + T + 3)).astype(np.float32))
+        color = r.inp("color", rng.standard_normal((G, n_src, 1 if static else nbnd, M)).astype(np.float32))
+        lengths = r.inp("lengths", ragged(rng, G * n_src, T)) if use_lengths else None
+        for res in range(4):
+            y = r.rows(f"y{T}_{res}", n_src, T, offset=4 * res, groups=G)
+            r.call("bas_color_rows_f32", P(x) + 4 * Hc, x.stride(0), x.stride(1), Hc, P(lengths), P(color), color.stride(0),
+                   color.stride(1), 0 if static else color.stride(2), M, G, n_src, T, K, P(y), y.stride(0), y.stride(1), r.stream)
+
+
+@case("bus_mix", ["bas_bus_mix_f32"], [(st, n_src) for st in (0, 1) for n_src in (1, 5)])
+def bus_mix(r, static, n_src):
+    G, K = 3, 30
+    for T in ROW_TS:
+        rng = np.random.default_rng(T + n_src)
+        nbnd = (T - 1) // K + 2
+        x = r.inp("x", rng.standard_normal((G, n_src, T + (T % 3))).astype(np.float32))
+        send = r.inp("send", rng.standard_normal((G, n_src, 1 if static else nbnd)))
+        for res in range(4):
+            bus = r.rows(f"bus{T}_{res}", G, T, offset=4 * res)
+            r.call("bas_bus_mix_f32", P(x), x.stride(0), x.stride(1), P(send), send.stride(0), send.stride(1),
+                   0 if static else 1, G, n_src, T, K, P(bus), bus.stride(0), r.stream)
+
+
+# ---- late reverberation ----------------------------------------------------------------------------------------------------
+def reverb_tail(r, Lr, Np, name="tail"):
+    rng = np.random.default_rng(Lr + Np)
+    h = r.inp(name + ".h", (rng.standard_normal((2, Lr + 3)) / Lr ** 0.5).astype(np.float32))
+    n = lib().bas_long_fir_tail_floats(Lr, Np)
+    assert n > 0
+    tail = r.out(name, (n,))
+    r.call("bas_long_fir_tail_f32", P(h), h.stride(0), Lr, Np, P(tail), r.stream)
+    return tail
+
+
+@case("long_fir_tail", ["bas_long_fir_tail_f32"], [(Lr, Np) for Np in (32, 512) for Lr in (1, Np - 1, Np, Np + 1)])
+def long_fir_tail(r, Lr, Np):
+    reverb_tail(r, Lr, Np)
+
+
+@case("long_fir", ["bas_long_fir_f32"],
+      [(32, 33, 2 * 32 + 5, 0), (32, 100, 5 * 32 + 7, 17), (32, 31, 9 * 32 + 1, 0), (512, 513, 512 + 100, 0),
+       (512, 700, 11 * 512 + 3, 40), (128, 1, 3 * 128 + 127, 5)])
+def long_fir(r, Np, Lr, T_out, Hb):
+    F = -(-T_out // Np)
+    assert T_out % Np and F % 8                          # a partial last frame; F < 4 and F >= 4 over the variants
+    n_bus, lag = 2, 3
+    tail = reverb_tail(r, Lr, Np)
+    r.watch("tail (read by the convolver)", tail)
+    rng = np.random.default_rng(T_out)
+    T_bus = T_out - 10 if T_out > 20 else T_out
+    bus = r.inp("bus", rng.standard_normal((n_bus, Hb + T_bus + 2)).astype(np.float32))
+    y_in = r.inp("y_in", rng.standard_normal((n_bus, 2, T_out)).astype(np.float32))
+    wb = lib().bas_long_fir_workspace_bytes(n_bus, T_out, Lr, Np)
+    assert wb > 0
+    for res, with_y in ((0, 1), (1, 0), (2, 1), (3, 0)):
+        out = r.rows(f"out{res}", 2, T_out, offset=4 * res, groups=n_bus)
+        peaks = r.out(f"peaks{res}", (n_bus + 4,), init=np.full(n_bus + 4, 0.125))
+        ws = r.ws(f"ws{res}", wb)
+        r.call("bas_long_fir_f32", P(bus) + 4 * Hb, bus.stride(0), Hb, T_bus, n_bus, P(tail), Lr, Np, lag,
+               P(y_in) if with_y else None, y_in.stride(0), y_in.stride(1), T_out, P(out), out.stride(0), out.stride(1), T_out,
+               P(peaks) + 8, P(ws), wb, r.stream)
+        if not r.dry:
+            p = peaks.cpu()
+            assert float(p[:2].min()) == float(p[:2].max()) == 0.125 == float(p[2 + n_bus:].min()) == float(p[2 + n_bus:].max())
+
+
+# ---- limiter and meter -------------------------------------------------------------------------------------------------------
+def out_layout(r, name, layout, G, T):
+    """The limiter's output [G][T][2] as (tensor, strides g / t / e): planar rows with gaps, or frames of 2 or 4 floats."""
+    if layout == "planar":
+        t = r.rows(name, 2, T, groups=G, offset=4)       # [G][2][T]
+        return t, (t.stride(0), 1, t.stride(1)), t.permute(0, 2, 1)
+    w = 2 if layout == "stride2" else 4
+    t = r.strided(name, (G, T, 2), (T * w + 3, w, 1), offset=8)
+    return t, t.stride(), t
+
+
+@case("limit", ["bas_limit_f32"],
+      [(layout, T, A, st) for layout in ("planar", "stride2", "stride4") for T in (1, 1023, 1024, 1025, 3000)
+       for A, st in ((0, 1), (63, 1), (1024, 1), (63, 0))])
+def limit(r, layout, T, A, streamed):
+    G, hold = 3, 5
+    assert limiter.TILE == 1024
+    rng = np.random.default_rng(T + A)
+    y = r.inp("y", rng.standard_normal((G, T, 2)).astype(np.float32))
+    out, (sg, st, se), _ = out_layout(r, "out", layout, G, T)
+    red = r.out("reduction", (G + 4,), init=np.ones(G + 4))
+    peak = r.out("peak", (G + 4,), init=np.zeros(G + 4))
+    state, stride = None, 0
+    if streamed:
+        n = lib().bas_limit_state_floats(A, hold)
+        assert n > 0
+        stride = -(-n // 4) * 4
+        state = r.out("state", (G * stride,), init=np.zeros(G * stride), back=guards.WS_BACK)
+    r.call("bas_limit_f32", P(y), y.stride(0), y.stride(1), y.stride(2), P(out), sg, st, se, G, T, T, 0.5, A, hold, P(state),
+           stride, P(red) + 8, P(peak) + 8, r.stream)
+    if not r.dry:
+        rc, pc = red.cpu(), peak.cpu()
+        assert bool((rc[:2] == 1).all()) and bool((rc[2 + G:] == 1).all()) and bool((pc[:2] == 0).all()) and bool((pc[2 + G:] == 0).all())
+        assert float(pc[2:2 + G].max()) <= 0.5 and float(rc[2:2 + G].max()) <= 1.0
+
+
+@case("meter", ["bas_meter_f32"],
+      [(G, T, st) for G in (1, 3) for T in (1, 799, 800, 801, 802, 2500) for st in (0, 1)])
+def meter(r, G, T, streamed):
+    fs, hop = 8000, 800
+    rng = np.random.default_rng(G + T)
+    y = r.inp("y", rng.standard_normal((G, T, 2)).astype(np.float32))
+    max_hops = T // hop + 1
+    energy = r.strided("energy", (G, 2, max_hops), (2 * (max_hops + 3) + 1, max_hops + 3, 1), F64, offset=8,
+                       init=np.zeros((G, 2, max_hops)))
+    wb = lib().bas_meter_workspace_bytes(G, T, hop)
+    assert (wb > 0) == (T > hop + 1)                     # one launch up to hop + 1 samples, three and a workspace beyond
+    ws = r.ws("ws", wb) if wb else None
+    state, stride, tp = None, 0, None
+    if streamed:
+        n = lib().bas_meter_state_doubles()
+        stride = n + (n % 2)
+        state = r.out("state", (G * stride,), F64, init=np.zeros(G * stride), back=guards.WS_BACK)
+    else:
+        tp = r.out("true_peak", (G, 2), init=np.zeros((G, 2)))
+    taps = loudness._taps_host()
+    r.call("bas_meter_f32", P(y), y.stride(0), y.stride(1), y.stride(2), G, T, fs, hop, taps.ctypes.data, P(energy),
+           energy.stride(0), energy.stride(1), max_hops, 0, P(state), stride, P(tp), P(ws), wb, r.stream)
+
+
+# ---- ambisonics, head tracking ---------------------------------------------------------------------------------------------
+@case("ambi_matrices", ["bas_ambi_matrices_f32"], [(1, 5, 1, 1), (2, 7, 3, 4), (3, 64, 2, 9)])
+def ambi_matrices(r, order, V, G, nb):
+    C, J = (order + 1) ** 2, 20
+    rng = np.random.default_rng(order + V)
+    head = r.inp("head", rng.standard_normal((G, nb, 5)))
+    D, Q = r.inp("D", rng.standard_normal((V, C))), r.inp("Q", rng.standard_normal((J, C)))
+    S = rng.standard_normal((J, 3))
+    S = r.inp("S", S / np.linalg.norm(S, axis=1, keepdims=True))
+    m = r.rows("m", nb, V * C, offset=4 * (V % 4), groups=G)
+    r.call("bas_ambi_matrices_f32", P(head), head.stride(0), head.stride(1), P(D), P(Q), P(S), J, order, V, G, nb, P(m),
+           m.stride(0), m.stride(1), r.stream)
+
+
+@case("ambi_encode_gains", ["bas_ambi_encode_gains_f32"], [(1, 1, 1, 1), (2, 5, 2, 3), (3, 40, 2, 4)])
+def ambi_encode_gains(r, order, n_src, G, nb):
+    C = (order + 1) ** 2
+    rng = np.random.default_rng(order + n_src)
+    e, a = angles(rng, (G, n_src, nb + 2))
+    elev, azim = r.inp("elev", e), r.inp("azim", a)
+    gain = r.inp("gain", rng.uniform(-2, 2, (G, n_src, nb)))
+    scale = (ctypes.c_double * (order + 1))(*[1.0 / (2 * l + 1) ** 0.5 for l in range(order + 1)])
+    bank = r.rows("e", nb, n_src * C, offset=4 * (n_src % 4), groups=G)
+    r.call("bas_ambi_encode_gains_f32", P(elev), P(azim), elev.stride(0), elev.stride(1), P(gain), gain.stride(0), gain.stride(1),
+           ctypes.addressof(scale), order, G, n_src, nb, P(bank), bank.stride(0), bank.stride(1), r.stream)
+
+
+@case("ambi_encode", ["bas_ambi_encode_f32"], [(4, 3, st, b) for st in (0, 1) for b in (0, 1)] + [(9, 40, 0, 0), (16, 70, 1, 1)])
+def ambi_encode(r, C, n_src, static, with_base):
+    G, K = 2, 64
+    for T in (1, 5, 1023, 1027, 2500):
+        rng = np.random.default_rng(T + C)
+        nbnd = (T - 1) // K + 2
+        x = r.inp("x", rng.standard_normal((G, n_src, T + 1)).astype(np.float32))
+        bank = r.inp("e", rng.standard_normal((G, 1 if static else nbnd, n_src * C)).astype(np.float32))
+        base = r.inp("base", rng.standard_normal((G, C, T)).astype(np.float32)) if with_base else None
+        for res in range(4):
+            y = r.rows(f"y{T}_{res}", C, T, offset=4 * res, groups=G)
+            r.call("bas_ambi_encode_f32", P(x), x.stride(0), x.stride(1), P(bank), bank.stride(0), 0 if static else bank.stride(1),
+                   n_src, C, G, T, K, P(base), base.stride(0) if with_base else 0, base.stride(1) if with_base else 0, P(y),
+                   y.stride(0), y.stride(1), r.stream)
+
+
+@case("head_relative", ["bas_head_relative_f64"], [(1, 1, 1), (3, 2, 9), (2, 5, 257)])
+def head_relative(r, G, n_src, nb):
+    rng = np.random.default_rng(G + nb)
+    e, a = angles(rng, (G, n_src, nb + 1))
+    elev, azim = r.inp("elev", e), r.inp("azim", a)
+    head = rng.standard_normal((G, nb, 6))
+    head[0, 0, 1:3] = 0.0                                # a pure yaw
+    head = r.inp("head", head)
+    eo = r.rows("elev_out", n_src, nb, dtype=F64, offset=8, groups=G)
+    ao = r.rows("azim_out", n_src, nb, dtype=F64, groups=G, gap=eo.stride(1) - nb)
+    assert ao.stride() == eo.stride()
+    r.call("bas_head_relative_f64", P(elev), P(azim), elev.stride(0), elev.stride(1), P(head), head.stride(0), head.stride(1),
+           G, n_src, nb, P(eo), P(ao), eo.stride(0), eo.stride(1), r.stream)
+
+
+# ---- Cartesian scenes ------------------------------------------------------------------------------------------------------
+@case("scene_params", ["bas_scene_params_f64", "bas_scene_params_bands_f64", "bas_scene_params_occluded_f64"],
+      [(form, room, G, nb) for form in ("plain", "bands", "occluded") for room, G, nb in ((0, 1, 1), (1, 2, 9), (1, 3, 130))])
+def scene_params(r, form, room, G, nb):
+    n_src, n_bands, n_screens = 3, 3, 2
+    rng = np.random.default_rng(G + nb)
+    size = np.array([4.0, 5.0, 3.0])
+    pos = r.inp("pos", rng.uniform(0.3, 2.7, (G, n_src, nb, 4)))
+    lpos = r.inp("lpos", rng.uniform(0.5, 2.5, (G, nb, 3)))
+    head = r.inp("head", rng.standard_normal((G, nb, 4)))
+    sg = r.inp("src_gain", rng.uniform(0.5, 1.5, (G, n_src, nb)))
+    n_img = 3 if room else 1
+    room_size = r.inp("room_size", size) if room else None
+    images = r.inp("images", np.array([[0, 0, 0], [1, 0, 0], [0, -1, 2]], np.int32)) if room else None
+    img_gain = r.inp("img_gain", np.array([1.0, 0.7, 0.4])) if room else None
+    n_rows = n_src * n_img
+    elev = r.rows("elev", n_rows, nb, dtype=F64, offset=8, groups=G)
+    gap = elev.stride(1) - nb
+    azim = r.rows("azim", n_rows, nb, dtype=F64, groups=G, gap=gap)
+    gain = r.rows("gain", n_rows, nb, dtype=F64, groups=G, gap=gap)
+    delay = r.rows("delay", n_rows, nb, dtype=F64, groups=G)
+    assert azim.stride() == elev.stride() == gain.stride()
+    front = (P(pos), pos.stride(0), pos.stride(1), pos.stride(2), None, 0, 0, 0.0, P(lpos), lpos.stride(0), lpos.stride(1),
+             P(head), head.stride(0), head.stride(1), P(sg), sg.stride(0), sg.stride(1), P(room_size), P(images), P(img_gain),
+             n_img, 44100.0 / 343.0, 1.0, 2.0, 4000.0, G, n_src, nb)
+    outs = (P(elev), P(azim), P(gain), elev.stride(0), elev.stride(1), P(delay), delay.stride(0), delay.stride(1))
+    if form == "plain":
+        r.call("bas_scene_params_f64", *front, *outs, r.stream)
+        return
+    orient = r.inp("orient", rng.standard_normal((G, n_src, nb, 4)))
+    pattern = r.inp("pattern", rng.uniform(0.0, 1.0, (n_src, n_bands)))
+    air = r.inp("air", rng.uniform(0.0, 0.01, n_bands))
+    img_logmag = r.inp("img_logmag", rng.uniform(-1.0, 0.0, (n_img, n_bands)))
+    bands = (P(orient), orient.stride(0), orient.stride(1), orient.stride(2), P(pattern), pattern.stride(0), P(air),
+             P(img_logmag), n_bands, 1e-6)
+    logmag = r.rows("logmag", n_rows, n_bands, dtype=F64, groups=G, ears=nb)
+    louts = (P(logmag), logmag.stride(0), logmag.stride(1), logmag.stride(2))
+    if form == "bands":
+        r.call("bas_scene_params_bands_f64", *front, *bands, *outs, *louts, r.stream)
+        return
+    e1, e2 = np.array([0.5, 0.0, 0.0]), np.array([0.0, 0.0, 0.6])
+    screens = r.inp("screens", np.stack([np.concatenate([[2.0, 2.5, 1.5], e1, e2]), np.concatenate([[1.0, 1.2, 1.0], e2, e1])]))
+    transmission = r.inp("transmission", rng.uniform(0.0, 1.0, (n_screens, n_bands)))
+    fresnel = r.inp("fresnel", 2.0 * np.array([250.0, 1000.0, 4000.0]) / 343.0)
+    r.call("bas_scene_params_occluded_f64", *front, *bands, P(screens), P(transmission), transmission.stride(0), P(fresnel),
+           n_screens, *outs, *louts, r.stream)
+
+
+# ---- table builder -----------------------------------------------------------------------------------------------------------
+@case("table_builder", ["bas_resample_up_f64", "bas_delaydiffs_f64"], [(3, 33, 2), (5, 64, 4), (7, 96, 8)])
+def table_builder(r, n_dir, n_taps, p):
+    import importlib
+    up = importlib.import_module("binaural-audio-synthesis_amd.upsample_irs")
+    rng = np.random.default_rng(n_dir + n_taps)
+    t = np.arange(n_taps)[None, :] - (0.4 * n_taps + rng.uniform(-3, 3, (n_dir, 1)))
+    irs = r.inp("irs", np.exp(-0.5 * (t / 2.5) ** 2) + 0.01 * rng.standard_normal((n_dir, n_taps)))
+    h, Lh = up.octave_resample_filter(p, 1)
+    h = r.inp("h", np.asarray(h, np.float64))
+    assert h.numel() == 2 * Lh + 1
+    y = r.out("y", (n_dir, n_taps * p), F64, offset=8)
+    r.call("bas_resample_up_f64", P(irs), n_dir, n_taps, P(h), int(Lh), p, P(y), r.stream)
+    diffs = r.out("diffs", (n_dir, n_dir), F64, offset=8)
+    status = r.out("status", (1,), I64)
+    r.call("bas_delaydiffs_f64", P(irs), n_dir, n_taps, P(h), int(Lh), p, P(diffs), P(status), r.stream)
+    if not r.dry:
+        assert int(status[0]) == 0
+
+
+# ---- the test ----------------------------------------------------------------------------------------------------------------
+def _ids():
+    return [(name, i) for name in sorted(CASES) for i in range(len(CASES[name][2]))]
+
+
+def _label(name, i):
+    return name + "-" + "-".join(str(v) for v in CASES[name][2][i])
+
+
+@pytest.mark.parametrize("name,i", _ids(), ids=[_label(n, i) for n, i in _ids()])
+def test_write_bounds(name, i):
+    _, fn, variants = CASES[name]
+    check(fn, variants[i])
+
+
+def test_the_cases_reach_what_they_claim():
+    """Every fused kernel of the planner and every stored-IR family is a case, with each way a fused render sums its tiles."""
+    assert {c[5] for c in STORED.values()} == {HD, ROWS32, GENERIC}
+    assert {c[5] for c in FUSED.values()} >= {FQ, FS128, FS104, FS0, "bas_render_fs_kernel<128,2>", "bas_render_fs_kernel<128,4>",
+                                              "bas_render_fz_kernel<4,0>", "bas_render_fz_kernel<4,1>", "bas_render_fz_kernel<1,0>"}
+    assert {c[6] for c in FUSED.values()} == {"direct", "slab", "wide"}
+    for n_src, T_in, K, S, L, _, _ in FUSED.values():    # a partial last tile, an odd output length
+        assert T_in % 2048 and T_in % 8192 and T_in % K == 0 and (T_in + L - 1) % 2 == 1
