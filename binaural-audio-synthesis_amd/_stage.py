@@ -20,14 +20,16 @@ def host_array(arg):
 
 
 # ---- stereo signals ---------------------------------------------------------------------------------------------------
-def stereo_host(y):
-    """y [n, 2] or [G, n, 2] as contiguous finite float32 on the host; ValueError otherwise."""
+def stereo_host(y, finite=True):
+    """y [n, 2] or [G, n, 2] as contiguous finite float32 on the host; ValueError otherwise.  finite=False: NaN and Inf
+    pass (the definitions say what a non-finite sample does; the device entry points take host data
+    with the check)."""
     a = np.asarray(y)
     if a.ndim not in (2, 3) or a.shape[-1] != 2:
         raise ValueError(f"y must be [n, 2] or [G, n, 2], got {a.shape}")
     with np.errstate(over="ignore"):                                       # (a value beyond binary32 becomes inf: refused)
         y32 = np.ascontiguousarray(a, dtype=np.float32)
-    if not np.isfinite(y32).all():
+    if finite and not np.isfinite(y32).all():
         raise ValueError("y must be finite")
     return y32
 

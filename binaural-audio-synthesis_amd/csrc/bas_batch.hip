@@ -109,15 +109,15 @@ __global__ __launch_bounds__(BB_THREADS) void bas_batch_peaks_kernel(const float
     for (int e = 0; e < 2; ++e) {
         const float *w = y + e * y_stride + off[b];
         const long head = bas_aligned16(w) ? 0 : min(n, (long)((16 - (reinterpret_cast<uintptr_t>(w) & 15)) >> 2));
-        if (blockIdx.x == 0 && threadIdx.x < head) lmax = fmaxf(lmax, fabsf(w[threadIdx.x]));
+        if (blockIdx.x == 0 && threadIdx.x < head) lmax = bas_peak_max(lmax, w[threadIdx.x]);
         const float *wa = w + head;
         const long nq = (n - head) >> 2;
         for (long i = blockIdx.x * (long)BB_THREADS + threadIdx.x; i < nq; i += gstride) {
             const f32x4 q = *reinterpret_cast<const f32x4 *>(wa + 4 * i);
-            lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
+            lmax = bas_peak_max4(lmax, q);
         }
         const long tail0 = head + 4 * nq;
-        if (blockIdx.x == 0 && tail0 + threadIdx.x < n) lmax = fmaxf(lmax, fabsf(w[tail0 + threadIdx.x]));
+        if (blockIdx.x == 0 && tail0 + threadIdx.x < n) lmax = bas_peak_max(lmax, w[tail0 + threadIdx.x]);
     }
     bas_block_peak_max(lmax, peak_bits + b);
 }

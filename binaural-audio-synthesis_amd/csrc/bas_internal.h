@@ -120,12 +120,29 @@ __device__ __forceinline__ int bas_submod(int a, int b, int M) {
     return c < 0 ? c + M : c;
 }
 
+// One step of a peak reduction: the larger of acc (a peak so far: a non-negative float or a NaN without its sign) and |v|,
+// taken as the UNSIGNED maximum of the bit patterns.  The patterns of non-negative floats order like the floats and every
+// NaN pattern lies above +Inf, so a NaN sample makes the peak NaN and keeps it NaN (fmaxf would drop it: DESIGN.md §3.22 R3);
+// for data without NaN the result has the bits fmaxf(acc, fabsf(v)) has.  The cross-lane and atomicMax steps work on the same order.
+__device__ __forceinline__ float bas_peak_max(float acc, float v) {
+    const unsigned a = __float_as_uint(acc), b = __float_as_uint(v) & 0x7fffffffu;
+    return __uint_as_float(a > b ? a : b);
+}
+__device__ __forceinline__ float bas_peak_max4(float acc, f32x4 v) {
+    return bas_peak_max(bas_peak_max(bas_peak_max(bas_peak_max(acc, v.x), v.y), v.z), v.w);
+}
+// the peak of a wave, in every lane
+__device__ __forceinline__ float bas_wave_peak(float lmax) {
+    for (int o = 32; o > 0; o >>= 1) lmax = bas_peak_max(lmax, __shfl_xor(lmax, o));
+    return lmax;
+}
+
 // max|.| of a wave into *peak_bits (float bits of a non-negative value: unsigned order = float order).
 // Atomics on ONE address serialise at ~12 ns each whatever the CU they come from - 1 724 waves of the slab reduce
 // spent 21 of its 25 us there - so a wave first reads the published peak (coherently: past the per-XCD L2) and only
 // sends its atomic when it would raise it; the value only grows within a launch, a stale read costs an atomic, no more.
 __device__ __forceinline__ void bas_wave_peak_max(float lmax, unsigned int *peak_bits) {
-    for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+    lmax = bas_wave_peak(lmax);
     if ((threadIdx.x & 63) == 0) {
         const unsigned int mine = __float_as_uint(lmax);
         if (mine > __hip_atomic_load(peak_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(peak_bits, mine);
@@ -136,11 +153,11 @@ __device__ __forceinline__ void bas_wave_peak_max(float lmax, unsigned int *peak
 // thread reads the published peak and sends at most one atomic per workgroup.
 __device__ __forceinline__ void bas_block_peak_max(float lmax, unsigned int *peak_bits) {
     __shared__ float wave_max[4];
-    for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+    lmax = bas_wave_peak(lmax);
     if ((threadIdx.x & 63) == 0) wave_max[(threadIdx.x >> 6) & 3] = lmax;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned int mine = __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3])));
+        const unsigned int mine = __float_as_uint(bas_peak_max(bas_peak_max(wave_max[0], wave_max[1]), bas_peak_max(wave_max[2], wave_max[3])));
         if (mine > __hip_atomic_load(peak_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(peak_bits, mine);
     }
 }

@@ -7,7 +7,7 @@
 
 // the required gain of one stereo sample: ONE binary32 division
 __device__ __forceinline__ float lim_required(f32x2 v, float c) {
-    const float m = fmaxf(fabsf(v.x), fabsf(v.y));
+    const float m = bas_peak_max(bas_peak_max(0.f, v.x), v.y);      // (a NaN in either ear: m NaN, r = 1, as np.abs(y).max(-1))
     return m > c ? c / m : 1.0f;
 }
 
@@ -38,7 +38,7 @@ __device__ __forceinline__ void lim_block_meters(float lmin, float lmax, unsigne
     __shared__ float wave_min[4], wave_max[4];
     for (int o = 32; o > 0; o >>= 1) {
         lmin = fminf(lmin, __shfl_xor(lmin, o));
-        lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+        lmax = bas_peak_max(lmax, __shfl_xor(lmax, o));
     }
     if ((threadIdx.x & 63) == 0) {
         wave_min[(threadIdx.x >> 6) & 3] = lmin;
@@ -50,7 +50,7 @@ __device__ __forceinline__ void lim_block_meters(float lmin, float lmax, unsigne
         if (mine < __hip_atomic_load(gain_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(gain_bits, mine);
     }
     if (threadIdx.x == 64 && peak_bits) {
-        const unsigned int mine = __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3])));
+        const unsigned int mine = __float_as_uint(bas_peak_max(bas_peak_max(wave_max[0], wave_max[1]), bas_peak_max(wave_max[2], wave_max[3])));
         if (mine > __hip_atomic_load(peak_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(peak_bits, mine);
     }
 }
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(LIM_THREADS) void bas_limit_kernel(const float *__r
             og[(o0 + u) * o_t] = l;
             og[(o0 + u) * o_t + o_e] = r;
             lmin = fminf(lmin, gain);
-            lmax = fmaxf(lmax, fmaxf(fabsf(l), fabsf(r)));
+            lmax = bas_peak_max(bas_peak_max(lmax, l), r);
         }
     }
     if (reduction || peak)                                               // (uniform)

@@ -47,7 +47,7 @@ __device__ __forceinline__ float met_sample(const float *__restrict__ yg, long y
 // binary64 and are added one by one from +0 with j ascending, then rounded to binary32 once.
 __device__ __forceinline__ float met_peak(const float *xs, int n, int cnt, const MeterParams &F) {
     float lmax = 0.f;
-    for (int i = threadIdx.x; i < n; i += MET_THREADS) lmax = fmaxf(lmax, fabsf(xs[MET_CTX + i]));
+    for (int i = threadIdx.x; i < n; i += MET_THREADS) lmax = bas_peak_max(lmax, xs[MET_CTX + i]);
     for (int mi = threadIdx.x; mi < cnt; mi += MET_THREADS) {
         double xv[MET_TAPS];
 #pragma unroll
@@ -57,7 +57,7 @@ __device__ __forceinline__ float met_peak(const float *xs, int n, int cnt, const
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < MET_TAPS; ++k) s += xv[k] * (double)F.taps[p * MET_TAPS + k];
-            lmax = fmaxf(lmax, fabsf((float)s));
+            lmax = bas_peak_max(lmax, (float)s);
         }
     }
     return lmax;

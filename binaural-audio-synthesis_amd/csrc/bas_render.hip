@@ -783,7 +783,7 @@ __global__ __launch_bounds__(256) void bas_render_generic_kernel(const float *__
         }
         y[n] = al_l;
         y[T_out + n] = al_r;
-        lmax = fmaxf(lmax, fmaxf(fabsf(al_l), fabsf(al_r)));
+        lmax = bas_peak_max(bas_peak_max(lmax, al_l), al_r);
     }
     if (peak_bits) {
         bas_block_peak_max(lmax, peak_bits);
@@ -829,8 +829,7 @@ __global__ __launch_bounds__(256) void bas_slab_reduce_kernel(const float *__res
             }
             bas_store4_sc1(y + n, sl);
             bas_store4_sc1(y + T_out + n, sr);
-            lmax = fmaxf(lmax, fmaxf(fmaxf(fmaxf(fabsf(sl.x), fabsf(sl.y)), fmaxf(fabsf(sl.z), fabsf(sl.w))),
-                                     fmaxf(fmaxf(fabsf(sr.x), fabsf(sr.y)), fmaxf(fabsf(sr.z), fabsf(sr.w)))));
+            lmax = bas_peak_max4(bas_peak_max4(lmax, sl), sr);
             continue;
         }
         float vl[4] = {sl.x, sl.y, sl.z, sl.w}, vr[4] = {sr.x, sr.y, sr.z, sr.w};
@@ -849,7 +848,7 @@ __global__ __launch_bounds__(256) void bas_slab_reduce_kernel(const float *__res
                     y[n + j] = a;
                     y[T_out + n + j] = b;
                 }
-                if (n + j >= plo && n + j < phi) lmax = fmaxf(lmax, fmaxf(fabsf(a), fabsf(b)));
+                if (n + j >= plo && n + j < phi) lmax = bas_peak_max(bas_peak_max(lmax, a), b);
             }
         }
     }
@@ -913,7 +912,7 @@ __global__ __launch_bounds__(256) void bas_slab_reduce_wide_kernel(const float *
                     bas_store1_sc1(ye + n + j, a);
                 else
                     ye[n + j] = a;
-                if (n + j >= plo && n + j < phi) lmax = fmaxf(lmax, fabsf(a));
+                if (n + j >= plo && n + j < phi) lmax = bas_peak_max(lmax, a);
             }
         }
     }
@@ -934,7 +933,7 @@ __global__ __launch_bounds__(256) void bas_absmax_kernel(const float *__restrict
                                                            unsigned int *peak_bits) {
     float lmax = 0.f;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L)
-        lmax = fmaxf(lmax, fabsf(y[i]));
+        lmax = bas_peak_max(lmax, y[i]);
     bas_block_peak_max(lmax, peak_bits);
 }
 
@@ -955,7 +954,7 @@ __global__ __launch_bounds__(256) void bas_mix_partials_kernel(const float *__re
         float v = 0.f;
         for (int p = 0; p < n_parts; ++p) v += parts[p * part_stride + i];
         y[i] = v;
-        lmax = fmaxf(lmax, fabsf(v));
+        lmax = bas_peak_max(lmax, v);
     }
     if (peak_bits) {
         bas_block_peak_max(lmax, peak_bits);
@@ -975,13 +974,13 @@ __global__ __launch_bounds__(256) void bas_mix_finish_kernel(const float *__rest
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int p = 0; p < n_parts; ++p) v += *reinterpret_cast<const f32x4_a4 *>(parts + p * part_stride + 4 * i);
         bas_store4_sc1(y + 4 * i, v);
-        lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        lmax = bas_peak_max4(lmax, v);
     }
     for (long i = 4 * n4 + blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) {
         float v = 0.f;
         for (int p = 0; p < n_parts; ++p) v += parts[p * part_stride + i];
         bas_store1_sc1(y + i, v);
-        lmax = fmaxf(lmax, fabsf(v));
+        lmax = bas_peak_max(lmax, v);
     }
     bas_tail<256>(T, lmax);
 }

@@ -297,10 +297,10 @@ __global__ __launch_bounds__(RV_MAX_NP) void bas_long_fir_inverse_kernel(const f
     if (peak) {                                                          // (uniform) the workgroup's maximum through LDS
         float *m = reinterpret_cast<float *>(s.tw);                      // (the twiddles have been used)
         __syncthreads();
-        m[t] = fmaxf(fabsf(ol), fabsf(orr));
+        m[t] = bas_peak_max(bas_peak_max(0.f, ol), orr);
         __syncthreads();
         for (int o = Np >> 1; o > 0; o >>= 1) {
-            if (t < o) m[t] = fmaxf(m[t], m[t + o]);
+            if (t < o) m[t] = bas_peak_max(m[t], m[t + o]);
             __syncthreads();
         }
         if (t == 0) {

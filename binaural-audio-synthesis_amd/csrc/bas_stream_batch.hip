@@ -98,15 +98,15 @@ __global__ __launch_bounds__(SB_THREADS) void bas_stream_block_epilogue_kernel(
     for (int e = 0; e < 2; ++e) {
         const float *w = y + e * y_stride + (long)g * W + halo;
         const long head = sb_aligned16(w) ? 0 : min(B, (long)((16 - (reinterpret_cast<uintptr_t>(w) & 15)) >> 2));
-        if (blockIdx.x == 0 && threadIdx.x < head) lmax = fmaxf(lmax, fabsf(w[threadIdx.x]));
+        if (blockIdx.x == 0 && threadIdx.x < head) lmax = bas_peak_max(lmax, w[threadIdx.x]);
         const float *wa = w + head;
         const long nq = (B - head) >> 2;
         for (long i = tid; i < nq; i += nthreads) {
             const f32x4 q = *reinterpret_cast<const f32x4 *>(wa + 4 * i);
-            lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
+            lmax = bas_peak_max4(lmax, q);
         }
         const long tail0 = head + 4 * nq;
-        if (blockIdx.x == 0 && tail0 + threadIdx.x < B) lmax = fmaxf(lmax, fabsf(w[tail0 + threadIdx.x]));
+        if (blockIdx.x == 0 && tail0 + threadIdx.x < B) lmax = bas_peak_max(lmax, w[tail0 + threadIdx.x]);
     }
     if (peak_bits) bas_block_peak_max(lmax, peak_bits + g);
     BasCarry C;

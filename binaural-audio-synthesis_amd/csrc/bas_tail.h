@@ -83,14 +83,14 @@ __device__ __forceinline__ void bas_tail(const BasTail &T, float lmax) {
     const unsigned n_groups = T.n_wg < 8u ? T.n_wg : 8u;
     const unsigned g = blockIdx.x & 7u;                      // (n_wg < 8: every workgroup its own group)
     const unsigned n_g = (T.n_wg - g + 7u) >> 3;             // members of this group
-    for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+    lmax = bas_wave_peak(lmax);
     if ((tid & 63) == 0) t_wmax[tid >> 6] = lmax;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's y stores have left
     __syncthreads();
     if (tid == 0) {
         float m = t_wmax[0];
 #pragma unroll
-        for (int w = 1; w < NWV; ++w) m = fmaxf(m, t_wmax[w]);
+        for (int w = 1; w < NWV; ++w) m = bas_peak_max(m, t_wmax[w]);
         bas_store1_sc1(T.wgpeak + blockIdx.x, m);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         t_word = __hip_atomic_fetch_add(T.ctl + BAS_CTL_GROUP(g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -100,16 +100,16 @@ __device__ __forceinline__ void bas_tail(const BasTail &T, float lmax) {
     // ---- the group's last member: the group's maximum, then the group is reported
     float m = 0.f;
     for (unsigned i = g + 8u * (unsigned)tid; i < T.n_wg; i += 8u * THREADS)
-        m = fmaxf(m, __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned *>(T.wgpeak) + i, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT)));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        m = bas_peak_max(m, __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned *>(T.wgpeak) + i, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT)));
+    m = bas_wave_peak(m);
     __syncthreads();
     if ((tid & 63) == 0) t_wmax[tid >> 6] = m;
     __syncthreads();
     if (tid == 0) {
         m = t_wmax[0];
 #pragma unroll
-        for (int w = 1; w < NWV; ++w) m = fmaxf(m, t_wmax[w]);
+        for (int w = 1; w < NWV; ++w) m = bas_peak_max(m, t_wmax[w]);
         __hip_atomic_store(T.ctl + BAS_CTL_GROUP(g), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (all members are in)
         __hip_atomic_store(T.ctl + BAS_CTL_GROUP_PEAK(g), __float_as_uint(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -136,13 +136,13 @@ __device__ __forceinline__ void bas_tail(const BasTail &T, float lmax) {
     m = 0.f;
     if (tid < (int)n_groups)
         m = __uint_as_float(__hip_atomic_load(T.ctl + BAS_CTL_GROUP_PEAK(tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    for (int o = 4; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    for (int o = 4; o > 0; o >>= 1) m = bas_peak_max(m, __shfl_xor(m, o));
     m = __shfl(m, 0);
     __syncthreads();
     if (tid == 0) t_wmax[0] = m;
     __syncthreads();
     m = t_wmax[0];
-    if (T.normalize && m > 1.0f && t_ok) {                   // :463-464 - this workgroup's share of y
+    if (T.normalize && m > 1.0f && t_ok) {                   // :463-464 (a NaN peak: false, y stays) - this workgroup's share of y
         const long n4 = T.n >> 2;
         const long lo = n4 * t / n_groups, hi = n4 * (t + 1) / n_groups;
         for (long i = lo + tid; i < hi; i += THREADS) {

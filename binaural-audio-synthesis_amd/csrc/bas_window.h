@@ -197,7 +197,7 @@ __device__ __forceinline__ float win_store_row_direct(const f32x2 (&acc)[32], fl
                 f32x4_a4 *p = reinterpret_cast<f32x4_a4 *>(ye + 4 * i);   // (the right ear starts at 4 T_out bytes)
                 if (accumulate) v += *p;
                 *p = v;
-                lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+                lmax = bas_peak_max4(lmax, v);
             } else {
                 const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -205,7 +205,7 @@ __device__ __forceinline__ float win_store_row_direct(const f32x2 (&acc)[32], fl
                     if (n + j < T_out) {
                         const float r = accumulate ? vv[j] + ye[4 * i + j] : vv[j];
                         ye[4 * i + j] = r;
-                        lmax = fmaxf(lmax, fabsf(r));
+                        lmax = bas_peak_max(lmax, r);
                     }
                 }
             }
@@ -216,7 +216,7 @@ __device__ __forceinline__ float win_store_row_direct(const f32x2 (&acc)[32], fl
 
 // max over the wave as the bits of a non-negative float, wave-uniform (kept in a scalar register across the row steps)
 __device__ __forceinline__ unsigned win_wave_max_bits(float lmax) {
-    for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+    lmax = bas_wave_peak(lmax);
     return (unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(lmax));
 }
 

@@ -24,8 +24,11 @@ limiter gives the bits of an offline one.
     StreamLimiter                the stream: process(block) is A samples late, finish() hands out the last A samples
 
 Not modelled: an exponential release, oversampled (true-peak) detection (loudness.py meters the true peak and the
-programme loudness of what this stage hands out; it does not limit them), unlinked ears, makeup gain.  Inputs must be
-finite; the bit-for-bit claims hold for |y| <= 2^20 c.
+programme loudness of what this stage hands out; it does not limit them), unlinked ears, makeup gain.  The bit-for-bit
+claims hold for |y| <= 2^20 c.  Host inputs must be finite (ValueError); a device input is not inspected, and for any
+input bits the outputs are finite and within the ceiling (a NaN frame has r = 1, an Inf frame r = 0,
+the bad frame's own output is not specified, the session's other outputs are limit_f32_ref's, other sessions are not
+touched).
 """
 import numpy as np
 
@@ -87,11 +90,12 @@ def _smoothed(r, A, Hd):
     return acc
 
 
-def limit_f64(y, ceiling, lookahead, hold, return_gain=False):
+def limit_f64(y, ceiling, lookahead, hold, return_gain=False, finite=True):
     """The definition: y float32 [n, 2] or [G, n, 2] -> float64 of the same shape (with return_gain also g [.., n]);
-    steps 2 to 6 in binary64 on the float32 inputs, the ceiling rounded to binary32 first."""
+    steps 2 to 6 in binary64 on the float32 inputs, the ceiling rounded to binary32 first.  finite=False: y may hold NaN
+    and Inf (a NaN in either ear: m is NaN, m > c false, r = 1; the frame's own output is NaN here)."""
     c32, A, Hd = check_params(ceiling, lookahead, hold)
-    y32 = stereo_host(y)
+    y32 = stereo_host(y, finite)
     c = float(c32)
     yd = y32.astype(np.float64)
     m = np.abs(yd).max(axis=-1)
@@ -103,12 +107,13 @@ def limit_f64(y, ceiling, lookahead, hold, return_gain=False):
     return (out, g) if return_gain else out
 
 
-def limit_f32_ref(y, ceiling, lookahead, hold, return_gain=False):
+def limit_f32_ref(y, ceiling, lookahead, hold, return_gain=False, finite=True):
     """The device arithmetic, step by step: r one float32 division; the sum sequential binary64 adds in ascending order,
     one binary64 division by A + 1, one rounding to binary32; one float32 multiplication, then the clamp.  float32 out
-    (with return_gain also g, float32 [.., n]).  bas_limit_f32 gives these bits."""
+    (with return_gain also g, float32 [.., n]).  bas_limit_f32 gives these bits.  finite=False: y may hold NaN and Inf;
+    bas_limit_f32 then gives these bits but for the non-finite products y g, which leave it as -c."""
     c32, A, Hd = check_params(ceiling, lookahead, hold)
-    y32 = stereo_host(y)
+    y32 = stereo_host(y, finite)
     m = np.abs(y32).max(axis=-1)
     r = np.ones_like(m)
     np.divide(c32, m, out=r, where=m > c32)

@@ -88,17 +88,18 @@ def _lfilter(b, a, x):
     return out
 
 
-def kweighted_f64(y, fs):
-    """The K-weighted signal: y float32 [n, 2] or [G, n, 2] -> float64 of the same shape."""
+def kweighted_f64(y, fs, finite=True):
+    """The K-weighted signal: y float32 [n, 2] or [G, n, 2] -> float64 of the same shape.  finite=False here and below:
+    y may hold NaN and Inf."""
     (b1, a1), (b2, a2) = kweighting(fs)
-    x = np.moveaxis(stereo_host(y).astype(np.float64), -2, -1)
+    x = np.moveaxis(stereo_host(y, finite).astype(np.float64), -2, -1)
     return np.moveaxis(_lfilter(b2, a2, _lfilter(b1, a1, x)), -1, -2)
 
 
-def hop_energies_f64(y, fs):
+def hop_energies_f64(y, fs, finite=True):
     """The definition of the hop energies: float64 [hops, 2] or [G, hops, 2], hops = n // (fs / 10)."""
     hop = check_fs(fs) // 10
-    z = kweighted_f64(y, fs)
+    z = kweighted_f64(y, fs, finite)
     hops = z.shape[-2] // hop
     z = z[..., :hops * hop, :]
     return (z * z).reshape(z.shape[:-2] + (hops, hop, 2)).sum(axis=-2)
@@ -147,7 +148,9 @@ def readings(E, hop):
     short = _lufs(_window_powers(E, 30, int(hop)))
     integrated = -np.inf
     keep = l > ABSOLUTE_GATE
-    if keep.any():
+    if np.isnan(p).any():                          # a NaN block fails every comparison: the gates would drop it and
+        integrated = float("nan")                  # hide a poisoned signal behind its clean start
+    elif keep.any():
         gate = -0.691 + 10.0 * np.log10(p[keep].mean()) - 10.0
         keep &= l > gate
         if keep.any():
@@ -166,10 +169,10 @@ def true_peak_taps():
     return np.array(rows).astype(np.float32)
 
 
-def true_peak_ref(y):
+def true_peak_ref(y, finite=True):
     """The device arithmetic of the true peak: float32 [2] or [G, 2], the maximum per ear over the samples and the three
     interpolated phases at every position whose window touches the signal.  bas_meter_f32 gives these bits."""
-    y32 = stereo_host(y)
+    y32 = stereo_host(y, finite)
     n = y32.shape[-2]
     taps = true_peak_taps().astype(np.float64)
     lead = y32.shape[:-2]
@@ -268,6 +271,7 @@ def _readings_device(E, hop):
     cnt2 = keep2.sum(dim=1)
     mean2 = torch.where(keep2, p, zero).sum(dim=1) / cnt2.clamp(min=1)
     integrated = torch.where(cnt2 > 0, lufs(mean2), ninf)
+    integrated = torch.where(torch.isnan(p).any(dim=1), torch.full_like(ninf, float("nan")), integrated)   # (as readings())
     return integrated, l.amax(dim=1), short_max
 
 

@@ -222,6 +222,10 @@ int bas_render_mix_profiled_f32(const float *x, long x_stride, const float *H, i
  *    to y before the call's work on `stream` ends - inside the tail of the last kernel (no launch of its own; the workgroups
  *    that finish last share the rescale) whenever y is 16-byte aligned, else by bas_scale_by_peak_f32.  `peak` (may be NULL)
  *    receives max|y| BEFORE the rule either way.
+ *    Every max|.| of this library (here, the batch's and the streams' peaks, the late tail's, the meters') is taken on the
+ *    bit patterns of |y|: a NaN among the samples makes it NaN - and it stays NaN - and +-Inf without
+ *    a NaN makes it +Inf.  The rule acts on that value as the reference's `if m > 1` does: a NaN peak leaves y as it is,
+ *    a +Inf peak divides by it.
  * n == 0 (no queries / no sources) is served by every entry point: the per-query arrays may then be NULL. */
 int bas_interp2d_plan_f32(const double *diffs, const int32_t *idx, const double *w, int n,
                           int ndir, int L, int U, void *plans, size_t plans_bytes,
@@ -724,8 +728,14 @@ int bas_long_fir_f32(const float *bus, long bus_stride, long Hb, long T_bus, int
  *   5. g[n] = min(s[n], r[n]);
  *   6. out[n] = min(max(y[n] g[n], -c), c) per ear             (one binary32 multiplication; the sign is kept).
  * The gain falls linearly over the A samples before a peak, meets the required gain at the peak, stays for Hd samples and
- * returns linearly over A samples; |out| <= c always; a signal whose peak is at most c keeps its bits.  Inputs must be
- * finite; the bits are specified for |y| <= 2^20 c (no r subnormal).
+ * returns linearly over A samples; |out| <= c always; a signal whose peak is at most c keeps its bits.  The bits are
+ * specified for |y| <= 2^20 c (no r subnormal).
+ * Non-finite inputs: for ANY input bits every output is finite and |out| <= c.  In step 1 a NaN in
+ * either ear makes m NaN (the maximum is taken on the bit patterns: bas_peak_max), so step 2 gives r = 1, as for a zeroed
+ * frame; an infinite sample gives r = 0.  A non-finite product in step 6 leaves as -c (min(max(NaN, -c), c)): what the bad
+ * frame itself becomes is not part of the contract.  The other outputs of the session are those of limit_f32_ref
+ * (limiter.py) on the same input; they are the bits of the run with that frame zeroed once 2 A + Hd samples have passed
+ * it.  No other session's outputs, meters or state change.
  *   y at y + g y_stride_g + t y_stride_t + e y_stride_e, out likewise: any strides >= 0 (the stream renderers' [B, 2]
  *   views of planar buffers, interleaved frames); the output's strides must address every element once, and input, output
  *   and state must not overlap (BAS_E_SHAPE: the limiter does not run in place).
