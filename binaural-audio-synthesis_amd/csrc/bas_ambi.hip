@@ -134,7 +134,7 @@ __global__ __launch_bounds__(MM_THREADS) void bas_matrix_mix_kernel(
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        o[i] = STATIC ? a[i] : fmaf((float)(j + i) * inv_K, b[i] - a[i], a[i]);
+                        o[i] = STATIC ? a[i] : bas_crossfade(a[i], b[i], (float)(j + i) * inv_K);
                 } else {                                                  // a chunk boundary inside the quad: one by one
                     int ki = k, ji = j;
 #pragma unroll
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(MM_THREADS) void bas_matrix_mix_kernel(
                             a = fmaf(ma[c], xr[c][i], a);
                             b = fmaf(mb[c], xr[c][i], b);
                         }
-                        o[i] = fmaf((float)ji * inv_K, b - a, a);
+                        o[i] = bas_crossfade(a, b, (float)ji * inv_K);
                         if (++ji == K) { ji = 0; ++ki; }
                     }
                 }
@@ -446,7 +446,7 @@ __global__ __launch_bounds__(ENC_THREADS) void bas_ambi_encode_kernel(
             if (c0 + c < c1) {
                 float o[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = STATIC ? A[c][i] : fmaf(w[i], B[STATIC ? 0 : c][i] - A[c][i], A[c][i]);
+                for (int i = 0; i < 4; ++i) o[i] = STATIC ? A[c][i] : bas_crossfade(A[c][i], B[STATIC ? 0 : c][i], w[i]);
                 if (bg) {
                     const f32x4 q = enc_load4(bg + (long)(c0 + c) * bs_c, tl, T);
                     o[0] = q.x + o[0]; o[1] = q.y + o[1]; o[2] = q.z + o[2]; o[3] = q.w + o[3];

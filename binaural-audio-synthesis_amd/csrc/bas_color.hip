@@ -91,7 +91,7 @@ __global__ __launch_bounds__(CL_THREADS) void bas_color_rows_kernel(
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    o[i] = STATIC ? a[i] : fmaf((float)(j + i) * inv_K, b[i] - a[i], a[i]);
+                    o[i] = STATIC ? a[i] : bas_crossfade(a[i], b[i], (float)(j + i) * inv_K);
             } else {                                                      // a chunk boundary inside the quad: one by one
                 int ki = k, ji = j;
                 for (int i = 0; i < 4; ++i) {
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(CL_THREADS) void bas_color_rows_kernel(
                             a = fmaf(ca[m], v, a);
                             if (!STATIC) b = fmaf(cb[m], v, b);
                         }
-                    o[i] = STATIC ? a : fmaf((float)ji * inv_K, b - a, a);
+                    o[i] = STATIC ? a : bas_crossfade(a, b, (float)ji * inv_K);
                     if (++ji == K) { ji = 0; ++ki; }
                 }
             }

@@ -120,6 +120,16 @@ __device__ __forceinline__ int bas_submod(int a, int b, int M) {
     return c < 0 ? c + M : c;
 }
 
+// The crossfade of the sums a, b of two chunk boundaries, (1 - w) a + w b with w = j / K in [0, 1) (colour, ambisonic
+// decoder and encoder rows).  a - w a is ONE rounding of (1 - w) a, so the result stays within float32 rounding of
+// (1 - w)|a| + w|b| - the magnitudes the definition gives this output - even where b lies far below a and w is near 1.
+// fmaf(w, b - a, a) does not: it rounds b - a and w (b - a) against |a|, K / 2 times the weight a still has at the end
+// of a chunk whose coefficients step down.  Equal sums keep their bits: boundary coefficients that
+// repeat give the static form's output.
+__device__ __forceinline__ float bas_crossfade(float a, float b, float w) {
+    return a == b ? a : fmaf(w, b, fmaf(-w, a, a));
+}
+
 // One step of a peak reduction: the larger of acc (a peak so far: a non-negative float or a NaN without its sign) and |v|,
 // taken as the UNSIGNED maximum of the bit patterns.  The patterns of non-negative floats order like the floats and every
 // NaN pattern lies above +Inf, so a NaN sample makes the peak NaN and keeps it NaN (fmaxf would drop it: DESIGN.md §3.22 R3);

@@ -526,7 +526,7 @@ int bas_batch_pack_delay_f32(const float *sig, int n_items, int n_src, long N, c
  *   A = sum_{m < M} c_k[m] x'(t - m),  B = sum_{m < M} c_{k+1}[m] x'(t - m),  x''(t) = A + (j / K)(B - A).
  * Precision: A and B are accumulated in binary32 by fused multiply-adds, acc = fma(c[m], x'(t - m), acc) from acc = 0 with
  * m ascending (M is padded to a multiple of 4 with zero taps, which add exact zeros); w = (float)j * (1.0f / (float)K);
- * x'' = fma(w, B - A, A).  The bits of an output depend on (j, K, c_k, c_{k+1}) and its M inputs alone - not on the absolute
+ * x'' = A if A == B, else fma(w, B, fma(-w, A, A)).  The bits of an output depend on (j, K, c_k, c_{k+1}) and its M inputs alone - not on the absolute
  * time nor on where a tile starts - so a stream's coloured block is the offline one bit for bit; (1, 0, .., 0) returns its
  * input bit for bit; B == A returns A.  Samples outside the readable range are 0.  Nothing is validated on the device.
  *   bas_color_rows_f32: rows (g, s), g < n_groups, s < n_src: input x + g x_stride_g + s x_stride_s (sample 0; samples
@@ -837,7 +837,7 @@ int bas_meter_f32(const float *y, long y_stride_g, long y_stride_t, long y_strid
  *   bas_matrix_mix_f32: the hot path.  Input rows x + g xs_g + c xs_c (C <= 16 rows of T samples), matrices
  *     m + g ms_g + k ms_k + v C + c for the (T - 1) / K + 2 chunk boundaries, output rows y + g ys_g + v ys_v (V <= 64).
  *     For t = k K + j:  A = fmaf(M_k[v][c], x_c(t), A) from +0 with c ascending, B likewise with M_{k+1},
- *     w = (float)j * (1.0f / (float)K),  y_v(t) = fmaf(w, B - A, A) - the form of bas_color_rows_f32: an output's bits
+ *     w = (float)j * (1.0f / (float)K),  y_v(t) = A == B ? A : fmaf(w, B, fmaf(-w, A, A)) - the form of bas_color_rows_f32: an output's bits
  *     depend on (j, K, M_k, M_{k+1}) and the C inputs at t alone, not on tiles, block boundaries or alignment.
  *     ms_k == 0 is the static form, y = A (B skipped): the bits of the per-boundary form fed repeated matrices.
  *     ms_g == 0 shares one matrix bank, xs_g == 0 one bed over all groups.  16-byte loads and stores where a row is
@@ -873,7 +873,7 @@ int bas_matrix_mix_f32(const float *x, long xs_g, long xs_c, const float *m, lon
  *     consecutive rows.  For t = k K + j:
  *       per block b:   A_b = fmaf(E_k[s][c], x_s(t), A_b) from +0 with s ascending inside the block, B_b likewise with E_{k+1};
  *       across blocks: A = A_0, then A = A + A_b for b = 1, 2, .. ascending (binary32 additions), B likewise;
- *       w = (float)j * (1.0f / (float)K),  y = fmaf(w, B - A, A);   with base:  y = base_c(t) + y  (one addition).
+ *       w = (float)j * (1.0f / (float)K),  y = A == B ? A : fmaf(w, B, fmaf(-w, A, A));   with base:  y = base_c(t) + y  (one addition).
  *     es_k == 0 is the static form, y = A (B skipped): the bits of the per-boundary form fed repeated banks.  An output's
  *     bits depend on (j, K, n_src, E_k[:, c], E_{k+1}[:, c]), the n_src inputs at t and base_c(t) alone - not on tiles, T,
  *     block boundaries of a stream, alignment, grid, slab sizes or groups.  With n_src <= 32 this is the chain of

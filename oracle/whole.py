@@ -129,6 +129,87 @@ def describe(res):
             f"got {res['got']:.9g}, want {res['want']:.9g}, scale {res['scale']:.6g}")
 
 
+U32 = 2.0 ** -24            # the unit roundoff of float32
+W_ROW = 32                  # one FIR row: the fast FIR forms x_e + x_o within a row
+
+
+def widen_max(a, w):
+    """max over |m - n| <= w of a[.., m], along the last axis (w = 0: a itself)."""
+    a = np.asarray(a, dtype=np.float64)
+    if w <= 0 or a.shape[-1] == 0:
+        return a.copy()
+    pad = [(0, 0)] * (a.ndim - 1) + [(w, w)]
+    win = np.lib.stride_tricks.sliding_window_view(np.pad(a, pad), 2 * w + 1, axis=-1)
+    return win.max(axis=-1)
+
+
+def frame_max(a, Np, before=1, after=1):
+    """The scale of a frame grid (the late tail, DESIGN.md §3.14): every sample of frame f = n // Np gets the maximum
+    of a over the frames f - before .. f + after, along the last axis."""
+    a = np.asarray(a, dtype=np.float64)
+    T = a.shape[-1]
+    nf = -(-T // Np)
+    pad = [(0, 0)] * (a.ndim - 1) + [(0, nf * Np - T)]
+    per = np.pad(a, pad).reshape(a.shape[:-1] + (nf, Np)).max(axis=-1)
+    pad = [(0, 0)] * (a.ndim - 1) + [(before, after)]
+    win = np.lib.stride_tricks.sliding_window_view(np.pad(per, pad), before + after + 1, axis=-1).max(axis=-1)
+    return np.repeat(win, Np, axis=-1)[..., :T]
+
+
+def local_scale(signals, K, S, irs_of_source, W=W_ROW, threads=None):
+    """A_W, float64 (2, T_out): what float32 rounding of output sample n is measured against.
+    A = render_mix_whole(|x|, K, S, |irs|) - the same C oracle fed absolute inputs and absolute chunk IRs; the crossfade
+    weights are non-negative, so A[e, n] >= sum over sources and taps of |g[k]| |x[n - k]| - and
+    A_W[e, n] = max over |m - n| <= W of A[e, m]."""
+    class _Abs:
+        def __len__(self):
+            return len(signals)
+
+        def __getitem__(self, i):
+            return np.abs(np.asarray(signals[i], dtype=np.float64))
+
+    A = render_mix_whole(_Abs(), K, S, lambda i: np.abs(np.asarray(irs_of_source(i), dtype=np.float64)), threads=threads)
+    return widen_max(A, W)
+
+
+def compare_local(got, want, scale, K=None, tile=TILE):
+    """The worst ratio = |got - want| / (2^-24 scale) over the samples with scale > 0, and where it lies.  Half an ulp of
+    float32(want) is taken off the error first: the output cast itself is not under test.  got / want / scale: arrays
+    of one shape, the last axis time ((2, T) for a render, (T,) or (rows, T) for a row stage).  Returns a dict: ratio,
+    zeros_ok (wherever scale == 0, got is exactly +-0), finite (no NaN or Inf in got), ear (the flat index of the
+    leading axes), n, n_mod_K, n_mod_tile, chunk (None without K), got, want, scale (at the worst sample), samples,
+    zeros (the samples with scale == 0)."""
+    got = np.asarray(got, dtype=np.float64)
+    want = np.asarray(want, dtype=np.float64)
+    scale = np.asarray(scale, dtype=np.float64)
+    assert got.shape == want.shape == scale.shape and got.ndim >= 1, (got.shape, want.shape, scale.shape)
+    T = got.shape[-1]
+    got, want, scale = got.reshape(-1, T), want.reshape(-1, T), scale.reshape(-1, T)
+    finite = bool(np.isfinite(got).all())
+    half_ulp = 0.5 * np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
+    err = np.maximum(np.abs(got - want) - half_ulp, 0.0)
+    live = scale > 0
+    ratio = np.zeros_like(err)
+    np.divide(err, U32 * scale, out=ratio, where=live)
+    ratio[live & ~np.isfinite(got)] = np.inf
+    flat = int(np.argmax(ratio)) if ratio.size else 0
+    ear, n = divmod(flat, T) if T else (0, 0)
+    res = {"ratio": float(ratio.reshape(-1)[flat]) if ratio.size else 0.0,
+           "zeros_ok": bool((got[~live] == 0).all()), "finite": finite,
+           "ear": int(ear), "n": int(n), "n_mod_K": None if K is None else int(n % K), "n_mod_tile": int(n % tile),
+           "chunk": None if K is None else int(n // K), "samples": int(got.size), "zeros": int((~live).sum())}
+    if ratio.size:
+        res.update(got=float(got[ear, n]), want=float(want[ear, n]), scale=float(scale[ear, n]))
+    return res
+
+
+def describe_local(res):
+    """One line: how far off in units of 2^-24 of the local scale, and where."""
+    return (f"ratio {res['ratio']:.3g} over {res['samples']} samples ({res['zeros']} of scale 0, zeros_ok {res['zeros_ok']}); "
+            f"worst at row {res['ear']} n={res['n']} (n mod K={res['n_mod_K']}, n mod tile={res['n_mod_tile']}, chunk "
+            f"{res['chunk']}): got {res.get('got', 0.0):.9g}, want {res.get('want', 0.0):.9g}, scale {res.get('scale', 0.0):.6g}")
+
+
 def silent_support(signals, L, t_out=None):
     """Boolean mask of the output samples n whose whole input support [n - L + 1, n] is zero in every source (input
     samples past a source's end count as zero).  Length t_out, by default the longest source + L - 1."""
