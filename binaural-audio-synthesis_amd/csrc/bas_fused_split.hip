@@ -4,7 +4,7 @@
 // differently: equal to that kernel's output up to float32 summation order) - but ONE workgroup of eight waves per CU:
 //
 //   waves 4-7 ("stagers")  fetch the x window and the read plans of unit u + 1, write the x image and evaluate the 18 chunk
-//                          IRs into LDS buffer (u + 1) & 1 - latency-bound work that issues ~500 vector instructions;
+//                          IRs into LDS buffer (u + 1) & 1 - latency-bound work that issues ~400 vector instructions;
 //   waves 0-3 ("filters")  run the row steps of unit u on buffer u & 1 - 3 600 vector instructions per lane, no memory access but LDS;
 //   one s_barrier per unit hands the finished buffer over and the drained one back.
 //
@@ -373,30 +373,31 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
             __builtin_amdgcn_wave_barrier();                 // other lanes of this wave read the plan words below
 
             // ---- chunk IRs from the table: lanes 0-31 four adjacent taps of the left ear, lanes 32-63 of the right.
-            // Two halves of 8 reads are in flight at any time; slot i - 1 = (IR i-1, IR i - IR i-1) is stored as soon
+            // The 16 reads of one IR are in flight at a time; slot i - 1 = (IR i-1, IR i - IR i-1) is stored as soon
             // as IR i is known: both ears of two taps per 16-byte LDS write.  The regrouping of the ears is linear, so it is
             // done once per IR and the difference is formed on the regrouped values.
             {
                 const int m = seg0 + 4 * (lane & 31);
                 const int m_c = m < A.L ? m : A.L - 1;       // idle lanes evaluate a valid tap and drop it
                 const unsigned m4 = 4u * (unsigned)m_c;
-                const f32x4 live = f32x4{m < A.L ? 1.f : 0.f, m + 1 < A.L ? 1.f : 0.f, m + 2 < A.L ? 1.f : 0.f,
-                                         m + 3 < A.L ? 1.f : 0.f};             // taps >= L read as zero
                 const f32x4 *pl = plw + half * (BAS_PLANS_WORDS / 4);
                 f32x4 *dst = reinterpret_cast<f32x4 *>(hd) + slot_a * (HD_SLOT / 4) + tq;
-                FzHalf ha, hb;
                 f32x2 pa = f32x2{0.f, 0.f}, pb = pa;         // the previous IR, regrouped: (t_a L, t_a R), (t_b L, t_b R)
-                const f32x4 *pl_last = pl + (n_ev > 0 ? n_ev - 1 : 0) * PL4;
-                if (n_ev > 0) fz_issue<0>(tab, pl, m4, L4, ha);
-                // a real loop without branches in its body: the load counters then carry across iterations and each
-                // half is folded while the next one is in flight (the last iteration re-requests its own first half)
+                // The 16 reads of an IR go out together and are folded in order as they land (counted waits); nothing is in
+                // flight across iterations, so nothing moves between registers.  (The loop before kept the next IR's first half
+                // in flight while it folded this one's second; hipcc rotated that half through registers - 18 v_mov_b64 per
+                // IR - and put a full wait at the loop's top all the same: 99 vector instructions per IR, now 75, and the
+                // filter wave of the SIMD pays for every one of them.  Same reads, same order of the FMAs: DESIGN.md 3.2.1.)
                 for (int i = 0; i < n_ev; ++i) {
-                    const f32x4 *pl_next = pl + PL4 < pl_last ? pl + PL4 : pl_last;
+                    FzHalf ha, hb;
+                    fz_issue<0>(tab, pl, m4, L4, ha);
                     fz_issue<1>(tab, pl, m4, L4, hb);
                     f32x4 h = fz_finish<0>(pl, ha, f32x4{0.f, 0.f, 0.f, 0.f});
-                    fz_issue<0>(tab, pl_next, m4, L4, ha);
                     h = fz_finish<1>(pl, hb, h);
-                    if (!all_live) h *= live;                // (uniform)
+                    if (!all_live) {                         // (uniform) taps >= L read as zero.  A branch, kept one by the
+                        asm volatile("" ::: "memory");       // empty statement: as a select it ran for every IR of every L
+                        h *= f32x4{m < A.L ? 1.f : 0.f, m + 1 < A.L ? 1.f : 0.f, m + 2 < A.L ? 1.f : 0.f, m + 3 < A.L ? 1.f : 0.f};
+                    }
                     if (i == 0 && wv > 0) {                  // (uniform) the previous wave's last slot needs this IR
                         bnd[wv * 64 + lane] = h;
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(512, 1) void bas_render_fs_kernel(
                     }
                     pa = ca;
                     pb = cb;
-                    pl = pl_next;
+                    pl += PL4;
                 }
                 if (need_next) {                             // (uniform) IR slot_b comes from the next wave's LDS copy
                     const bool got = fz_wait_handover(flags + wv + 1, pass_id, A);   // it stored that IR first thing
