@@ -41,7 +41,9 @@ bas_scene_params_f64, _bands_f64,             elev, azim, gain, delay, logmag ro
 bas_resample_up_f64, bas_delaydiffs_f64       y; diffs, status
 
 Adding a case: write a function of one Run `r` (and its variant's parameters) that takes inputs with r.inp, written buffers
-with r.out / r.rows / r.ws, calls through r.call, and decorate it with @case(name, entry points, variants).
+with r.out / r.rows / r.ws, calls through r.call, and decorate it with @case(name, entry points, variants).  Tell r.inp what of
+an input bas.h calls readable (owned, valid) and which of its strides the call passes (gaps, align), and pass the tensor's own
+strides: tests/test_gpu_read_bounds.py runs every case here again with its inputs laid out by that, among zeros and among NaNs.
 tests/test_guards_cpu.py fails until every `int bas_*(` of include/bas.h is in a case here, in COVERED_ELSEWHERE (with the
 existing sentinel test) or in NOTHING_TO_WRITE (with the reason).
 """
@@ -105,8 +107,10 @@ class Run:
         self.outs, self.guards, self.inputs, self.rcs = {}, [], [], []
         self.stream = None if dry or self.dev.type != "cuda" else bas._hip.current_stream(self.dev)
 
-    def inp(self, name, a, dtype=None):
-        """A read-only input on the device; compared with its copy after the call."""
+    def inp(self, name, a, dtype=None, owned=None, valid=None, gaps=None, align=1):
+        """A read-only input on the device; compared with its copy after the call.  owned, valid, gaps, align say what
+        of it the callee may read and which of its strides the call passes (guards.input_view): nothing here depends on
+        them, the read-guarded runs of tests/test_gpu_read_bounds.py lay the input out by them."""
         t = torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a)
         t = (t if dtype is None else t.to(dtype)).to(self.dev).contiguous()
         self.inputs.append((name, t, t.clone()))
@@ -394,7 +398,7 @@ def render_mix(r, name, accumulate, profiled):
     assert lib().bas_render_kernel_name(n_src, T_in, K, S, L).decode() == kernel
     hx, e, a = host_scene(n_src, T_in, K, False, 11)
     t = table(r, L, 8)
-    x = r.inp("x", hx)
+    x = r.inp("x", hx, gaps={0: None}, align=4)
     nq = T_in // K + 1
     n = n_src * nq
     idx, w = sphere.interpolation_params_batch(e, a)
@@ -463,7 +467,7 @@ def render_fused(r, name, form):
     assert lib().bas_render_fused_kernel_name(*shape).decode() == kernel and fused_site(*shape) == site
     hx, e, a = host_scene(n_src, T_in, K, True, 12)
     t = table(r, L, 8)
-    x = r.inp("x", hx)
+    x = r.inp("x", hx, gaps={0: None}, align=4)
     plans = fused_plans(r, t, e, a)
     T_out = T_in + L - 1
     wb = lib().bas_render_fused_workspace_bytes(*shape)
@@ -541,7 +545,7 @@ def stream_epilogue(r, n_src, K, halo, B, gained):
     gap = elev.stride(0) - (nh + nb)
     azim = r.rows("azim", n_src, nh + nb, dtype=F64, init=ang[1], gap=gap)
     gain = r.rows("gain", n_src, nh + nb, dtype=F64, init=ang[2], gap=gap)
-    y = r.inp("y", rng.standard_normal((2, halo + B + 7)).astype(np.float32))
+    y = r.inp("y", rng.standard_normal((2, halo + B + 7)).astype(np.float32), owned=halo + B, gaps={0: None})
     last = r.out("last", (2, n_src), F64)
     gain_last = r.out("gain_last", (n_src,), F64, init=np.zeros(n_src))
     rpeak = r.out("running_peak", (1,), init=[0.25])
@@ -565,7 +569,7 @@ def stream_batch_epilogue_gain(r, G, n_src, K, halo, B):
     gap = elev.stride(0) - Q
     azim = r.rows("azim", n_src, Q, dtype=F64, init=ang[1], gap=gap)
     gain = r.rows("gain", n_src, Q, dtype=F64, init=ang[2], gap=gap)
-    y = r.inp("y", rng.standard_normal((2, T_in + 7)).astype(np.float32))
+    y = r.inp("y", rng.standard_normal((2, T_in + 7)).astype(np.float32), owned=T_in, gaps={0: None})
     last = r.out("last", (G, 2, n_src), F64)
     gain_last = r.out("gain_last", (G, n_src), F64)
     peaks = r.out("peaks", (G,), init=np.abs(rng.standard_normal(G)))
@@ -611,8 +615,9 @@ def batch_pack(r, K, L, form):
     n_items, n_src, N = len(lengths), 3, 2 * K + 3
     n_q_max = -(-N // K) + 2
     rng = np.random.default_rng(K + L)
-    sig = r.inp("sig", (rng.standard_normal((n_items, n_src, N)) + 1.0).astype(np.float32))
-    meta = r.inp("meta", np.stack([lay.lengths, lay.offsets]).astype(np.int64))
+    sig = r.inp("sig", (rng.standard_normal((n_items, n_src, N)) + 1.0).astype(np.float32),
+                valid=np.repeat(np.minimum(lay.lengths, N)[:, None], n_src, axis=1))
+    meta = r.inp("lengths", np.asarray(lay.lengths, np.int64)), r.inp("offsets", np.asarray(lay.offsets, np.int64))
     ang = rng.standard_normal((3, n_items, n_src, n_q_max))
     e, a, g = r.inp("elev", ang[0]), r.inp("azim", ang[1]), r.inp("gain", ang[2])
     x_stride = -(-lay.T_in // 4) * 4 + 4
@@ -655,7 +660,8 @@ def peak_rule(r, n):
 def mix_partials(r, n):
     rng = np.random.default_rng(n + 1)
     n_parts, stride = 3, n + 5
-    parts = r.inp("parts", rng.standard_normal((n_parts, stride)).astype(np.float32))
+    parts = r.inp("parts", rng.standard_normal((n_parts, stride)).astype(np.float32), owned=n, gaps={0: None})
+    stride = parts.stride(0)
     for res in range(4):
         y = r.out(f"y{res}", (n,), offset=4 * res)
         peak = r.out(f"peak{res}", (1,), init=[0.0])
@@ -685,9 +691,11 @@ def delay_rows(r, interp, Hh, use_lengths):
         rng = np.random.default_rng(T + interp)
         nbnd = (T - 1) // K + 2
         xs = Hh + T + 3
-        x = r.inp("x", rng.standard_normal((G, n_src, xs)).astype(np.float32))
-        delay = r.inp("delay", rng.uniform(0.0, 20.0, (G, n_src, nbnd)))
-        lengths = r.inp("lengths", ragged(rng, G * n_src, T)) if use_lengths else None
+        hx, hd = rng.standard_normal((G, n_src, xs)).astype(np.float32), rng.uniform(0.0, 20.0, (G, n_src, nbnd))
+        hl = ragged(rng, G * n_src, T) if use_lengths else None
+        x = r.inp("x", hx, owned=Hh + T, valid=Hh + hl.reshape(G, n_src) if use_lengths else None, gaps={0: None, 1: None})
+        delay = r.inp("delay", hd, gaps={0: None, 1: None})
+        lengths = r.inp("lengths", hl) if use_lengths else None
         for res in range(4):
             y = r.rows(f"y{T}_{res}", n_src, T, offset=4 * res, groups=G)
             r.call("bas_delay_rows_f32", P(x) + 4 * Hh, x.stride(0), x.stride(1), Hh, P(lengths), P(delay), delay.stride(0),
@@ -714,9 +722,12 @@ def color_rows(r, M, static, use_lengths):
     for T in ROW_TS:
         rng = np.random.default_rng(T + M)
         nbnd = (T - 1) // K + 2
-        x = r.inp("x", rng.standard_normal((G, n_src, Hc + T + 3)).astype(np.float32))
-        color = r.inp("color", rng.standard_normal((G, n_src, 1 if static else nbnd, M)).astype(np.float32))
-        lengths = r.inp("lengths", ragged(rng, G * n_src, T)) if use_lengths else None
+        hx = rng.standard_normal((G, n_src, Hc + T + 3)).astype(np.float32)
+        hc = rng.standard_normal((G, n_src, 1 if static else nbnd, M)).astype(np.float32)
+        hl = ragged(rng, G * n_src, T) if use_lengths else None
+        x = r.inp("x", hx, owned=Hc + T, valid=Hc + hl.reshape(G, n_src) if use_lengths else None, gaps={0: None, 1: None})
+        color = r.inp("color", hc, gaps={0: None, 1: None, 2: None})
+        lengths = r.inp("lengths", hl) if use_lengths else None
         for res in range(4):
             y = r.rows(f"y{T}_{res}", n_src, T, offset=4 * res, groups=G)
             r.call("bas_color_rows_f32", P(x) + 4 * Hc, x.stride(0), x.stride(1), Hc, P(lengths), P(color), color.stride(0),
@@ -729,8 +740,8 @@ def bus_mix(r, static, n_src):
     for T in ROW_TS:
         rng = np.random.default_rng(T + n_src)
         nbnd = (T - 1) // K + 2
-        x = r.inp("x", rng.standard_normal((G, n_src, T + (T % 3))).astype(np.float32))
-        send = r.inp("send", rng.standard_normal((G, n_src, 1 if static else nbnd)))
+        x = r.inp("x", rng.standard_normal((G, n_src, T + (T % 3))).astype(np.float32), owned=T, gaps={0: None, 1: None})
+        send = r.inp("send", rng.standard_normal((G, n_src, 1 if static else nbnd)), gaps={0: None, 1: None})
         for res in range(4):
             bus = r.rows(f"bus{T}_{res}", G, T, offset=4 * res)
             r.call("bas_bus_mix_f32", P(x), x.stride(0), x.stride(1), P(send), send.stride(0), send.stride(1),
@@ -740,7 +751,7 @@ def bus_mix(r, static, n_src):
 # ---- late reverberation ----------------------------------------------------------------------------------------------------
 def reverb_tail(r, Lr, Np, name="tail"):
     rng = np.random.default_rng(Lr + Np)
-    h = r.inp(name + ".h", (rng.standard_normal((2, Lr + 3)) / Lr ** 0.5).astype(np.float32))
+    h = r.inp(name + ".h", (rng.standard_normal((2, Lr + 3)) / Lr ** 0.5).astype(np.float32), owned=Lr, gaps={0: None})
     n = lib().bas_long_fir_tail_floats(Lr, Np)
     assert n > 0
     tail = r.out(name, (n,))
@@ -764,8 +775,8 @@ def long_fir(r, Np, Lr, T_out, Hb):
     r.watch("tail (read by the convolver)", tail)
     rng = np.random.default_rng(T_out)
     T_bus = T_out - 10 if T_out > 20 else T_out
-    bus = r.inp("bus", rng.standard_normal((n_bus, Hb + T_bus + 2)).astype(np.float32))
-    y_in = r.inp("y_in", rng.standard_normal((n_bus, 2, T_out)).astype(np.float32))
+    bus = r.inp("bus", rng.standard_normal((n_bus, Hb + T_bus + 2)).astype(np.float32), owned=Hb + T_bus, gaps={0: None})
+    y_in = r.inp("y_in", rng.standard_normal((n_bus, 2, T_out)).astype(np.float32), gaps={0: None, 1: None})
     wb = lib().bas_long_fir_workspace_bytes(n_bus, T_out, Lr, Np)
     assert wb > 0
     for res, with_y in ((0, 1), (1, 0), (2, 1), (3, 0)):
@@ -798,7 +809,7 @@ def limit(r, layout, T, A, streamed):
     G, hold = 3, 5
     assert limiter.TILE == 1024
     rng = np.random.default_rng(T + A)
-    y = r.inp("y", rng.standard_normal((G, T, 2)).astype(np.float32))
+    y = r.inp("y", rng.standard_normal((G, T, 2)).astype(np.float32), gaps={0: None, 1: 2})     # frames of 2 floats, or of 4
     out, (sg, st, se), _ = out_layout(r, "out", layout, G, T)
     red = r.out("reduction", (G + 4,), init=np.ones(G + 4))
     peak = r.out("peak", (G + 4,), init=np.zeros(G + 4))
@@ -821,7 +832,7 @@ def limit(r, layout, T, A, streamed):
 def meter(r, G, T, streamed):
     fs, hop = 8000, 800
     rng = np.random.default_rng(G + T)
-    y = r.inp("y", rng.standard_normal((G, T, 2)).astype(np.float32))
+    y = r.inp("y", rng.standard_normal((G, T, 2)).astype(np.float32), gaps={0: None, 1: 2})     # frames of 2 floats, or of 4
     max_hops = T // hop + 1
     energy = r.strided("energy", (G, 2, max_hops), (2 * (max_hops + 3) + 1, max_hops + 3, 1), F64, offset=8,
                        init=np.zeros((G, 2, max_hops)))
@@ -845,7 +856,7 @@ def meter(r, G, T, streamed):
 def ambi_matrices(r, order, V, G, nb):
     C, J = (order + 1) ** 2, 20
     rng = np.random.default_rng(order + V)
-    head = r.inp("head", rng.standard_normal((G, nb, 5)))
+    head = r.inp("head", rng.standard_normal((G, nb, 5)), owned=4, gaps={0: None, 1: None})
     D, Q = r.inp("D", rng.standard_normal((V, C))), r.inp("Q", rng.standard_normal((J, C)))
     S = rng.standard_normal((J, 3))
     S = r.inp("S", S / np.linalg.norm(S, axis=1, keepdims=True))
@@ -859,8 +870,8 @@ def ambi_encode_gains(r, order, n_src, G, nb):
     C = (order + 1) ** 2
     rng = np.random.default_rng(order + n_src)
     e, a = angles(rng, (G, n_src, nb + 2))
-    elev, azim = r.inp("elev", e), r.inp("azim", a)
-    gain = r.inp("gain", rng.uniform(-2, 2, (G, n_src, nb)))
+    elev, azim = r.inp("elev", e, owned=nb, gaps={0: 3, 1: 2}), r.inp("azim", a, owned=nb, gaps={0: 3, 1: 2})   # (one stride pair)
+    gain = r.inp("gain", rng.uniform(-2, 2, (G, n_src, nb)), gaps={0: None, 1: None})
     scale = (ctypes.c_double * (order + 1))(*[1.0 / (2 * l + 1) ** 0.5 for l in range(order + 1)])
     bank = r.rows("e", nb, n_src * C, offset=4 * (n_src % 4), groups=G)
     r.call("bas_ambi_encode_gains_f32", P(elev), P(azim), elev.stride(0), elev.stride(1), P(gain), gain.stride(0), gain.stride(1),
@@ -873,9 +884,9 @@ def ambi_encode(r, C, n_src, static, with_base):
     for T in (1, 5, 1023, 1027, 2500):
         rng = np.random.default_rng(T + C)
         nbnd = (T - 1) // K + 2
-        x = r.inp("x", rng.standard_normal((G, n_src, T + 1)).astype(np.float32))
-        bank = r.inp("e", rng.standard_normal((G, 1 if static else nbnd, n_src * C)).astype(np.float32))
-        base = r.inp("base", rng.standard_normal((G, C, T)).astype(np.float32)) if with_base else None
+        x = r.inp("x", rng.standard_normal((G, n_src, T + 1)).astype(np.float32), owned=T, gaps={0: None, 1: None})
+        bank = r.inp("e", rng.standard_normal((G, 1 if static else nbnd, n_src * C)).astype(np.float32), gaps={0: None, 1: None})
+        base = r.inp("base", rng.standard_normal((G, C, T)).astype(np.float32), gaps={0: None, 1: None}) if with_base else None
         for res in range(4):
             y = r.rows(f"y{T}_{res}", C, T, offset=4 * res, groups=G)
             r.call("bas_ambi_encode_f32", P(x), x.stride(0), x.stride(1), P(bank), bank.stride(0), 0 if static else bank.stride(1),
@@ -887,10 +898,10 @@ def ambi_encode(r, C, n_src, static, with_base):
 def head_relative(r, G, n_src, nb):
     rng = np.random.default_rng(G + nb)
     e, a = angles(rng, (G, n_src, nb + 1))
-    elev, azim = r.inp("elev", e), r.inp("azim", a)
+    elev, azim = r.inp("elev", e, owned=nb, gaps={0: 5, 1: 1}), r.inp("azim", a, owned=nb, gaps={0: 5, 1: 1})   # (one stride pair)
     head = rng.standard_normal((G, nb, 6))
     head[0, 0, 1:3] = 0.0                                # a pure yaw
-    head = r.inp("head", head)
+    head = r.inp("head", head, owned=4, gaps={0: None, 1: None})
     eo = r.rows("elev_out", n_src, nb, dtype=F64, offset=8, groups=G)
     ao = r.rows("azim_out", n_src, nb, dtype=F64, groups=G, gap=eo.stride(1) - nb)
     assert ao.stride() == eo.stride()
@@ -905,10 +916,10 @@ def scene_params(r, form, room, G, nb):
     n_src, n_bands, n_screens = 3, 3, 2
     rng = np.random.default_rng(G + nb)
     size = np.array([4.0, 5.0, 3.0])
-    pos = r.inp("pos", rng.uniform(0.3, 2.7, (G, n_src, nb, 4)))
-    lpos = r.inp("lpos", rng.uniform(0.5, 2.5, (G, nb, 3)))
-    head = r.inp("head", rng.standard_normal((G, nb, 4)))
-    sg = r.inp("src_gain", rng.uniform(0.5, 1.5, (G, n_src, nb)))
+    pos = r.inp("pos", rng.uniform(0.3, 2.7, (G, n_src, nb, 4)), owned=3, gaps={0: None, 1: None, 2: None})
+    lpos = r.inp("lpos", rng.uniform(0.5, 2.5, (G, nb, 3)), gaps={0: None, 1: None})
+    head = r.inp("head", rng.standard_normal((G, nb, 4)), gaps={0: None, 1: None})
+    sg = r.inp("src_gain", rng.uniform(0.5, 1.5, (G, n_src, nb)), gaps={0: None, 1: None})
     n_img = 3 if room else 1
     room_size = r.inp("room_size", size) if room else None
     images = r.inp("images", np.array([[0, 0, 0], [1, 0, 0], [0, -1, 2]], np.int32)) if room else None
@@ -927,8 +938,8 @@ def scene_params(r, form, room, G, nb):
     if form == "plain":
         r.call("bas_scene_params_f64", *front, *outs, r.stream)
         return
-    orient = r.inp("orient", rng.standard_normal((G, n_src, nb, 4)))
-    pattern = r.inp("pattern", rng.uniform(0.0, 1.0, (n_src, n_bands)))
+    orient = r.inp("orient", rng.standard_normal((G, n_src, nb, 4)), gaps={0: None, 1: None, 2: None})
+    pattern = r.inp("pattern", rng.uniform(0.0, 1.0, (n_src, n_bands)), gaps={0: None})
     air = r.inp("air", rng.uniform(0.0, 0.01, n_bands))
     img_logmag = r.inp("img_logmag", rng.uniform(-1.0, 0.0, (n_img, n_bands)))
     bands = (P(orient), orient.stride(0), orient.stride(1), orient.stride(2), P(pattern), pattern.stride(0), P(air),
@@ -940,7 +951,7 @@ def scene_params(r, form, room, G, nb):
         return
     e1, e2 = np.array([0.5, 0.0, 0.0]), np.array([0.0, 0.0, 0.6])
     screens = r.inp("screens", np.stack([np.concatenate([[2.0, 2.5, 1.5], e1, e2]), np.concatenate([[1.0, 1.2, 1.0], e2, e1])]))
-    transmission = r.inp("transmission", rng.uniform(0.0, 1.0, (n_screens, n_bands)))
+    transmission = r.inp("transmission", rng.uniform(0.0, 1.0, (n_screens, n_bands)), gaps={0: None})
     fresnel = r.inp("fresnel", 2.0 * np.array([250.0, 1000.0, 4000.0]) / 343.0)
     r.call("bas_scene_params_occluded_f64", *front, *bands, P(screens), P(transmission), transmission.stride(0), P(fresnel),
            n_screens, *outs, *louts, r.stream)
