@@ -186,8 +186,18 @@ SIGNATURES = {
                                      _c_long, _c_int, _c_void_p, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_void_p]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/bas_rate.h (sample-rate conversion, DESIGN.md §3.24: the
+# same library, a header of its own)
+RATE_SIGNATURES = {
+    "bas_rate_produced": (_c_long, [_c_long, _c_int, _c_int, _c_int]),
+    "bas_rate_needed": (_c_long, [_c_long, _c_int, _c_int, _c_int]),
+    "bas_rate_convert_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_int, _c_int, _c_long, _c_long, _c_void_p,
+                                      _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_long, _c_long, _c_long, _c_long, _c_long,
+                                      _c_void_p]),
+}
+
 _lib = None
-ABI_VERSION = 7                                                      # BAS_ABI_VERSION of include/bas.h
+ABI_VERSION = 7                                                     # BAS_ABI_VERSION of include/bas.h
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libbas_hip_diag.so")   # -DBAS_DIAG build: reads BAS_FORCE_KERNEL (tests only)
 
 
@@ -228,9 +238,10 @@ def _load(path):
             f"or `make -C {os.path.dirname(path)}`.  There is no CPU fallback.")
     import torch                                # noqa: F401  first: PyTorch-ROCm brings its own libamdhip64, and the library
     handle = ctypes.CDLL(path)                  # must bind to THAT runtime (loaded the other way round a second HIP runtime
-    for name, (res, args) in SIGNATURES.items():   # comes up beside torch's and sees no device)
-        fn = getattr(handle, name)              # AttributeError if the symbol is not exported
-        fn.restype, fn.argtypes = res, args
+    for table in (SIGNATURES, RATE_SIGNATURES):    # comes up beside torch's and sees no device)
+        for name, (res, args) in table.items():
+            fn = getattr(handle, name)          # AttributeError if the symbol is not exported
+            fn.restype, fn.argtypes = res, args
     if handle.bas_version() != ABI_VERSION:
         raise RuntimeError(f"{os.path.basename(path)} ABI version {handle.bas_version()} != {ABI_VERSION}")
     return handle

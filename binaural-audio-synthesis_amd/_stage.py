@@ -53,6 +53,20 @@ def stereo_device(t, name, G=None, device=None):
     return t3
 
 
+# ---- rows -------------------------------------------------------------------------------------------------------------
+def rows_host(x, finite=True):
+    """x [..., n] (at least one dimension) as contiguous finite float32 on the host; ValueError otherwise.  finite=False:
+    NaN and Inf pass, as in stereo_host."""
+    a = np.asarray(host_array(x))
+    if a.ndim < 1:
+        raise ValueError("x must have at least one dimension [..., n]")
+    with np.errstate(over="ignore"):
+        x32 = np.ascontiguousarray(a, dtype=np.float32)
+    if finite and not np.isfinite(x32).all():
+        raise ValueError("x must be finite")
+    return x32
+
+
 # ---- views ------------------------------------------------------------------------------------------------------------
 def span(t):
     """[first, last + 1) byte addresses of a tensor's elements (strides >= 0, at least one element)."""
