@@ -4,7 +4,7 @@ Public surface mirrors the reference's apply_hrtf.py / sphere.py for the path
 load_irs_and_delaydiffs -> interpolate_2d -> make_signal_move_2d; all arithmetic
 runs in the C-ABI HIP library built from csrc/ (see include/bas.h).
 """
-from . import synth, sphere, _hip, apply_hrtf, distributed, stream, batch, stream_batch, scene, reverb, limiter, ambisonics, loudness, rate  # noqa: F401
+from . import synth, sphere, _hip, apply_hrtf, distributed, stream, batch, stream_batch, scene, reverb, limiter, ambisonics, loudness, rate, output  # noqa: F401
 from .batch import render_batch, make_signal_move_2d_batch  # noqa: F401
 from .stream import StreamRenderer  # noqa: F401
 from .stream_batch import StreamBatchRenderer  # noqa: F401
@@ -13,6 +13,8 @@ from .reverb import LateTail, late_tail  # noqa: F401
 from .limiter import limit, StreamLimiter  # noqa: F401
 from .loudness import measure, StreamMeter, normalize_loudness  # noqa: F401
 from .rate import convert_rate, StreamRateConverter  # noqa: F401
+from .output import (OutputFilter, filter_output, StreamOutputFilter, headphone_eq, crosstalk_canceller,  # noqa: F401
+                     speaker_plant)
 from .ambisonics import render_bed, BedStream, encode_bed, BedEncoder  # noqa: F401
 from .apply_hrtf import (  # noqa: F401
     load_irs_and_delaydiffs, irs_and_delaydiffs, interpolate_2d, interpolate_2d_deg, interpolate_2d_batch,
