@@ -319,6 +319,23 @@ def render_device(x, chunksize, subchunksize, H, tbl_L, normalize="mix", out=Non
     return y, peak
 
 
+def fused_serves(x, tbl, chunksize, subchunksize):
+    """Whether the fused kernels (chunk IRs evaluated inside the FIR kernel) render x [n_src, T_in] with this table: a
+    shape they serve, a table of U >= 4 (the read plans' form), rows 16-byte aligned.  The one rule of every renderer;
+    plans for the CURRENT device (callers bring the tensor's device: _hip.on_device)."""
+    n_src, t_in = x.shape
+    return bool(_hip.lib().bas_render_fused_supported(n_src, t_in, chunksize, subchunksize, tbl.L)) and \
+        tbl.upsampling >= 4 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
+
+
+def render_workspace_bytes(n_src, t_in, chunksize, subchunksize, L):
+    """Render workspace of a window of n_src x t_in inputs that serves whichever path renders it: the larger of the
+    stored-IR and the fused path's."""
+    lib = _hip.lib()
+    return max(lib.bas_render_workspace_bytes(n_src, t_in, chunksize, subchunksize, L),
+               lib.bas_render_fused_workspace_bytes(n_src, t_in, chunksize, subchunksize, L))
+
+
 @_hip.on_device_of("x")
 def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix", out=None, events=None,
                          ws=None, ws_plans=None, fused=None, angles=None, n_queries=None, want_peak=True, check=False,
@@ -343,8 +360,7 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     if normalize not in ("mix", "none"):
         raise ValueError("normalize must be 'mix' or 'none'")
     if fused is None or fused:                                # default: fused wherever the kernel serves the shape
-        fused = bool(lib.bas_render_fused_supported(n_src, t_in, chunksize, subchunksize, tbl.L)) and \
-            tbl.upsampling >= 4 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0
+        fused = fused_serves(x, tbl, chunksize, subchunksize)
     n_q = idx.shape[0] if idx is not None else n_queries
     if plans_ready and not fused:
         raise ValueError("plans_ready: this shape is not served by the fused kernels (they are the ones that read plans)")

@@ -28,7 +28,7 @@
 #include "bas_plan.h"
 #include "bas_fir.h"
 #include "bas_fused.h"
-#include <stdlib.h>
+#include <string.h>
 
 #ifdef BAS_STAMPS
 // Diagnostic build only (make stamps): per-wave totals of the pass phases in 10 ns ticks (s_memrealtime).
@@ -445,16 +445,12 @@ extern "C" int bas_debug_read_fz_stamps(unsigned long long *host, size_t count) 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct FzPlan {
-    int nw;                    // waves per workgroup: 4 or 1 (0: shape not served)
-    int split;                 // one workgroup of 4 filter + 4 stager waves per CU (bas_fused_split.hip)
-    int quad;                  // four waves per tile of 2048, the row steps dealt over them (bas_fused_quad.hip)
-    int honly;                 // LDS rows hold (h_L, h_R) only (chunk sizes below ~448)
-    int tile, nslots, spw;
-    long n_tiles, units_total;
-    int n_wg, units_per_wg, parts_per_wg;
-    size_t lds_bytes, slab_bytes;
-};
+// The rows of the kernel table (bas_dispatch.h)
+#define FZ_KEY(nw, honly) (10 * (nw) + (honly))
+#define FZ_ROW(pub, nw, honly)                                                                                             \
+    {"bas_render_fz_kernel<" #nw ", " #honly ">", "bas_render_fz_kernel<" pub ">",                                          \
+     reinterpret_cast<const void *>(bas_render_fz_kernel<nw, honly>), 64 * nw, FZ_KEY(nw, honly), nw | (honly << 4)}
+static const BasKernelRow fz_rows[] = {FZ_ROW("4,0", 4, false), FZ_ROW("1,0", 1, false), FZ_ROW("4,1", 4, true)};   // (code object order)
 
 static int fz_slots(int nw, int K) {                         // chunk slots a window of this tile can touch (any alignment)
     const int rows = 2048 * nw / 32 + HD_HALO;
@@ -505,30 +501,26 @@ static int fz_slots_exact(int nw, int K, int Lp, long n_tiles) {
     return worst;
 }
 
-static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L);
+static BasPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L, const BasDiag &D);
 
 // The plan of a shape is asked for three times per render (supported?, workspace size, launch) and the streaming
-// renderer renders the same shape block after block: remember the last one per thread.
-static FzPlan fz_plan(int n_src, long T_in, int K, int S, int L) {
-    struct Key {
-        int n_src, K, S, L, cus;
-        long T_in;
-    };
-    static thread_local Key last_key = {-1, 0, 0, 0, 0, 0};
-    static thread_local FzPlan last_plan = {};
+// renderer renders the same shape block after block: remember the last one per thread (keyed on the diagnostic build's
+// overrides too: they may change between calls).
+static BasPlan fz_plan(int n_src, long T_in, int K, int S, int L, const BasDiag &D) {
+    struct Key { int n_src, K, S, L, cus; long T_in; BasDiag D; };
+    static thread_local Key last_key = {-1, 0, 0, 0, 0, 0, {}};
+    static thread_local BasPlan last_plan = {};
     const int cus = bas_device_cus();
-#ifndef BAS_DIAG                                             // (the diagnostic build's BAS_FZ_NW may change between calls)
     if (last_key.n_src == n_src && last_key.T_in == T_in && last_key.K == K && last_key.S == S && last_key.L == L &&
-        last_key.cus == cus)
+        last_key.cus == cus && !memcmp(&last_key.D, &D, sizeof D))
         return last_plan;
-#endif
-    last_plan = fz_plan_uncached(n_src, T_in, K, S, L);
-    last_key = Key{n_src, K, S, L, cus, T_in};
+    last_plan = fz_plan_uncached(n_src, T_in, K, S, L, D);
+    last_key = Key{n_src, K, S, L, cus, T_in, D};
     return last_plan;
 }
 
-static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
-    FzPlan p = {};
+static BasPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L, const BasDiag &D) {
+    BasPlan p = {};
     // subchunks: multiples of 32 (a row of 32 inputs meets one crossfaded tap set), or 16 / 8 - two / four sets per row, which only the
     // unit blocks of the split-role kernel hold (scenes with more than one (tile of 8192, source) unit per CU; L = 97 .. 104, 121 .. 128,
     // or several whole 128-tap segments: bas_fs_unit_len)
@@ -537,6 +529,7 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
     if ((S % 32 != 0 && !s16) || K % S != 0) return p;
     const long T_out = T_in + L - 1;
     const int cus = bas_device_cus();
+    const bool force_nw = D.fz_nw != BAS_DIAG_UNSET;         // diagnostic build only: force the tile size
     if (fz_slots(4, K) > FZ_MAXSLOTS) {                      // K < 448 or so: h-only rows, four-wave workgroups, two per CU
         if (s16) return p;
         const long n_tiles = (T_out + 8191) / 8192;
@@ -544,46 +537,30 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
         const int spw = (rows_h + 3) / 4;
         const int xrows = 8192 / 32 + HD_HALO;
         const size_t lds = (size_t)(8 * (xrows + 1) * 4 + ((rows_h * HO_SLOT + 3) & ~3) + 4 * FZ_HO_MAXEV * 2 * BAS_PLANS_WORDS) * sizeof(float);
-        const long units = n_tiles * n_src;
-        if (spw > FZ_HO_MAXEV || 2 * lds > 160 * 1024 || units < 2L * cus) return p;   // (few sources: the stored-IR path)
-#ifdef BAS_DIAG
-        if (getenv("BAS_FZ_NW") && atoi(getenv("BAS_FZ_NW")) != 4) return p;
-#endif
-        p.nw = 4;
-        p.honly = 1;
-        p.tile = 8192;
+        if (spw > FZ_HO_MAXEV || 2 * lds > 160 * 1024 || n_tiles * n_src < 2L * cus) return p;   // (few sources: the stored-IR path)
+        if (force_nw && D.fz_nw != 4) return p;
+        p.row = bas_find_row(fz_rows, FZ_KEY(4, true));
         p.nslots = rows_h - 1;
         p.spw = spw;
-        p.n_tiles = n_tiles;
-        p.units_total = units;
-        bas_deal_units(units, 2L * cus, n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg, &p.slab_bytes);
         p.lds_bytes = lds;
+        bas_plan_deal(p, 8192, T_out, n_src, 2L * cus, true);
         return p;
     }
     // largest tile that still gives every workgroup slot of the chip a unit; scenes with few sources (one source
     // x 10 s is 54 tiles of 8192) take smaller tiles and with them more, narrower workgroups
     const int cand[2] = {4, 1};                              // (a tile of 4096 never wins: same number of busy waves as 2048)
-#ifdef BAS_DIAG
-    const char *force_nw = getenv("BAS_FZ_NW");              // diagnostic build only: force the tile size
-#endif
     for (int ci = 0; ci < 2; ++ci) {
         const int nw = cand[ci];
-#ifdef BAS_DIAG
-        if (force_nw && atoi(force_nw) != nw) continue;
-#endif
-        const long n_tiles_nw = (T_out + 2048L * nw - 1) / (2048L * nw);
-#ifdef BAS_DIAG
-        if (nw == 4 && !force_nw) {
-#else
-        if (nw == 4) {                                       // short signals (real-time blocks): a tile of 8192 that is mostly past the
-#endif
+        if (force_nw && D.fz_nw != nw) continue;
+        const long n_tiles = (T_out + 2048L * nw - 1) / (2048L * nw);
+        if (nw == 4 && !force_nw) {                          // short signals (real-time blocks): a tile of 8192 that is mostly past the
             const long n1 = (T_out + 2047) / 2048;           // end of the output costs as much as a full one - narrow tiles then
-            if (n1 < 3 * n_tiles_nw) continue;               // useful fraction T_out / (n_tiles_nw 8192) below 3/4 of the narrow tiles'
-                                                             // T_out / (n1 2048), as 4 n1 2048 < 3 n_tiles_nw 8192: no product with T_out
+            if (n1 < 3 * n_tiles) continue;                  // useful fraction T_out / (n_tiles 8192) below 3/4 of the narrow tiles'
+                                                             // T_out / (n1 2048), as 4 n1 2048 < 3 n_tiles 8192: no product with T_out
             // small scenes: the tiles of 2048 fit in FZ_QUAD_ROUNDS rounds of four-wave workgroups (below): narrow tiles
             if (FZ_QUAD && n1 * n_src <= (long)FZ_QUAD_ROUNDS * 2 * cus) continue;
         }
-        const int nslots = fz_slots_exact(nw, K, (L + 7) & ~7, n_tiles_nw);
+        const int nslots = fz_slots_exact(nw, K, (L + 7) & ~7, n_tiles);
         const int maxev = nw == 4 ? 6 : 7;
         const int spw = (nslots + nw - 1) / nw;                 // (h-only rows only; the (h0, d) path deals nslots + 1 IRs)
         if ((nslots + 1 + nw - 1) / nw > maxev) continue;
@@ -595,20 +572,15 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
         long wg_per_cu = (long)(160 * 1024 / lds);
         const long by_waves = 8 / nw;                        // two waves per SIMD (register budget of the row step)
         if (wg_per_cu > by_waves) wg_per_cu = by_waves;
-#ifdef BAS_DIAG
-        if (getenv("BAS_FZ_WG_PER_CU")) wg_per_cu = atoi(getenv("BAS_FZ_WG_PER_CU"));   // diagnostic: a workgroup alone on its CU
-#endif
+        if (D.fz_wg_per_cu != BAS_DIAG_UNSET) wg_per_cu = D.fz_wg_per_cu;   // diagnostic: a workgroup alone on its CU
         if (wg_per_cu < 1) continue;
         long slots = wg_per_cu * cus;
-        const long n_tiles = (T_out + 2048L * nw - 1) / (2048L * nw);
         const long units = n_tiles * n_src;
         // split roles (one workgroup per CU, the staging of unit u + 1 under the FIR of unit u): worth it as soon as some
         // workgroup has two units (the first unit's staging is exposed); needs two (x image, taps) buffers in LDS
         const bool split_fits = FZ_SPLIT && nw == 4 && wg_per_cu == 2 && bas_fs_lds_bytes(nslots) <= 160 * 1024;
         bool split = split_fits && units > (long)FZ_SPLIT_MIN_UNITS * cus;
-#ifdef BAS_DIAG
-        if (getenv("BAS_FZ_SPLIT")) split = split_fits && atoi(getenv("BAS_FZ_SPLIT")) != 0;   // (1: also for small scenes)
-#endif
+        if (D.fz_split != BAS_DIAG_UNSET) split = split_fits && D.fz_split != 0;   // (1: also for small scenes)
         if (split) slots = cus;
         // four waves per tile of 2048 (staging and row steps dealt over them: a unit takes a third of the one-wave kernel's
         // time, a CU holds two such workgroups instead of eight one-wave ones): for scenes whose units fit in a few rounds
@@ -618,64 +590,66 @@ static FzPlan fz_plan_uncached(int n_src, long T_in, int K, int S, int L) {
             quad_lds = bas_fq_lds_bytes(nslots);
             const long per_cu = quad_lds * 2 <= 160 * 1024 ? 2 : quad_lds <= 160 * 1024 ? 1 : 0;
             quad = per_cu > 0 && units <= (long)FZ_QUAD_ROUNDS * per_cu * cus;
-#ifdef BAS_DIAG
-            if (getenv("BAS_FZ_QUAD")) quad = per_cu > 0 && atoi(getenv("BAS_FZ_QUAD")) != 0;
-#endif
+            if (D.fz_quad != BAS_DIAG_UNSET) quad = per_cu > 0 && D.fz_quad != 0;
             if (quad) slots = per_cu * cus;
         }
-#ifdef BAS_DIAG
-        if (units < slots && nw > 1 && !force_nw) continue;
-#else
-        if (units < slots && nw > 1) continue;               // not enough work for this tile: try a smaller one
-#endif
-        if (s16 && !split) return FzPlan{};                  // (subchunks of 16: the split-role kernel or the stored-IR path)
-        p.nw = nw;
-        p.split = split ? 1 : 0;
-        p.quad = quad ? 1 : 0;
-        p.tile = 2048 * nw;
+        if (units < slots && nw > 1 && !force_nw) continue;  // not enough work for this tile: try a smaller one
+        if (s16 && !split) return p;                         // (subchunks of 16: the split-role kernel or the stored-IR path)
+        p.row = split ? bas_fs_row((L + 7) & ~7, S, D) : quad ? bas_fq_row() : bas_find_row(fz_rows, FZ_KEY(nw, false));
+        if (!p.row) return p;                                // (a build without that instance: not served)
         p.nslots = nslots;
         p.spw = spw;
-        p.n_tiles = n_tiles;
-        p.units_total = units;
-        bas_deal_units(units, slots, n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg, &p.slab_bytes);
         p.lds_bytes = split ? bas_fs_lds_bytes(nslots) : quad ? quad_lds : lds;
+        bas_plan_deal(p, 2048 * nw, T_out, n_src, slots, true);
         return p;
     }
     return p;
 }
 
 extern "C" int bas_render_fused_supported(int n_src, long T_in, int K, int S, int L) {
-    return fz_plan(n_src, T_in, K, S, L).nw ? 1 : 0;
+    return fz_plan(n_src, T_in, K, S, L, bas_diag()).row ? 1 : 0;
 }
 
 extern "C" const char *bas_render_fused_kernel_name(int n_src, long T_in, int K, int S, int L) {
-    const FzPlan p = fz_plan(n_src, T_in, K, S, L);
-    if (!p.nw) return "";
-    if (p.split) {
-        const int u = bas_fs_unit_len((L + 7) & ~7);
-        if (S == 16) return u == 128 ? "bas_render_fs_kernel<128,2>" : "bas_render_fs_kernel<104,2>";
-        if (S == 8) return u == 128 ? "bas_render_fs_kernel<128,4>" : "bas_render_fs_kernel<104,4>";
-        return u == 128 ? "bas_render_fs_kernel<128>" : u == 104 ? "bas_render_fs_kernel<104>" : "bas_render_fs_kernel<0>";
-    }
-    if (p.quad) return "bas_render_fq_kernel";
-    return p.honly ? "bas_render_fz_kernel<4,1>" : p.nw == 4 ? "bas_render_fz_kernel<4,0>" : "bas_render_fz_kernel<1,0>";
+    const BasPlan p = fz_plan(n_src, T_in, K, S, L, bas_diag());
+    return p.row ? p.row->public_name : "";
 }
 
 #ifdef BAS_DIAG
 // diagnostic build only (tests, tools/stress_fused.py): which kernel a shape gets - waves per workgroup | h-only rows << 4 |
-// split roles << 5 | four waves per tile of 2048 << 6 | the FIR kernel writes y itself (direct output: no slab reduce) << 7 |
-// the slab reduce is the wide kernel (bas_launch_slab_reduce: more than 24 parts per tile) << 8 (0: not served)
+// split roles << 5 | four waves per tile of 2048 << 6 (the row's code) | the FIR kernel writes y itself (direct output: no slab
+// reduce) << 7 | the slab reduce is the wide kernel << 8 (0: not served)
 extern "C" int bas_debug_fused_plan(int n_src, long T_in, int K, int S, int L) {
-    const FzPlan p = fz_plan(n_src, T_in, K, S, L);
-    if (!p.nw) return 0;
-    const int direct = p.units_per_wg % n_src == 0;
-    const int wide = !direct && (n_src + p.units_per_wg - 1) / p.units_per_wg + 1 > 24;
-    return p.nw | (p.honly << 4) | (p.split << 5) | (p.quad << 6) | (direct << 7) | (wide << 8);
+    const BasPlan p = fz_plan(n_src, T_in, K, S, L, bas_diag());
+    return p.row ? p.row->code | (p.direct << 7) | ((p.reduce == BAS_REDUCE_WIDE) << 8) : 0;
+}
+
+// ... and the whole plan of the fused (fused != 0) or the stored-IR path: out[BAS_PLAN_FIELDS] = tile, n_tiles, units_total,
+// n_wg, units_per_wg, parts_per_wg, nslots, spw, lds_bytes, slab_bytes, direct, reduce (0 none, 1 plain, 2 wide); name = the
+// kernel table row's instance ("": not served).  Returns 1 where a kernel is named.
+extern "C" int bas_debug_dispatch_plan(int fused, int n_src, long T_in, int K, int S, int L, long *out, char *name,
+                                       size_t name_len) {
+    const BasPlan p = fused ? fz_plan(n_src, T_in, K, S, L, bas_diag()) : plan_render(n_src, T_in, K, S, L, true, bas_diag());
+    bas_plan_fields(p, out);
+    snprintf(name, name_len, "%s", p.row ? p.row->instance : "");
+    return p.row ? 1 : 0;
 }
 #endif
 
 extern "C" size_t bas_render_fused_workspace_bytes(int n_src, long T_in, int K, int S, int L) {
-    return BAS_WS_HEAD_BYTES + fz_plan(n_src, T_in, K, S, L).slab_bytes + 16;
+    return BAS_WS_HEAD_BYTES + fz_plan(n_src, T_in, K, S, L, bas_diag()).slab_bytes + 16;
+}
+
+// The launch of an fz, fs or fq row - one signature: full LDS once per device, the profiling events around it
+static hipError_t launch_fz_row(const BasPlan &p, FzArgs &A, const float *x, float *slab, const float *packed, const unsigned *plans,
+                                float *y, unsigned int *peak_bits, hipStream_t st, hipEvent_t eb, hipEvent_t ee) {
+    const hipError_t e = bas_allow_full_lds(p.row->fn);
+    if (e != hipSuccess) return e;
+    void *args[] = {&A, &x, &slab, &packed, &plans, &y, &peak_bits};
+    if (eb) (void)hipEventRecord(eb, st);
+    (void)hipLaunchKernel(p.row->fn, dim3(p.n_wg), dim3(p.row->threads), args, p.lds_bytes, st);
+    if (ee) (void)hipEventRecord(ee, st);
+    return hipSuccess;                                       // (a failed launch: bas_check_launch)
 }
 
 // phases: 1 = the FIR kernel (slab parts, or y itself for scenes whose tiles are each finished by one workgroup),
@@ -717,8 +691,9 @@ static int fused_impl(const char *who, int phases, const float *x, long x_stride
     BAS_REQUIRE(reinterpret_cast<uintptr_t>(plans) % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
                     x_stride % 4 == 0 && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
                 BAS_E_ALIGN, "%s: x, plans and ws must be 16-byte aligned, x_stride a multiple of 4", who);
-    const FzPlan p = fz_plan(n_src, T_in, K, S, L);
-    BAS_REQUIRE(p.nw != 0, BAS_E_SHAPE,
+    const BasDiag D = bas_diag();
+    const BasPlan p = fz_plan(n_src, T_in, K, S, L, D);
+    BAS_REQUIRE(p.row != nullptr, BAS_E_SHAPE,
                 "%s: sizes not served by the fused kernel (bas_render_fused_supported); use bas_interp2d_f32 + "
                 "bas_render_mix_f32", who);
     BAS_REQUIRE(p.units_total < (1L << 31) - 65536, BAS_E_SHAPE,
@@ -745,13 +720,13 @@ static int fused_impl(const char *who, int phases, const float *x, long x_stride
     A.units_total = p.units_total; A.units_per_wg = p.units_per_wg; A.parts_per_wg = p.parts_per_wg;
     A.nslots = p.nslots; A.spw = p.spw;
     A.packed_bytes = (unsigned)table_bytes;
-    A.direct = p.units_per_wg % n_src == 0;
+    A.direct = p.direct;
     A.accumulate = accumulate;
     A.T_out = T_out;
     A.ctl = ctl;
     A.tail_mode = 0;
 #ifdef BAS_DIAG
-    { const char *d = getenv("BAS_DEBUG_FLAGS"); A.inject = d ? (atoi(d) & 256) : 0; }
+    A.inject = D.debug_flags & 256;
 #endif
     bool rule_done = false;                                  // the peak rule has been applied inside a kernel tail
     if (A.direct && want_peak) {
@@ -769,32 +744,16 @@ static int fused_impl(const char *who, int phases, const float *x, long x_stride
     if (!want_peak) peak_bits = nullptr; else peak_bits = reinterpret_cast<unsigned int *>(peak_dev);
     hipEvent_t eb = reinterpret_cast<hipEvent_t>(ev_begin), ee = reinterpret_cast<hipEvent_t>(ev_end);
     if (phases & 1) {
-        if (p.split) {
-            hipError_t e = bas_fs_launch(A, x, slab, packed, reinterpret_cast<const unsigned *>(plans), y, peak_bits, p.n_wg,
-                                         p.lds_bytes, st, eb, ee);
-            if (e != hipSuccess) return bas_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        } else if (p.quad) {
-            hipError_t e = bas_fq_launch(A, x, slab, packed, reinterpret_cast<const unsigned *>(plans), y, peak_bits, p.n_wg,
-                                         p.lds_bytes, st, eb, ee);
-            if (e != hipSuccess) return bas_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        } else {
-            typedef void (*fz_fn)(FzArgs, const float *, float *, const float *, const unsigned *, float *, unsigned int *);
-            const fz_fn fn = p.honly ? bas_render_fz_kernel<4, true> : p.nw == 4 ? bas_render_fz_kernel<4, false> : bas_render_fz_kernel<1, false>;
-            hipError_t e = bas_allow_full_lds(reinterpret_cast<const void *>(fn));
-            if (e != hipSuccess) return bas_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-            if (eb) (void)hipEventRecord(eb, st);
-            hipLaunchKernelGGL(fn, dim3(p.n_wg), dim3(64 * p.nw), p.lds_bytes, st, A, x, slab, packed,
-                               reinterpret_cast<const unsigned *>(plans), y, peak_bits);
-            if (ee) (void)hipEventRecord(ee, st);
-        }
+        hipError_t e = launch_fz_row(p, A, x, slab, packed, reinterpret_cast<const unsigned *>(plans), y, peak_bits, st, eb, ee);
+        if (e != hipSuccess) return bas_fail((int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
         int rc = bas_check_launch(who);
         if (rc) return rc;
     }
     if (!(phases & 2)) return 0;
     if (!A.direct) {                                         // direct output: y and the peak are complete
         int skipped = 1;
-        int rc = bas_launch_slab_reduce(slab, p.tile, n_src, p.units_per_wg, p.parts_per_wg, p.n_wg, T_out, y, accumulate,
-                                        peak_bits, want_peak ? &T : nullptr, &skipped, carry, st, who);
+        int rc = bas_launch_slab_reduce(slab, p, n_src, T_out, y, accumulate, peak_bits, want_peak ? &T : nullptr, &skipped,
+                                        carry, st, who);
         if (rc) return rc;
         rule_done = !skipped && T.normalize != 0;
     } else if (carry) {

@@ -245,16 +245,12 @@ size_t bas_fq_lds_bytes(int nslots) {
            (size_t)3 * 32 * 64 * sizeof(f32x2);
 }
 
-hipError_t bas_fq_launch(const FzArgs &A, const float *x, float *slab, const float *packed, const unsigned *plans, float *y,
-                         unsigned int *peak_bits, int n_wg, size_t lds_bytes, hipStream_t st, hipEvent_t eb, hipEvent_t ee) {
+const BasKernelRow *bas_fq_row() {
 #if FZ_ASM
-    hipError_t e = bas_allow_full_lds(reinterpret_cast<const void *>(bas_render_fq_kernel));
-    if (e != hipSuccess) return e;
-    if (eb) (void)hipEventRecord(eb, st);
-    hipLaunchKernelGGL(bas_render_fq_kernel, dim3(n_wg), dim3(256), lds_bytes, st, A, x, slab, packed, plans, y, peak_bits);
-    if (ee) (void)hipEventRecord(ee, st);
-    return hipSuccess;
+    static const BasKernelRow row = {"bas_render_fq_kernel", "bas_render_fq_kernel", reinterpret_cast<const void *>(bas_render_fq_kernel),
+                                     256, 0, 1 | (1 << 6)};
+    return &row;
 #else
-    return hipErrorNotSupported;                             // (make cppstep: the kernel exists only around the assembly blocks)
+    return nullptr;                                          // (make cppstep: the kernel exists only around the assembly blocks)
 #endif
 }

@@ -17,7 +17,6 @@
 // The walk, the window geometry, the row-step setup and the flush are bas_window.h, shared with the other FIR kernels; what
 // the stagers keep to themselves says so where it stands.  No MFMA: this is a 1-D FIR (BASELINE.json north_star).
 #include "bas_fused.h"
-#include <stdlib.h>
 
 #ifndef FS_PSPLIT
 #define FS_PSPLIT 1             // unit blocks of subchunks >= 32: the half-rate product P split once more (0: round 4's first form)
@@ -478,36 +477,32 @@ size_t bas_fs_lds_bytes(int nslots) {
            sizeof(float);
 }
 
-hipError_t bas_fs_launch(const FzArgs &A, const float *x, float *slab, const float *packed, const unsigned *plans, float *y,
-                         unsigned int *peak_bits, int n_wg, size_t lds_bytes, hipStream_t st, hipEvent_t eb, hipEvent_t ee) {
+// The rows of the kernel table: keys 100 UNITLEN + 10 NSUB + PSPLIT.  The compile-time switches decide which exist: the unit
+// blocks of subchunks >= 32 with P split (FS_PSPLIT) and every tap read once (FS_TAPS_ONCE; the diagnostic build also holds
+// the twice-read blocks: BAS_FS_TAPS_ONCE=0, A/B and tests), or round 4's first form.
+const BasKernelRow *bas_fs_row(int Lp, int S, const BasDiag &D) {
 #if FZ_ASM
-    typedef void (*fs_fn)(FzArgs, const float *, float *, const float *, const unsigned *, float *, unsigned int *);
-    const int ul = bas_fs_unit_len(A.Lp);
+#define FS_KEY(ul, nsub, ps) (100 * (ul) + 10 * (nsub) + (ps))
+#define FS_ROW(pub, ul, nsub, ps)                                                                                          \
+    {"bas_render_fs_kernel<" #ul ", " #nsub ", " #ps ">", "bas_render_fs_kernel<" pub ">",                                  \
+     reinterpret_cast<const void *>(bas_render_fs_kernel<ul, nsub, ps>), 512, FS_KEY(ul, nsub, ps), 4 | (1 << 5)}
+    static const BasKernelRow rows[] = {                     // (in this order the kernels stand in the code object)
 #if FS_PSPLIT && FS_TAPS_ONCE
-    fs_fn fn = ul == 128 ? bas_render_fs_kernel<128, 1, 2> : ul == 104 ? bas_render_fs_kernel<104, 1, 2> : bas_render_fs_kernel<0>;
-#ifdef BAS_DIAG
-    {                                                        // diagnostic build only: the block that reads every tap twice (A/B, tests)
-        const char *once = getenv("BAS_FS_TAPS_ONCE");
-        if (once && atoi(once) == 0 && ul != 0) fn = ul == 128 ? bas_render_fs_kernel<128, 1, 1> : bas_render_fs_kernel<104, 1, 1>;
-    }
-#endif
-#elif FS_PSPLIT
-    fs_fn fn = ul == 128 ? bas_render_fs_kernel<128, 1, 1> : ul == 104 ? bas_render_fs_kernel<104, 1, 1> : bas_render_fs_kernel<0>;
+        FS_ROW("104", 104, 1, 2), FS_ROW("0", 0, 1, 0), FS_ROW("128", 128, 1, 2),
 #else
-    fs_fn fn = ul == 128 ? bas_render_fs_kernel<128> : ul == 104 ? bas_render_fs_kernel<104> : bas_render_fs_kernel<0>;
+        FS_ROW("0", 0, 1, 0),
 #endif
-    if (A.S == 16 || A.S == 8) {                             // (the plan gives these to this kernel only with a unit block)
-        if (ul == 0) return hipErrorNotSupported;
-        fn = A.S == 16 ? (ul == 128 ? bas_render_fs_kernel<128, 2> : bas_render_fs_kernel<104, 2>)
-                       : (ul == 128 ? bas_render_fs_kernel<128, 4> : bas_render_fs_kernel<104, 4>);
-    }
-    hipError_t e = bas_allow_full_lds(reinterpret_cast<const void *>(fn));
-    if (e != hipSuccess) return e;
-    if (eb) (void)hipEventRecord(eb, st);
-    hipLaunchKernelGGL(fn, dim3(n_wg), dim3(512), lds_bytes, st, A, x, slab, packed, plans, y, peak_bits);
-    if (ee) (void)hipEventRecord(ee, st);
-    return hipSuccess;
+#if FS_PSPLIT && (!FS_TAPS_ONCE || defined(BAS_DIAG))
+        FS_ROW("128", 128, 1, 1), FS_ROW("104", 104, 1, 1),
+#endif
+#if !FS_PSPLIT
+        FS_ROW("128", 128, 1, 0), FS_ROW("104", 104, 1, 0),
+#endif
+        FS_ROW("128,2", 128, 2, 0), FS_ROW("104,2", 104, 2, 0), FS_ROW("128,4", 128, 4, 0), FS_ROW("104,4", 104, 4, 0)};
+    const int ul = bas_fs_unit_len(Lp), nsub = S == 16 ? 2 : S == 8 ? 4 : 1;
+    const int once = FS_TAPS_ONCE && D.fs_taps_once != 0;
+    return bas_find_row(rows, FS_KEY(ul, nsub, nsub == 1 && ul != 0 && FS_PSPLIT ? 1 + once : 0));
 #else
-    return hipErrorNotSupported;                             // (make cppstep: the kernel exists only around the assembly blocks)
+    return nullptr;                                          // (make cppstep: the kernel exists only around the assembly blocks)
 #endif
 }

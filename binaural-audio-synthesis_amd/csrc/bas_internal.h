@@ -38,9 +38,6 @@ struct BasCarry {
     double *gain;               // [n_src] rows of nh + nb gains at the angles' stride (null: no gain row)
     double *gain_last;          // [n_src]: the gain at the block's end (with gain)
 };
-int bas_launch_slab_reduce(const float *slab, int tile, int n_src, int units_per_wg, int parts_per_wg, int n_wg,
-                           long T_out, float *y, int accumulate, unsigned int *peak_bits, const BasTail *tail,
-                           int *tail_skipped, const BasCarry *carry, hipStream_t st, const char *what);
 // Workspaces start with a head the library owns: the 2048-byte control block (zero between calls) and BAS_TAIL_MAX_WG
 // per-workgroup maxima (bas_tail.h); the slabs follow.
 #define BAS_TAIL_MAX_WG 4096

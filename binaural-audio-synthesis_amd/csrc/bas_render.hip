@@ -27,6 +27,7 @@
 #include "bas_plan.h"
 #include "bas_window.h"
 #include "bas_tail.h"
+#include "bas_dispatch.h"
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
@@ -1045,128 +1046,114 @@ hipError_t bas_allow_full_lds(const void *fn) {
     return hipSuccess;
 }
 
+// What the diagnostic build takes from the environment: the ONLY getenv of the FIR dispatch, and none in the shipped build.
+BasDiag bas_diag() {
+    BasDiag D;
+#ifdef BAS_DIAG
+    auto num = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
+    if (const char *f = getenv("BAS_FORCE_KERNEL"))
+        D.force_kernel = !strcmp(f, "hd") ? BAS_FORCE_HD : !strcmp(f, "rows32") ? BAS_FORCE_ROWS32 : !strcmp(f, "generic") ? BAS_FORCE_GENERIC : BAS_FORCE_OTHER;
+    D.fz_nw = num("BAS_FZ_NW", BAS_DIAG_UNSET);
+    D.fz_split = num("BAS_FZ_SPLIT", BAS_DIAG_UNSET);
+    D.fz_quad = num("BAS_FZ_QUAD", BAS_DIAG_UNSET);
+    D.fz_wg_per_cu = num("BAS_FZ_WG_PER_CU", BAS_DIAG_UNSET);
+    D.fs_taps_once = num("BAS_FS_TAPS_ONCE", BAS_DIAG_UNSET);
+    D.debug_flags = num("BAS_DEBUG_FLAGS", 0);
+#endif
+    return D;
+}
+
 // slabs of partial tiles -> y (fixed order), fused max|y|: shared by the FIR launchers (bas_fused.hip too).
 // tail != null (fused entry points): tail->ctl / wgpeak / y / n / peak / normalize are filled in, the launch geometry here;
 // the kernel then ends in bas_tail.  Launches with more workgroups than the control area has maxima slots keep the round-3
 // form (returns 1 in *tail_skipped: the caller launches the scale kernel itself).
-int bas_launch_slab_reduce(const float *slab, int tile, int n_src, int units_per_wg, int parts_per_wg, int n_wg,
-                           long T_out, float *y, int accumulate, unsigned int *peak_bits, const BasTail *tail,
-                           int *tail_skipped, const BasCarry *carry, hipStream_t st, const char *what) {
+int bas_launch_slab_reduce(const float *slab, const BasPlan &p, int n_src, long T_out, float *y, int accumulate,
+                           unsigned int *peak_bits, const BasTail *tail, int *tail_skipped, const BasCarry *carry,
+                           hipStream_t st, const char *what) {
     BasCarry C = {};
     if (carry) {                                             // a stream block: its own maximum, no tail (see the kernels)
         C = *carry;
         tail = nullptr;
         peak_bits = nullptr;
     }
-    const int parts = (n_src + units_per_wg - 1) / units_per_wg + 1;       // workgroups that can share one tile
     BasTail T = {};
     if (tail_skipped) *tail_skipped = 1;
-    if (parts > 24) {                                        // many sources on a short signal: sum the parts in parallel
-        const long blocks_per_ear = (((T_out + 3) / 4) + 3) / 4;
-        if (tail && 2 * blocks_per_ear <= BAS_TAIL_MAX_WG) {
-            T = *tail;
-            T.n_wg = (unsigned)(2 * blocks_per_ear);
-            if (tail_skipped) *tail_skipped = 0;
-        }
-        hipLaunchKernelGGL(bas_slab_reduce_wide_kernel, dim3((unsigned)(2 * blocks_per_ear)), dim3(256), 0, st, slab, tile,
-                           n_src, units_per_wg, parts_per_wg, n_wg, T_out, y, accumulate, peak_bits, T, C);
-        return bas_check_launch(what);
-    }
-    const int grid = bas_grid_for((T_out + 3) / 4, 2048);
+    const bool wide = p.reduce == BAS_REDUCE_WIDE;           // many sources on a short signal: sum the parts in parallel
+    const long blocks_per_ear = (((T_out + 3) / 4) + 3) / 4;
+    const int grid = wide ? (int)(2 * blocks_per_ear) : bas_grid_for((T_out + 3) / 4, 2048);
     if (tail && grid <= BAS_TAIL_MAX_WG) {
         T = *tail;
         T.n_wg = (unsigned)grid;
         if (tail_skipped) *tail_skipped = 0;
     }
-    hipLaunchKernelGGL(bas_slab_reduce_kernel, dim3(grid), dim3(256), 0, st, slab, tile,
-                       n_src, units_per_wg, parts_per_wg, n_wg, T_out, y, accumulate, peak_bits, T, C);
+    hipLaunchKernelGGL(wide ? bas_slab_reduce_wide_kernel : bas_slab_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, st, slab,
+                       p.tile, n_src, p.units_per_wg, p.parts_per_wg, p.n_wg, T_out, y, accumulate, peak_bits, T, C);
     return bas_check_launch(what);
 }
 
-enum { KIND_GENERIC = 0, KIND_ROWS32 = 1, KIND_HD = 2 };
+// ---- the kernel table (bas_dispatch.h) of the stored-IR path
+#define HD_KEY(nsub, honly, dual) (100 * (nsub) + 10 * (honly) + (dual))
+#define HD_ROW(nsub, honly, dual)                                                                                           \
+    {"bas_render_hd_kernel<" #nsub ", " #honly ", " #dual ">", "bas_render_hd_kernel",                                      \
+     reinterpret_cast<const void *>(bas_render_hd_kernel<nsub, honly, dual>), HD_THREADS, HD_KEY(nsub, honly, dual), 0}
+static const BasKernelRow hd_rows[] = {                     // (in this order the kernels stand in the code object)
+    HD_ROW(1, true, false), HD_ROW(1, false, false), HD_ROW(2, true, false), HD_ROW(2, false, false), HD_ROW(4, true, false),
+    HD_ROW(4, false, false), HD_ROW(8, true, false), HD_ROW(8, false, false), HD_ROW(1, true, true), HD_ROW(1, false, true)};
+static const BasKernelRow rows32_row = {"bas_render_rows32_kernel", "bas_render_rows32_kernel",
+                                        reinterpret_cast<const void *>(bas_render_rows32_kernel), RT_THREADS, 0, 0};
+static const BasKernelRow generic_row = {"bas_render_generic_kernel", "bas_render_generic_kernel",
+                                         reinterpret_cast<const void *>(bas_render_generic_kernel), 256, 0, 0};
 
-struct RenderPlan {
-    int kind;
-    int tile;                  // outputs per tile
-    long n_tiles, units_total;
-    int n_wg, units_per_wg, parts_per_wg;
-    int hd_slots;              // chunk slots of the hd kernel
-    int honly;                 // 1: h-only LDS image (small chunks), see hd_load_octet
-    int dual;                  // 1: dual row step (subchunk size not a power of two / multiple of 32)
-    size_t lds_bytes, slab_bytes;
-};
+// LDS of the hd kernel: the x image and slots + 1 rows of taps, (h0, d) per tap or - h-only image - h alone
+static size_t hd_lds_bytes(int slots, bool honly) {
+    return (size_t)(HD_X_FLOATS + (slots + 1) * (honly ? HO_SLOT : HD_SLOT)) * sizeof(float);
+}
 
 // Which kernel renders (n_src, T_in, K, S, L), and how the (tile, source) work units are dealt to
 // workgroups: equal contiguous shares, so every workgroup finishes at the same time.
-static RenderPlan plan_render(int n_src, long T_in, int K, int S, int L, bool aligned) {
-    RenderPlan p = {};
-    p.kind = KIND_GENERIC;
+BasPlan plan_render(int n_src, long T_in, int K, int S, int L, bool aligned, const BasDiag &D) {
+    BasPlan p = {};
+    p.row = &generic_row;
+    p.direct = 1;                                            // (the generic kernel writes y itself: no slabs)
     const bool s_pow2 = S > 0 && (S & (S - 1)) == 0;
     const bool hd_small_s = s_pow2 && S >= 4 && S < 32 && K % 32 == 0;        // rows of 32 hold 2 / 4 / 8 subchunks
                                                                               // (16 / 32 per row build for minutes: not offered)
-#ifdef BAS_DIAG
-    const char *force = getenv("BAS_FORCE_KERNEL");          // diagnostic build only: tests force the fallback kernels
-#else
-    const char *force = nullptr;
-#endif
+    const int force = D.force_kernel;                        // diagnostic build only: tests force the fallback kernels
     if (!(aligned && n_src > 0 && T_in > 0 && K > 0 && S > 0 && L > 0 && bas_sizes_in_range(n_src, T_in, K, S, L))) return p;
-    if (!(S % 32 == 0 || hd_small_s)) {
+    const bool dual = !(S % 32 == 0 || hd_small_s);
+    int slots, hd, honly;
+    if (dual) {
         // Any other subchunk size >= 2 (any chunk size >= 32; the caller keeps rows 16-byte aligned through x_stride):
         // the hd kernel's multi-part row step.  One slot more than the rows reach: the part of a row behind a chunk
         // boundary reads the next chunk's slot.
-        const int dual_slots = (K - 1 + 32 * (HD_ROWS - 1) + 31) / K + 2;
-        const bool full = dual_slots <= HD_MAXSLOTS;
-        const size_t lds = full ? (size_t)(HD_X_FLOATS + (dual_slots + 1) * HD_SLOT) * sizeof(float)
-                                : (size_t)(HD_X_FLOATS + (dual_slots + 1) * HO_SLOT) * sizeof(float);
-        if (S < 2 || K < 32 || lds > 160 * 1024 || (force && strcmp(force, "hd"))) return p;
-        p.kind = KIND_HD;
-        p.dual = 1;
-        p.honly = !full;
-        p.hd_slots = dual_slots;
-        p.tile = HD_TILE;
-        p.lds_bytes = lds;
-        long wg_per_cu = (long)(160 * 1024 / lds);
-        wg_per_cu = wg_per_cu > 2 ? 2 : (wg_per_cu < 1 ? 1 : wg_per_cu);
-        const long T_out = T_in + L - 1;
-        p.n_tiles = (T_out + p.tile - 1) / p.tile;
-        p.units_total = p.n_tiles * n_src;
-        bas_deal_units(p.units_total, wg_per_cu * bas_device_cus(), n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg,
-                       &p.slab_bytes);
-        return p;
-    }
-    const int hd_slots = (K - 32 + 32 * (HD_ROWS - 1)) / K + 1;
-    // hd kernel: up to HD_MAXSLOTS chunk slots per tile (K >= 448) the LDS image holds (h0, d) per tap; smaller
-    // chunks put more slots under a tile and use the h-only image (half the bytes per slot, d taken in the row
-    // step: two workgroups per CU down to K ~ 192, one below).  On the 256-source scene: 0.89 ms at K = 256,
-    // S = 32 (rows32: 1.24 ms), 0.93 ms at K = 256, S = 16 and 1.2 ms at K = 128, S = 16 (generic: 32 ms).
-    const bool hd_fits = (s_pow2 || S % 32 == 0) && (hd_slots <= HD_MAXSLOTS ||
-                                    (size_t)(HD_X_FLOATS + (hd_slots + 1) * HO_SLOT) * sizeof(float) <= 160 * 1024);
-    int kind = hd_fits ? KIND_HD : KIND_ROWS32;
-    if (force && !strcmp(force, "rows32")) kind = KIND_ROWS32;
-    if (kind == KIND_ROWS32 && S % 32 != 0) return p;        // small subchunks: hd kernel or nothing
-    if (force && !strcmp(force, "generic")) return p;
-    if (kind == KIND_ROWS32 && L % 2 != 0) return p;         // rows32 loads tap pairs
-    long wg_per_cu;
-    if (kind == KIND_HD) {
-        p.tile = HD_TILE;
-        p.hd_slots = hd_slots;
-        p.honly = hd_slots > HD_MAXSLOTS;                   // measured faster than the full image at one workgroup per CU
-        p.lds_bytes = p.honly ? (size_t)(HD_X_FLOATS + (hd_slots + 1) * HO_SLOT) * sizeof(float)
-                              : (size_t)(HD_X_FLOATS + (hd_slots + 1) * HD_SLOT) * sizeof(float);
-        wg_per_cu = (long)(160 * 1024 / p.lds_bytes);
-        if (wg_per_cu > 2) wg_per_cu = 2;
-        if (wg_per_cu < 1) wg_per_cu = 1;
+        slots = (K - 1 + 32 * (HD_ROWS - 1) + 31) / K + 2;
+        honly = slots > HD_MAXSLOTS;
+        if (S < 2 || K < 32 || hd_lds_bytes(slots, honly) > 160 * 1024 || (force && force != BAS_FORCE_HD)) return p;
+        hd = true;
     } else {
-        p.tile = RT_TILE;
-        p.lds_bytes = RT_LDS_BYTES;
-        wg_per_cu = 2;
+        slots = (K - 32 + 32 * (HD_ROWS - 1)) / K + 1;
+        // hd kernel: up to HD_MAXSLOTS chunk slots per tile (K >= 448) the LDS image holds (h0, d) per tap; smaller
+        // chunks put more slots under a tile and use the h-only image (half the bytes per slot, d taken in the row
+        // step: two workgroups per CU down to K ~ 192, one below).  On the 256-source scene: 0.89 ms at K = 256,
+        // S = 32 (rows32: 1.24 ms), 0.93 ms at K = 256, S = 16 and 1.2 ms at K = 128, S = 16 (generic: 32 ms).
+        honly = slots > HD_MAXSLOTS;                         // measured faster than the full image at one workgroup per CU
+        hd = (s_pow2 || S % 32 == 0) && (!honly || hd_lds_bytes(slots, true) <= 160 * 1024) && force != BAS_FORCE_ROWS32;
+        if (!hd && S % 32 != 0) return p;                    // small subchunks: hd kernel or nothing
+        if (force == BAS_FORCE_GENERIC) return p;
+        if (!hd && L % 2 != 0) return p;                     // rows32 loads tap pairs
     }
-    p.kind = kind;
-    const long T_out = T_in + L - 1;
-    p.n_tiles = (T_out + p.tile - 1) / p.tile;
-    p.units_total = p.n_tiles * n_src;
-    bas_deal_units(p.units_total, wg_per_cu * bas_device_cus(), n_src, p.tile, &p.units_per_wg, &p.n_wg, &p.parts_per_wg,
-                   &p.slab_bytes);
+    long wg_per_cu = 2;
+    if (hd) {
+        p.row = bas_find_row(hd_rows, HD_KEY(dual || S >= 32 ? 1 : 32 / S, honly, dual));
+        p.nslots = slots;
+        p.lds_bytes = hd_lds_bytes(slots, honly);
+        wg_per_cu = (long)(160 * 1024 / p.lds_bytes);
+        wg_per_cu = wg_per_cu > 2 ? 2 : (wg_per_cu < 1 ? 1 : wg_per_cu);
+    } else {
+        p.row = &rows32_row;
+        p.lds_bytes = RT_LDS_BYTES;
+    }
+    bas_plan_deal(p, hd ? HD_TILE : RT_TILE, T_in + L - 1, n_src, wg_per_cu * bas_device_cus(), false);
     return p;
 }
 
@@ -1174,26 +1161,32 @@ extern "C" size_t bas_render_workspace_bytes(int n_src, long T_in, int K, int S,
     if (n_src <= 0 || T_in <= 0 || K <= 0 || S <= 0 || L <= 0) return BAS_WS_HEAD_BYTES + 16;
     // the kernel is chosen at launch time (pointer alignment, diagnostics override): both fast kernels
     // use the same slab formula, so size for the larger tile count of the two
-    RenderPlan p = plan_render(n_src, T_in, K, S, L, true);
+    const BasPlan p = plan_render(n_src, T_in, K, S, L, true, bas_diag());
     size_t need = p.slab_bytes;
-    if (p.kind == KIND_HD && L % 2 == 0) {
-        RenderPlan q = p;
-        const long T_out = T_in + L - 1;
-        q.tile = RT_TILE;
-        q.n_tiles = (T_out + RT_TILE - 1) / RT_TILE;
-        q.units_total = q.n_tiles * n_src;
-        size_t alt = 0;
-        bas_deal_units(q.units_total, 2L * bas_device_cus(), n_src, RT_TILE, &q.units_per_wg, &q.n_wg, &q.parts_per_wg, &alt);
-        if (alt > need) need = alt;
+    if (p.tile == HD_TILE && L % 2 == 0) {
+        BasPlan q = {};
+        bas_plan_deal(q, RT_TILE, T_in + L - 1, n_src, 2L * bas_device_cus(), false);
+        if (q.slab_bytes > need) need = q.slab_bytes;
     }
     return BAS_WS_HEAD_BYTES + need + 16;                    // (the head is the library's control area: never slab space)
 }
 
 extern "C" const char *bas_render_kernel_name(int n_src, long T_in, int K, int S, int L) {
-    if (n_src <= 0 || T_in <= 0 || K <= 0 || S <= 0 || L <= 0) return "bas_render_generic_kernel";
-    RenderPlan p = plan_render(n_src, T_in, K, S, L, true);
-    return p.kind == KIND_HD ? "bas_render_hd_kernel"
-                             : (p.kind == KIND_ROWS32 ? "bas_render_rows32_kernel" : "bas_render_generic_kernel");
+    if (n_src <= 0 || T_in <= 0 || K <= 0 || S <= 0 || L <= 0) return generic_row.public_name;
+    return plan_render(n_src, T_in, K, S, L, true, bas_diag()).row->public_name;
+}
+
+// The launch of an hd or the rows32 row: full LDS once per device, the profiling events around it.  hd kernels take
+// (RenderArgs, chunk slots), rows32 (RenderArgs) alone.
+static hipError_t launch_stored_row(const BasPlan &p, RenderArgs &A, hipStream_t st, hipEvent_t ev_begin, hipEvent_t ev_end) {
+    const hipError_t e = bas_allow_full_lds(p.row->fn);
+    if (e != hipSuccess) return e;
+    int nslots = p.nslots;
+    void *hd_args[] = {&A, &nslots}, *rows32_args[] = {&A};
+    if (ev_begin) (void)hipEventRecord(ev_begin, st);
+    (void)hipLaunchKernel(p.row->fn, dim3(p.n_wg), dim3(p.row->threads), p.row == &rows32_row ? rows32_args : hd_args, p.lds_bytes, st);
+    if (ev_end) (void)hipEventRecord(ev_end, st);
+    return hipSuccess;                                       // (a failed launch: bas_check_launch)
 }
 
 static int render_mix_impl(const float *x, long x_stride, const float *H, int n_src, long T_in, int K, int S,
@@ -1222,8 +1215,9 @@ static int render_mix_impl(const float *x, long x_stride, const float *H, int n_
     const bool aligned = (reinterpret_cast<uintptr_t>(x) % 16 == 0) && (x_stride % 4 == 0) &&
                          (reinterpret_cast<uintptr_t>(ws) % 16 == 0) && (reinterpret_cast<uintptr_t>(H) % 8 == 0);
     const int live_src = T_in == 0 ? 0 : n_src;
-    RenderPlan p = plan_render(live_src, T_in, K, S, L, aligned);
-    if (p.kind == KIND_GENERIC) {
+    const BasDiag D = bas_diag();
+    const BasPlan p = plan_render(live_src, T_in, K, S, L, aligned, D);
+    if (p.row == &generic_row) {
         if (ev_begin) (void)hipEventRecord(ev_begin, st);
         hipLaunchKernelGGL(bas_render_generic_kernel, dim3(bas_grid_for(T_out, 8192)), dim3(256), 0, st, x, x_stride,
                            H, live_src, T_in, K, S, L, n_chunks, T_out, y, accumulate, peak_bits);
@@ -1240,37 +1234,14 @@ static int render_mix_impl(const float *x, long x_stride, const float *H, int n_
     A.units_total = p.units_total; A.units_per_wg = p.units_per_wg; A.parts_per_wg = p.parts_per_wg;
     A.slab = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + BAS_WS_HEAD_BYTES);   // (behind the control area)
 #ifdef BAS_DIAG
-    { const char *d = getenv("BAS_DEBUG_FLAGS"); A.dbg = d ? atoi(d) : 0; }
+    A.dbg = D.debug_flags;
 #endif
-    const int nsub = S >= 32 ? 1 : 32 / S;
-    typedef void (*hd_fn)(RenderArgs, int);
-    auto pick = [&](bool honly) -> hd_fn {
-        switch (nsub) {
-        case 1: return honly ? bas_render_hd_kernel<1, true> : bas_render_hd_kernel<1>;
-        case 2: return honly ? bas_render_hd_kernel<2, true> : bas_render_hd_kernel<2>;
-        case 4: return honly ? bas_render_hd_kernel<4, true> : bas_render_hd_kernel<4>;
-        default: return honly ? bas_render_hd_kernel<8, true> : bas_render_hd_kernel<8>;
-        }
-    };
-    hd_fn hdk = pick(false);
-    if (p.kind == KIND_HD && p.dual)
-        hdk = p.honly ? bas_render_hd_kernel<1, true, true> : bas_render_hd_kernel<1, false, true>;
-    else if (p.kind == KIND_HD && p.honly)
-        hdk = pick(true);
-    const void *fn = p.kind == KIND_HD ? reinterpret_cast<const void *>(hdk)
-                                        : reinterpret_cast<const void *>(bas_render_rows32_kernel);
-    hipError_t e = bas_allow_full_lds(fn);
+    hipError_t e = launch_stored_row(p, A, st, ev_begin, ev_end);
     if (e != hipSuccess) return bas_fail((int)e, "bas_render_mix_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (ev_begin) (void)hipEventRecord(ev_begin, st);
-    if (p.kind == KIND_HD)
-        hipLaunchKernelGGL(hdk, dim3(p.n_wg), dim3(HD_THREADS), p.lds_bytes, st, A, p.hd_slots);
-    else
-        hipLaunchKernelGGL(bas_render_rows32_kernel, dim3(p.n_wg), dim3(RT_THREADS), p.lds_bytes, st, A);
-    if (ev_end) (void)hipEventRecord(ev_end, st);
-    int rc = bas_check_launch(p.kind == KIND_HD ? "bas_render_mix_f32(hd)" : "bas_render_mix_f32(rows32)");
+    int rc = bas_check_launch(p.row == &rows32_row ? "bas_render_mix_f32(rows32)" : "bas_render_mix_f32(hd)");
     if (rc) return rc;
-    return bas_launch_slab_reduce(A.slab, p.tile, live_src, p.units_per_wg, p.parts_per_wg, p.n_wg, T_out, y, accumulate,
-                                  peak_bits, nullptr, nullptr, nullptr, st, "bas_render_mix_f32(reduce)");
+    return bas_launch_slab_reduce(A.slab, p, live_src, T_out, y, accumulate, peak_bits, nullptr, nullptr, nullptr, st,
+                                  "bas_render_mix_f32(reduce)");
 }
 
 extern "C" int bas_render_mix_f32(const float *x, long x_stride, const float *H, int n_src, long T_in,

@@ -34,7 +34,8 @@ tiles of 2048 samples anyway - a 512-sample block with a 512-sample halo is ONE 
 source, exactly as it would be with a 128-sample halo.
 """
 from . import _hip, sphere, propagation
-from .apply_hrtf import as_device_table, plan_angles_device, render_angles_device, check_gain, is_device_arg
+from .apply_hrtf import (as_device_table, plan_angles_device, render_angles_device, check_gain, is_device_arg, fused_serves,
+                         render_workspace_bytes)
 
 
 def rotate_into_views(elev, azim, head, views):
@@ -241,8 +242,7 @@ class _BlockStream:
         import torch
         lib, dev, K, S, L = _hip.lib(), self.tbl.device, self.K, self.S, self.tbl.L
         with _hip.on_device(dev):
-            wb = max(lib.bas_render_workspace_bytes(n_src, T_in, K, S, L),
-                     lib.bas_render_fused_workspace_bytes(n_src, T_in, K, S, L))
+            wb = render_workspace_bytes(n_src, T_in, K, S, L)
         self._ws = _hip.new_workspace(wb, dev)
         self._ws_plans = torch.empty((lib.bas_interp2d_workspace_bytes(n_q),), dtype=torch.uint8, device=dev)
 
@@ -430,8 +430,7 @@ class StreamRenderer(_BlockStream):
             src.carry(B)
         xbuf, x = self._x_rows.buf, self._x_rows.window(B)
         with _hip.on_device(dev):
-            one_call = self.one_call and bool(_hip.lib().bas_render_fused_supported(n, halo + B, self.K, self.S, tbl.L)) \
-                and tbl.upsampling >= 4 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+            one_call = self.one_call and fused_serves(x, tbl, self.K, self.S)
         # live gains ride beside the angles and the end angles in every argument list
         g = self._gain_all
         gain, gain_last = ((), ()) if g is None else ((_hip.ptr(g),), (_hip.ptr(self._gain_last),))
