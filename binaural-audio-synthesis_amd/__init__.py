@@ -4,7 +4,8 @@ Public surface mirrors the reference's apply_hrtf.py / sphere.py for the path
 load_irs_and_delaydiffs -> interpolate_2d -> make_signal_move_2d; all arithmetic
 runs in the C-ABI HIP library built from csrc/ (see include/bas.h).
 """
-from . import synth, sphere, _hip, apply_hrtf, distributed, stream, batch, stream_batch, scene, reverb, limiter, ambisonics, loudness, rate, output  # noqa: F401
+from . import synth, sphere, _hip, apply_hrtf, distributed, stream, batch, stream_batch, scene, reverb, limiter, ambisonics, loudness, rate, output, bank  # noqa: F401
+from .bank import TableBank  # noqa: F401
 from .batch import render_batch, make_signal_move_2d_batch  # noqa: F401
 from .stream import StreamRenderer  # noqa: F401
 from .stream_batch import StreamBatchRenderer  # noqa: F401

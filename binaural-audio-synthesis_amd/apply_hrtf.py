@@ -20,6 +20,7 @@ import numpy as np
 from . import _hip
 from ._stage import host_array, is_device
 from . import sphere
+from .bank import TableBank, table_columns_to_device
 
 
 # --------------------------------------------------------------------------
@@ -83,6 +84,9 @@ def as_device_table(tbl, device=None):
     re-bound field gets its own copy."""
     if isinstance(tbl, irs_and_delaydiffs):
         return tbl
+    if isinstance(tbl, TableBank):                          # (every interface but the two below takes ONE table)
+        raise ValueError("a TableBank is not a table: banks are taken by StreamBatchRenderer(bank, ..., tables=) and "
+                         "render_batch(..., tbl=bank, tables=) (DESIGN.md §3.26); pass one of its tables here")
     device = _hip.require_gpu(device)
     key = _table_key(tbl)
     cache = getattr(tbl, "_bas_device_tables", None)            # {device: (key, device table)}
@@ -100,6 +104,18 @@ def as_device_table(tbl, device=None):
     # the arrays are kept alive with the entry so that their id()s cannot be reused by later allocations
     cache[str(device)] = (key, made, (tbl.diffs_left, tbl.diffs_right, tbl.irs_left, tbl.irs_right))
     return made
+
+
+def table_or_bank(tbl, table_of):
+    """The table argument of the four device-side calls that take table_of=: a TableBank as it is (it
+    needs its table_of: ValueError without), anything else through as_device_table (table_of must then be None)."""
+    if isinstance(tbl, TableBank):
+        if table_of is None:
+            raise ValueError("a TableBank needs table_of=: one table index per chunk-boundary column")
+        return tbl
+    if table_of is not None:
+        raise ValueError("table_of= goes with a TableBank")
+    return as_device_table(tbl)
 
 
 # --------------------------------------------------------------------------
@@ -165,15 +181,17 @@ def delay_compensated_interpolation_easy(irs_and_delaydiffs, continuous_index: f
 # --------------------------------------------------------------------------
 # a6
 # --------------------------------------------------------------------------
-def interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=None):
+def interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=None, table_of=None):
     """Batched table arithmetic of interpolate_2d (apply_hrtf.py:219-279) for
     precomputed parameters: idx int32 [n,4], w float64 [n,3] (numpy or device
     tensors).  Returns a device tensor [n, 2, L] float32 (`out` if given).
     validate=False skips the index range check (a host<->device sync).
-    gain: None, or one float64 value per query ([n]): H[q] = gain[q] interpolate_2d(q)."""
-    tbl = as_device_table(tbl)
+    gain: None, or one float64 value per query ([n]): H[q] = gain[q] interpolate_2d(q).
+    table_of: with a TableBank as tbl, a contiguous int32 device tensor of `cols` table indices, cols
+    dividing n: query q is interpolated in table table_of[q % cols] (bas_interp2d_bank_f32)."""
+    tbl = table_or_bank(tbl, table_of)
     with _hip.on_device(tbl.device):
-        return _interpolate_2d_params(tbl, idx, w, out, validate, ws, gain)
+        return _interpolate_2d_params(tbl, idx, w, out, validate, ws, gain, table_of)
 
 
 # ---- per-source gain at chunk boundaries (DESIGN.md §3.10) -----------------------------------------------------------
@@ -227,9 +245,9 @@ def _flat_device_gain(gain, n_q):
     return gain.reshape(-1)
 
 
-def _interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=None):
+def _interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=None, table_of=None):
     import torch
-    tbl = as_device_table(tbl)
+    tbl = table_or_bank(tbl, table_of)
     dev = tbl.device
     idx_t = torch.as_tensor(idx, dtype=torch.int32).reshape(-1, 4).contiguous().to(dev)
     w_t = torch.as_tensor(w, dtype=torch.float64).reshape(-1, 3).contiguous().to(dev)
@@ -242,6 +260,15 @@ def _interpolate_2d_params(tbl, idx, w, out=None, validate=True, ws=None, gain=N
     ws_bytes = _hip.lib().bas_interp2d_workspace_bytes(n)
     if ws is None or ws.numel() < ws_bytes:
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    if table_of is not None:                                # a bank: the gain is optional to its entry
+        table_of = table_columns_to_device(tbl, table_of, n_q=n)
+        g = None
+        if gain is not None:
+            g, _ = gain_to_device(gain.reshape(-1) if hasattr(gain, "reshape") else np.reshape(gain, -1), (n,), dev)
+        _hip.call("bas_interp2d_bank_f32", _hip.ptr(tbl.packed), _hip.ptr(tbl.diffs), _hip.ptr(idx_t), _hip.ptr(w_t),
+                  _hip.ptr(g), n, tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(H), _hip.ptr(ws), ws.numel(),
+                  _hip.ptr(table_of), table_of.numel(), tbl.n_tables, _hip.current_stream(dev))
+        return H
     if gain is None:
         _hip.call("bas_interp2d_f32", _hip.ptr(tbl.packed), _hip.ptr(tbl.diffs), _hip.ptr(idx_t), _hip.ptr(w_t), n,
                   tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(H), _hip.ptr(ws), ws.numel(), _hip.current_stream(dev))
@@ -339,7 +366,7 @@ def render_workspace_bytes(n_src, t_in, chunksize, subchunksize, L):
 @_hip.on_device_of("x")
 def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix", out=None, events=None,
                          ws=None, ws_plans=None, fused=None, angles=None, n_queries=None, want_peak=True, check=False,
-                         plans_ready=False, gain=None):
+                         plans_ready=False, gain=None, table_of=None):
     """interpolate_2d + render for precomputed parameters: x [n_src, T_in] device float32,
     idx int32 [n_src*(n_chunks+1), 4], w float64 [.., 3] on the device.  Uses the fused kernel
     (chunk IRs evaluated inside the FIR kernel, never stored) when the sizes allow it, else
@@ -351,12 +378,18 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     plans_ready=True: ws_plans already holds this scene's read plans (plan_angles_device on another stream, ordered before
     this call by the caller): only the fused FIR is launched; needs n_queries and a shape the fused kernels serve.
     gain: None, or one float64 gain per query (a contiguous device tensor of n_queries values): the chunk
-    IRs become gain[q] interpolate_2d(q) (in the read plans, or in the stored IRs of the other path)."""
+    IRs become gain[q] interpolate_2d(q) (in the read plans, or in the stored IRs of the other path).
+    table_of: with a TableBank as tbl, a contiguous int32 device tensor of one table index per chunk
+    boundary column (T_in/K + 1 entries): every source's boundary k is rendered through table table_of[k].  The plans
+    (or stored IRs) come from the bank entries; the FIR entry points are the same calls, given the bank's packed tables
+    and n_tables * ndir.  The fused path of a bank plans from angles (angles=)."""
     import torch
-    tbl = as_device_table(tbl)
+    tbl = table_or_bank(tbl, table_of)
     dev = x.device
     n_src, t_in = x.shape
     lib = _hip.lib()
+    if table_of is not None:
+        table_of = table_columns_to_device(tbl, table_of, cols=t_in // chunksize + 1)
     if normalize not in ("mix", "none"):
         raise ValueError("normalize must be 'mix' or 'none'")
     if fused is None or fused:                                # default: fused wherever the kernel serves the shape
@@ -371,7 +404,7 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
         if idx is None:                                       # (angles given, shape not served by the fused kernel)
             idx, w = sphere.interpolation_params_device(angles[0], angles[1], branch=angles[2])
             idx, w = idx.reshape(-1, 4), w.reshape(-1, 3)
-        H = interpolate_2d_params(tbl, idx, w, validate=False, ws=ws_plans, gain=gain)
+        H = interpolate_2d_params(tbl, idx, w, validate=False, ws=ws_plans, gain=gain, table_of=table_of)
         return render_device(x, chunksize, subchunksize, H.view(n_src, n_q // max(n_src, 1), 2, tbl.L), tbl.L,
                              normalize, out=out, events=events, ws=ws)
     t_out = t_in + tbl.L - 1
@@ -387,6 +420,8 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     if plans_ready:
         if ws_plans.numel() < pb:
             raise ValueError("plans_ready: ws_plans is smaller than bas_interp2d_workspace_bytes(n_queries)")
+    elif angles is None and table_of is not None:
+        raise ValueError("a TableBank's read plans are made from angles (angles=, or render_angles_device)")
     elif angles is None and gain is None:
         _hip.call("bas_interp2d_plan_f32", _hip.ptr(tbl.diffs), _hip.ptr(idx), _hip.ptr(w), n_q, tbl.ndir, tbl.L,
                   tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
@@ -395,9 +430,10 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
                   tbl.ndir, tbl.L, tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
     else:                                                     # small batch: a3 + plans in one launch
         e, z, branch = angles
-        _plan_angles_call(tbl, e, z, gain, n_q, branch, ws_plans, dev, stream)
+        _plan_angles_call(tbl, e, z, gain, n_q, branch, ws_plans, dev, stream, table_of)
+    ndir = tbl.ndir if table_of is None else tbl.ndir_all     # (the FIR entry points size the table resource by it)
     args = (_hip.ptr(x), x.stride(0), _hip.ptr(tbl.packed), _hip.ptr(ws_plans), n_src, t_in, chunksize, subchunksize, tbl.L,
-            tbl.upsampling, tbl.ndir, _hip.ptr(y), 0, _hip.ptr(peak), int(normalize == "mix"), _hip.ptr(ws), ws.numel(), stream)
+            tbl.upsampling, ndir, _hip.ptr(y), 0, _hip.ptr(peak), int(normalize == "mix"), _hip.ptr(ws), ws.numel(), stream)
     if events is None:
         _hip.call("bas_render_mix_fused_f32", *args)          # peak rule included (:462-464)
     else:
@@ -407,27 +443,33 @@ def render_params_device(x, chunksize, subchunksize, tbl, idx, w, normalize="mix
     return y, peak
 
 
-def _plan_angles_call(tbl, elev, azim, gain, n_q, branch, ws_plans, dev, stream):
-    """a3 + read plans in one launch; with a gain (flat float64 device tensor) the gained instantiation."""
+def _plan_angles_call(tbl, elev, azim, gain, n_q, branch, ws_plans, dev, stream, table_of=None):
+    """a3 + read plans in one launch; with a gain (flat float64 device tensor) the gained instantiation; with table_of
+    (checked by the caller) tbl is a bank and the launch its entry's (the gain optional)."""
     ring_elev, ring_start, ring_count = sphere._ring_args()
     common = (ring_elev, ring_start, ring_count, _hip.ptr(sphere.device_nodes(dev)), sphere.BRANCHES[branch], tbl.ndir,
               tbl.L, tbl.upsampling, _hip.ptr(ws_plans), ws_plans.numel(), stream)
-    if gain is None:
+    if table_of is not None:                                  # (table_of, cols, n_tables) in front of the stream
+        _hip.call("bas_interp2d_plan_angles_bank_f32", _hip.ptr(tbl.diffs), _hip.ptr(elev), _hip.ptr(azim),
+                  _hip.ptr(gain), n_q, *common[:-1], _hip.ptr(table_of), table_of.numel(), tbl.n_tables, stream)
+    elif gain is None:
         _hip.call("bas_interp2d_plan_angles_f32", _hip.ptr(tbl.diffs), _hip.ptr(elev), _hip.ptr(azim), n_q, *common)
     else:
         _hip.call("bas_interp2d_plan_angles_gain_f32", _hip.ptr(tbl.diffs), _hip.ptr(elev), _hip.ptr(azim),
                   _hip.ptr(gain), n_q, *common)
 
 
-def plan_angles_device(tbl, elev, azim, ws_plans, branch="f64", gain=None):
+def plan_angles_device(tbl, elev, azim, ws_plans, branch="f64", gain=None, table_of=None):
     """The first launch of render_angles_device alone, on the current stream: trajectory angles (float64 device tensors,
     one per source and chunk boundary) -> a3 -> the fused kernels' read plans in ws_plans (uint8 device tensor of at least
     bas_interp2d_workspace_bytes(elev.numel()) bytes).  For callers that render a SEQUENCE of scenes and let the plans of
     the next one be computed beside the FIR of the current one (bench.py --overlap-plans; a rank's share of a multi-GPU
     scene leaves CUs free): render_params_device(..., plans_ready=True) is the other half.  gain: None, or a contiguous
-    float64 device tensor of one gain per angle, folded into the plans' weights."""
+    float64 device tensor of one gain per angle, folded into the plans' weights.
+    table_of: with a TableBank as tbl, a contiguous int32 device tensor of `cols` table indices, cols
+    dividing the number of angles: angle q (flat) is planned in table table_of[q % cols]."""
     import torch
-    tbl = as_device_table(tbl)
+    tbl = table_or_bank(tbl, table_of)
     if not (elev.is_cuda and azim.is_cuda and elev.dtype == torch.float64 and azim.dtype == torch.float64
             and elev.is_contiguous() and azim.is_contiguous() and elev.numel() == azim.numel()):
         raise ValueError("elev/azim must be contiguous float64 device tensors of equal size")
@@ -437,7 +479,9 @@ def plan_angles_device(tbl, elev, azim, ws_plans, branch="f64", gain=None):
     gain = _flat_device_gain(gain, n_q)
     if ws_plans.numel() < _hip.lib().bas_interp2d_workspace_bytes(n_q):
         raise ValueError("ws_plans is smaller than bas_interp2d_workspace_bytes(n_queries)")
-    _plan_angles_call(tbl, elev, azim, gain, n_q, branch, ws_plans, dev, _hip.current_stream(dev))
+    if table_of is not None:
+        table_of = table_columns_to_device(tbl, table_of, n_q=n_q)
+    _plan_angles_call(tbl, elev, azim, gain, n_q, branch, ws_plans, dev, _hip.current_stream(dev), table_of)
     return ws_plans
 
 
@@ -447,7 +491,7 @@ MERGED_A3_MAX_QUERIES = 1 << 30     # a3 rides inside the plan kernel (one launc
 
 def render_angles_device(x, chunksize, subchunksize, tbl, elev, azim, normalize="mix", out=None, events=None,
                          ws=None, ws_plans=None, fused=None, params=None, branch="f64", want_peak=True, check=False,
-                         plans_ready=False, gain=None):
+                         plans_ready=False, gain=None, table_of=None):
     """The whole device side of make_signal_move_2d for trajectories that live on the GPU: x [n_src, T_in] device
     float32 (T_in % K == 0), elev / azim float64 device tensors [n_src, T_in/K + 1] (radians at t = 0, K, .., T_in).
     bas_traj_params_f64 (a3 + the elevation bracket), then render_params_device (read plans + fused FIR where the
@@ -457,8 +501,10 @@ def render_angles_device(x, chunksize, subchunksize, tbl, elev, azim, normalize=
     in which both ears' threads redid the angle arithmetic, lost above 65 536 queries - 53 us against 9 + 15 us for 221 k;
     round 4's does it once per query: equal there, 3 us ahead for a 32-source share: tools/ab_a3_merge.py).  `params` is
     only written by the two-launch form (MERGED_A3_MAX_QUERIES = 0).
-    gain: None, or a contiguous float64 device tensor of one gain per angle."""
-    tbl = as_device_table(tbl)
+    gain: None, or a contiguous float64 device tensor of one gain per angle.
+    table_of: with a TableBank as tbl, a contiguous int32 device tensor of one table index per chunk
+    boundary column (T_in/K + 1 entries); the angles must then be contiguous."""
+    tbl = table_or_bank(tbl, table_of)
     n_src, t_in = x.shape
     if elev.numel() != n_src * (t_in // chunksize + 1) or azim.numel() != elev.numel():
         raise ValueError("elev/azim must hold one angle per source and chunk boundary")
@@ -471,7 +517,10 @@ def render_angles_device(x, chunksize, subchunksize, tbl, elev, azim, normalize=
             raise ValueError("branch must be 'f64' or 'pyfloat'")
         return render_params_device(x, chunksize, subchunksize, tbl, None, None, normalize, out=out, events=events, ws=ws,
                                     ws_plans=ws_plans, fused=fused, angles=(elev, azim, branch), n_queries=elev.numel(),
-                                    want_peak=want_peak, check=check, plans_ready=plans_ready, gain=gain)
+                                    want_peak=want_peak, check=check, plans_ready=plans_ready, gain=gain,
+                                    table_of=table_of)
+    if table_of is not None:
+        raise ValueError("a TableBank needs contiguous angle tensors (the merged a3 + plan launch)")
     if plans_ready:
         raise ValueError("plans_ready needs contiguous angle tensors (the merged a3 + plan launch)")
     idx, w = sphere.interpolation_params_device(elev, azim, out=params, branch=branch)

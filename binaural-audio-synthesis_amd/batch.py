@@ -132,7 +132,8 @@ def _all_finite(a):
 
 
 def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None, normalize="each", branch="f64",
-                 contiguous=False, check=False, max_samples=None, events=None, gain=None, delay=None, interp="cubic"):
+                 contiguous=False, check=False, max_samples=None, events=None, gain=None, delay=None, interp="cubic",
+                 tables=None):
     """Render B independent clips in one device render, each as make_signal_move_2d renders it alone.
 
     signals: [B, N] (one source per item) or [B, n_src, N] (small scenes, mixed per item as render_sources mixes), numpy
@@ -155,26 +156,36 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
     delay: None, or float64 of elev's shape [B, (n_src,) n_q_max]: each source's propagation delay in samples at each of its
     item's chunk boundaries (interp "cubic" or "linear").  The pack launch writes the delayed inputs (no
     launch more); item b's reads are bounded by its own valid length.  Host delays must be finite and at least the
-    interpolator's d_min (ValueError); device tensors are checked for shape and dtype only."""
+    interpolator's d_min (ValueError); device tensors are checked for shape and dtype only.
+    tables: with a TableBank as tbl, one table index per item (required; host values, out of range:
+    ValueError): item b is rendered through table tables[b] of the bank."""
     import torch
     from . import _hip, sphere, propagation
     from .apply_hrtf import as_device_table, render_angles_device, gain_to_device
+    from .bank import TableBank, check_tables, batch_table_columns
     B, n_src, N, n = _check_args(tuple(signals.shape), lengths, tuple(np.shape(elev)), tuple(np.shape(azim)),
                                  chunksize, subchunksize, normalize)
     if branch not in sphere.BRANCHES:
         raise ValueError("branch must be 'f64' or 'pyfloat'")
     if not (_all_finite(elev) and _all_finite(azim)):
         raise ValueError("trajectory contains non-finite angles")
+    if isinstance(tbl, TableBank):                        # (validated before any device work)
+        if tables is None:
+            raise ValueError("a TableBank needs tables=: one table index per item")
+        tables = check_tables(tables, B, tbl.n_tables, "item")
+    elif tables is not None:
+        raise ValueError("tables= goes with a TableBank")
+    else:
+        tbl = as_device_table(tbl)
     g_all = None
     if gain is not None:                                  # (validated before any device work)
-        g_all = gain_to_device(gain, tuple(np.shape(elev)), as_device_table(tbl).device)[0].reshape(B, n_src, -1)
+        g_all = gain_to_device(gain, tuple(np.shape(elev)), tbl.device)[0].reshape(B, n_src, -1)
     d_all = None
     if delay is not None:
         code = propagation.interp_code(interp)
-        d_all = propagation.delay_to_device(delay, tuple(np.shape(elev)), interp, as_device_table(tbl).device)
+        d_all = propagation.delay_to_device(delay, tuple(np.shape(elev)), interp, tbl.device)
         d_all = d_all.reshape(B, n_src, -1)
     K, S = int(chunksize), int(subchunksize)
-    tbl = as_device_table(tbl)
     dev = tbl.device
     L = tbl.L
     groups = split_items(n, K, L, n_src, max_samples)
@@ -219,8 +230,9 @@ def render_batch(signals, chunksize, subchunksize, elev, azim, tbl, lengths=None
                           stride, _hip.ptr(ang[0]), _hip.ptr(ang[1]), _hip.ptr(ang[2]), stream)
             if events is not None:
                 events[1].record()
+            t_of = None if tables is None else torch.from_numpy(batch_table_columns(lay, tables[b0:b1])).to(dev)
             y, _ = render_angles_device(x, K, S, tbl, ang[0], ang[1], normalize="none", branch=branch, want_peak=False,
-                                        check=check, gain=None if g_all is None else ang[2])
+                                        check=check, gain=None if g_all is None else ang[2], table_of=t_of)
             if events is not None:
                 events[2].record()
             _hip.call("bas_batch_finish_f32", _hip.ptr(y), y.stride(0), nb, _hip.ptr(meta[1]), _hip.ptr(meta[2]),

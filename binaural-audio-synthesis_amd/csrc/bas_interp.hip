@@ -26,6 +26,7 @@
 // with the 16 weights W_k folded once per (query, ear) in binary64.
 #include "bas_internal.h"
 #include "bas_plan.h"
+#include "../../include/bas_bank.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -265,13 +266,19 @@ struct PlanAngles {
 // interpolated one - every one of the 16 weights is multiplied by gain[q] in binary64 and rounded to binary32 once (the
 // crossfade of apply_hrtf.py:443 then runs between gained IRs unchanged).  `gain` is the last argument so that the
 // GAIN = false instantiations read their other arguments at the same offsets as before and never touch it.
-template <int ANG, int WAVE_STAGED = 0, bool GAIN = false>
+// BANK (include/bas_bank.h): `diffs` and the packed rows are those of table table_of[q % cols] of a bank of
+// n_tables tables side by side - the table's base goes into the 16 byte offsets, so whoever reads the plans reads the right
+// table without knowing of banks.  Weights, o4 and the staging are untouched.  Its three arguments follow `gain` for the same
+// reason: the BANK = false instantiations are the code they were (same registers, same LDS) and never touch them.
+template <int ANG, int WAVE_STAGED = 0, bool GAIN = false, bool BANK = false>
 __global__ __launch_bounds__(256) void bas_interp2d_plan_kernel(const double *__restrict__ diffs,
                                                                   const int32_t *__restrict__ idx,
                                                                   const double *__restrict__ w, int n,
                                                                   int ndir, int L, int U,
                                                                   EarPlanS *__restrict__ plans, PlanAngles PA,
-                                                                  const double *__restrict__ gain) {
+                                                                  const double *__restrict__ gain,
+                                                                  const int32_t *__restrict__ table_of, int cols,
+                                                                  int n_tables) {
     long t = blockIdx.x * 256L + threadIdx.x;
     if (t >= 2L * n) t = 2L * n - 1;                         // (idle threads of the last block redo its last record: barrier below)
     const long q = t >> 1;
@@ -310,6 +317,13 @@ __global__ __launch_bounds__(256) void bas_interp2d_plan_kernel(const double *__
     const int pt = clamp_dir(ix[0], ndir), qt = clamp_dir(ix[1], ndir);
     const int pb = clamp_dir(ix[2], ndir), qb = clamp_dir(ix[3], ndir);
     const double at = wt[0], ab = wt[1], a = wt[2];
+    int tab_row = 0;                                         // float offset of the query's table in the bank's `packed`
+    if constexpr (BANK) {
+        int tb = table_of[(int)q % cols];                                        // (q < n: an int)
+        tb = tb < 0 ? 0 : (tb >= n_tables ? n_tables - 1 : tb);                 // memory safety, as clamp_dir
+        diffs += (long)tb * 2 * ndir * ndir;
+        tab_row = tb * (2 * ndir * U * BAS_PLANE(L));                           // (the whole bank is below 2^29 floats)
+    }
     const double *d = diffs + (long)e * ndir * ndir;
     // delays of the two ring interpolations in non-upsampled samples (apply_hrtf.py:106)
     const double dt = (at * ((double)U * d[(long)pt * ndir + qt])) / (double)U;
@@ -324,6 +338,10 @@ __global__ __launch_bounds__(256) void bas_interp2d_plan_kernel(const double *__
     const int c_top = bas_submod(0, b4, M);
     ring_plan(top, d, e, ndir, pt, qt, at, L, U, c_top, s2);
     ring_plan(bot, d, e, ndir, pb, qb, ab, L, U, bas_submod(c_top, b3, M), s2);
+    if constexpr (BANK) {
+        top.row_p += tab_row; top.row_q += tab_row;
+        bot.row_p += tab_row; bot.row_q += tab_row;
+    }
     // the four read sets: (packed row, offset c of read 0 in upsampled samples); read j of a set sits at c - j
     const int set_row[4] = {bot.row_q, bot.row_p, top.row_q, top.row_p};
     const int set_c[4] = {bot.c_q, bot.c_p, top.c_q, top.c_p};
@@ -554,13 +572,35 @@ extern "C" size_t bas_interp2d_workspace_bytes(int n) {
 
 // the plan kernel for a batch of n queries: per-wave staging from BAS_PLAN_WAVE_STAGED_FROM queries on, GAIN when `gain` is
 // given (the gain-less launches pick exactly the instantiations they always did)
+// With a bank (table_of given; bas_bank.h) the BANK instantiation of the same choice.
 typedef void (*plan_fn)(const double *, const int32_t *, const double *, int, int, int, int, EarPlanS *, PlanAngles,
-                        const double *);
+                        const double *, const int32_t *, int, int);
+template <int ANG, bool BANK>
+static plan_fn plan_kernel_of(bool big, bool gain) {
+    if (gain) return big ? bas_interp2d_plan_kernel<ANG, 1, true, BANK> : bas_interp2d_plan_kernel<ANG, 0, true, BANK>;
+    return big ? bas_interp2d_plan_kernel<ANG, 1, false, BANK> : bas_interp2d_plan_kernel<ANG, 0, false, BANK>;
+}
 template <int ANG>
-static plan_fn plan_kernel_for(int n, const double *gain) {
+static plan_fn plan_kernel_for(int n, const double *gain, const int32_t *table_of = nullptr) {
     const bool big = n >= BAS_PLAN_WAVE_STAGED_FROM;
-    if (gain) return big ? bas_interp2d_plan_kernel<ANG, 1, true> : bas_interp2d_plan_kernel<ANG, 0, true>;
-    return big ? bas_interp2d_plan_kernel<ANG, 1, false> : bas_interp2d_plan_kernel<ANG, 0, false>;
+    return table_of ? plan_kernel_of<ANG, true>(big, gain != nullptr) : plan_kernel_of<ANG, false>(big, gain != nullptr);
+}
+
+// A bank of n_tables tables (bas_bank.h): what the two bank entries check on top of their namesakes' checks.
+struct BankArgs {
+    const int32_t *table_of;
+    int cols, n_tables;
+};
+static int bank_check(const char *who, const BankArgs *bank, int n, int ndir, int L, int U) {
+    if (!bank) return 0;
+    BAS_REQUIRE(bank->table_of || n == 0, BAS_E_NULL, "%s: null pointer (table_of)", who);
+    BAS_REQUIRE(bank->n_tables > 0 && bank->cols > 0 && n % bank->cols == 0, BAS_E_SHAPE,
+                "%s: need n_tables>0, cols>0, n %% cols == 0 (n=%d cols=%d n_tables=%d)", who, n, bank->cols, bank->n_tables);
+    BAS_REQUIRE(U >= BAS_PLAN_MIN_U, BAS_E_SHAPE, "%s: banks need an upsampling factor >= %d (U=%d)", who, BAS_PLAN_MIN_U, U);
+    const long per_table = bas_table_floats(ndir, L, U);                     // (>= 0: checked by the caller)
+    BAS_REQUIRE((__int128)per_table * bank->n_tables * 4 < ((__int128)1 << 31), BAS_E_SHAPE,
+                "%s: a bank of %d tables of %ld floats is 2^31 bytes or more", who, bank->n_tables, per_table);
+    return 0;
 }
 
 // bas_interp2d_plan_f32 / bas_interp2d_plan_gain_f32 (gain == null: the former)
@@ -578,7 +618,8 @@ static int plan_impl(const char *who, const double *diffs, const int32_t *idx, c
                 bas_interp2d_workspace_bytes(n), plans_bytes);
     const long rows = 2L * n;
     hipLaunchKernelGGL(plan_kernel_for<0>(n, gain), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, bas_stream(stream),
-                       diffs, idx, w, n, ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PlanAngles{}, gain);
+                       diffs, idx, w, n, ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PlanAngles{}, gain,
+                       (const int32_t *)nullptr, 0, 0);
     return bas_check_launch(who);
 }
 
@@ -597,7 +638,7 @@ extern "C" int bas_interp2d_plan_gain_f32(const double *diffs, const int32_t *id
 static int plan_angles_impl(const char *who, const double *diffs, const double *elev, const double *azim,
                             const double *gain, bool need_gain, int n, const double *ring_elev, const int32_t *ring_start,
                             const int32_t *ring_count, const float *node_az, int branch, int ndir, int L, int U,
-                            void *plans, size_t plans_bytes, bas_stream_t stream) {
+                            void *plans, size_t plans_bytes, bas_stream_t stream, const BankArgs *bank = nullptr) {
     BAS_REQUIRE(diffs && ring_elev && ring_start && ring_count && node_az &&
                     ((elev && azim && (gain || !need_gain)) || n == 0),
                 BAS_E_NULL, "%s: null pointer", who);
@@ -606,6 +647,7 @@ static int plan_angles_impl(const char *who, const double *diffs, const double *
     BAS_REQUIRE(branch == BAS_BRANCH_F64 || branch == BAS_BRANCH_PYFLOAT, BAS_E_SHAPE,
                 "%s: branch must be BAS_BRANCH_F64 (0) or BAS_BRANCH_PYFLOAT (1), got %d", who, branch);
     BAS_REQUIRE(bas_table_floats(ndir, L, U) >= 0, BAS_E_SHAPE, "%s: table too large", who);
+    if (int rc = bank_check(who, bank, n, ndir, L, U)) return rc;
     if (n == 0) return 0;
     BAS_REQUIRE(plans && plans_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(plans) % 16 == 0,
                 BAS_E_WORKSPACE, "%s: 16-byte aligned buffer of %zu bytes needed, %zu given", who,
@@ -620,10 +662,23 @@ static int plan_angles_impl(const char *who, const double *diffs, const double *
                     BAS_E_SHAPE, "%s: ring %d out of the %d-direction table", who, i, ndir);
     }
     const long rows = 2L * n;
-    const plan_fn fn = branch == BAS_BRANCH_PYFLOAT ? plan_kernel_for<2>(n, gain) : plan_kernel_for<1>(n, gain);
+    const BankArgs bk = bank ? *bank : BankArgs{nullptr, 0, 0};
+    const plan_fn fn = branch == BAS_BRANCH_PYFLOAT ? plan_kernel_for<2>(n, gain, bk.table_of)
+                                                    : plan_kernel_for<1>(n, gain, bk.table_of);
     hipLaunchKernelGGL(fn, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, bas_stream(stream), diffs, nullptr, nullptr, n,
-                       ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PA, gain);
+                       ndir, L, U, reinterpret_cast<EarPlanS *>(plans), PA, gain, bk.table_of, bk.cols, bk.n_tables);
     return bas_check_launch(who);
+}
+
+// bas_bank.h: the gained entry over a bank; gain may be null
+extern "C" int bas_interp2d_plan_angles_bank_f32(const double *diffs, const double *elev, const double *azim,
+                                                 const double *gain, int n, const double *ring_elev,
+                                                 const int32_t *ring_start, const int32_t *ring_count, const float *node_az,
+                                                 int branch, int ndir, int L, int U, void *plans, size_t plans_bytes,
+                                                 const int32_t *table_of, int cols, int n_tables, bas_stream_t stream) {
+    const BankArgs bank = {table_of, cols, n_tables};
+    return plan_angles_impl("bas_interp2d_plan_angles_bank_f32", diffs, elev, azim, gain, false, n, ring_elev, ring_start,
+                            ring_count, node_az, branch, ndir, L, U, plans, plans_bytes, stream, &bank);
 }
 
 extern "C" int bas_interp2d_plan_angles_f32(const double *diffs, const double *elev, const double *azim, int n,
@@ -646,12 +701,13 @@ extern "C" int bas_interp2d_plan_angles_gain_f32(const double *diffs, const doub
 
 static int interp2d_impl(const char *who, const float *packed, const double *diffs, const int32_t *idx, const double *w,
                          const double *gain, bool need_gain, int n, int ndir, int L, int U, float *H, void *ws,
-                         size_t ws_bytes, bas_stream_t stream) {
+                         size_t ws_bytes, bas_stream_t stream, const BankArgs *bank = nullptr) {
     BAS_REQUIRE(packed && diffs && ((idx && w && H && (gain || !need_gain)) || n == 0), BAS_E_NULL, "%s: null pointer",
                 who);   // (no queries: idx, w, H may be null)
     BAS_REQUIRE(n >= 0 && ndir > 0 && L > 0 && U > 0, BAS_E_SHAPE,
                 "%s: need n>=0, ndir>0, L>0, U>0 (n=%d ndir=%d L=%d U=%d)", who, n, ndir, L, U);
     BAS_REQUIRE(bas_table_floats(ndir, L, U) >= 0, BAS_E_SHAPE, "%s: table too large", who);
+    if (int rc = bank_check(who, bank, n, ndir, L, U)) return rc;
     if (n == 0) return 0;
     BAS_REQUIRE(ws && ws_bytes >= bas_interp2d_workspace_bytes(n) && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
                 BAS_E_WORKSPACE, "%s: 16-byte aligned workspace of %zu bytes needed, %zu given", who,
@@ -672,14 +728,16 @@ static int interp2d_impl(const char *who, const float *packed, const double *dif
         snprintf(what, sizeof what, "%s(generic)", who);
         return bas_check_launch(what);
     }
-    hipLaunchKernelGGL(plan_kernel_for<0>(n, gain), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, diffs, idx, w, n,
-                       ndir, L, U, plans, PlanAngles{}, gain);
+    const BankArgs bk = bank ? *bank : BankArgs{nullptr, 0, 0};
+    hipLaunchKernelGGL(plan_kernel_for<0>(n, gain, bk.table_of), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, diffs,
+                       idx, w, n, ndir, L, U, plans, PlanAngles{}, gain, bk.table_of, bk.cols, bk.n_tables);
     snprintf(what, sizeof what, "%s(plan)", who);
     int rc = bas_check_launch(what);
     if (rc) return rc;
     long blocks = ((long)n + 3) / 4;
     if (blocks > 16384) blocks = 16384;
-    const unsigned table_bytes = (unsigned)((size_t)2 * ndir * U * BAS_PLANE(L) * sizeof(float));
+    // (a bank: the resource spans all its tables - below 2^31 bytes, bank_check)
+    const unsigned table_bytes = (unsigned)((size_t)(bank ? bk.n_tables : 1) * 2 * ndir * U * BAS_PLANE(L) * sizeof(float));
     hipLaunchKernelGGL(bas_interp2d_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, st, packed, table_bytes, plans,
                        (long)n, L, H);
     snprintf(what, sizeof what, "%s(eval)", who);
@@ -698,6 +756,16 @@ extern "C" int bas_interp2d_gain_f32(const float *packed, const double *diffs, c
                                      size_t ws_bytes, bas_stream_t stream) {
     return interp2d_impl("bas_interp2d_gain_f32", packed, diffs, idx, w, gain, true, n, ndir, L, U, H, ws, ws_bytes,
                          stream);
+}
+
+// bas_bank.h: the stored chunk IRs over a bank (plan, then eval over the whole bank); gain may be null
+extern "C" int bas_interp2d_bank_f32(const float *packed, const double *diffs, const int32_t *idx, const double *w,
+                                     const double *gain, int n, int ndir, int L, int U, float *H, void *ws,
+                                     size_t ws_bytes, const int32_t *table_of, int cols, int n_tables,
+                                     bas_stream_t stream) {
+    const BankArgs bank = {table_of, cols, n_tables};
+    return interp2d_impl("bas_interp2d_bank_f32", packed, diffs, idx, w, gain, false, n, ndir, L, U, H, ws, ws_bytes, stream,
+                         &bank);
 }
 
 // ---------------------------------------------------------------------------

@@ -146,9 +146,11 @@ class _BlockStream:
     stream-ordered work of one block), input_view, _boundary_view (a block's part of an angle or gain buffer), _carried
     (the tensors prepare() must leave as they were) and _emitted (the samples a block emits)."""
 
+    _device_table = staticmethod(as_device_table)         # what a renderer takes as its table (a bank: StreamBatchRenderer alone)
+
     def __init__(self, tbl, chunksize, subchunksize, graph, copy_out, lead, max_delay=None, interp="cubic"):
         assert chunksize % subchunksize == 0, 'subchunksize does not divide chunksize evenly'
-        self.tbl = as_device_table(tbl)
+        self.tbl = self._device_table(tbl)
         self.K, self.S = int(chunksize), int(subchunksize)
         self.halo = halo_samples(self.K, self.tbl.L)
         self.nh = self.halo // self.K                     # chunk boundaries carried with the halo

@@ -29,7 +29,8 @@ import numpy as np
 
 from . import _hip, sphere, propagation
 from .batch import MAX_RENDER_SAMPLES, render_batch
-from .apply_hrtf import check_gain, gain_to_device
+from .apply_hrtf import as_device_table, check_gain, gain_to_device, render_angles_device
+from .bank import TableBank, check_tables, stream_table_columns
 from .stream import _BlockStream, _is_buffer, halo_samples, rotate_into_views, stage
 from ._stage import MAX_SESSIONS, session_indices, session_runs
 
@@ -112,14 +113,29 @@ def plan_stream_layout(n_sessions, n_src, K, L, B):
     return lay
 
 
+def _table_or_bank(tbl):
+    return tbl if isinstance(tbl, TableBank) else as_device_table(tbl)
+
+
 class StreamBatchRenderer(_BlockStream):
+    _device_table = staticmethod(_table_or_bank)          # (the one renderer of the core that takes a bank)
+
     def __init__(self, tbl, n_sessions, n_src, chunksize, subchunksize, graph=True, copy_out=True, max_delay=None,
-                 interp="cubic"):
+                 interp="cubic", tables=None):
         """n_sessions independent streams of n_src sources each.  graph, copy_out, max_delay, interp: as
-        for StreamRenderer (max_delay: every block needs delay=, and every session carries its own raw history)."""
+        for StreamRenderer (max_delay: every block needs delay=, and every session carries its own raw history).
+        tbl may be a TableBank: tables is then one table index per session (default: all 0; values out
+        of range: ValueError), session g is rendered through table tables[g], and set_tables() changes the choice."""
         import torch
         self.G, self.n_src = int(n_sessions), int(n_src)
         plan_stream_layout(self.G, self.n_src, int(chunksize), 1, int(chunksize))   # (session and source counts: ValueError)
+        self._tables = None                               # host copy of every session's table index (a bank's renderer)
+        self._table_of = None                             # the layout's column array on the device (int32 [n_q])
+        if isinstance(tbl, TableBank):
+            self._tables = check_tables(np.zeros(self.G, dtype=np.int32) if tables is None else tables, self.G,
+                                        tbl.n_tables, "session")
+        elif tables is not None:
+            raise ValueError("tables= goes with a TableBank")
         super().__init__(tbl, chunksize, subchunksize, graph, copy_out, (self.G, self.n_src), max_delay, interp)
         dev = self.tbl.device
         self._lay = None                                  # layout of the current block size
@@ -160,6 +176,8 @@ class StreamBatchRenderer(_BlockStream):
                 if new is not None:
                     self._a3(new, lay)[:, :, :nh] = self._a3(old)[:, :, :nh]
         self._lay, self._x, self._elev_all, self._azim_all, self._gain_all = lay, x, elev, azim, gain
+        if self._tables is not None:                      # a bank: the table of every column, here, before any capture
+            self._table_of = torch.from_numpy(stream_table_columns(lay, self._tables)).to(dev)
         # the raw rows only grow (the histories stay in front): after longer blocks their row stride is the longest
         # block's, not this layout's, and samples of those blocks lie behind H + B, where no kernel reads
         if self._raw_rows is not None:
@@ -176,6 +194,35 @@ class StreamBatchRenderer(_BlockStream):
     def layout(self, B):
         """The StreamLayout of blocks of B samples (no device work)."""
         return plan_stream_layout(self.G, self.n_src, self.K, self.tbl.L, B)
+
+    # ---- a bank's tables (DESIGN.md §3.26) -------------------------------------------------------------
+    @property
+    def tables(self):
+        """int32 [G] (host copy): every session's table index; None for a renderer of one table."""
+        return None if self._tables is None else self._tables.copy()
+
+    def set_tables(self, tables, sessions=None):
+        """Give these sessions (None: all G) other tables of the bank: one index per listed session, in ascending
+        session order as finish() returns its tails; values out of range are a ValueError.  The column array is rewritten
+        in place - the same device memory, so a captured graph reads the new values - and the change takes effect from
+        the next block: a hard switch with no crossfade, in which the session's carried halo is planned with the new
+        table as well.  From that block on the session's output is that of a renderer that had the new table from the
+        start and was fed the same blocks."""
+        import torch
+        if self._tables is None:
+            raise ValueError("set_tables: the renderer was built with one table, not a TableBank")
+        idx = session_indices(sessions, self.G)
+        new = check_tables(tables, len(idx), self.tbl.n_tables, "listed session")
+        self._tables[idx] = new
+        if self._table_of is not None:                    # (stream-ordered behind the blocks rendered so far)
+            self._table_of.copy_(torch.from_numpy(stream_table_columns(self._lay, self._tables)))
+
+    def _render_window(self, x, elev, azim, gain=None):
+        if self._table_of is None:
+            return super()._render_window(x, elev, azim, gain)
+        render_angles_device(x, self.K, self.S, self.tbl, elev, azim, normalize="none", out=self._y, ws=self._ws,
+                             ws_plans=self._ws_plans, events=self._events, want_peak=False, gain=gain,
+                             table_of=self._table_of)
 
     def input_view(self, B):
         """Device view [G, n_src, B] (strided) of the renderer's own input buffer for blocks of B samples.  A producer that
@@ -369,7 +416,8 @@ class StreamBatchRenderer(_BlockStream):
     def finish(self, sessions, return_peaks=False):
         """Emit the last L-1 samples of these sessions' streams (the tail the reference appends, apply_hrtf.py:410), as
         StreamRenderer.finish: each session's [halo | K zeros] window with its halo angles (and gains), then its end angle twice,
-        rendered for the listed sessions only, in one batched render (render_batch: the gap behind each window is at least
+        rendered for the listed sessions only (each through its own table of a bank), in one batched render (render_batch:
+        the gap behind each window is at least
         L-1 samples, so a tail reads no other session's inputs).  The tail's samples count into the sessions' peaks; then
         the slots restart as fresh streams (reset).  Returns a device tensor [len(sessions), L-1, 2] in ascending session
         order, and with return_peaks=True also float32 [len(sessions)] (host): the finished streams' final peaks."""
@@ -390,7 +438,8 @@ class StreamBatchRenderer(_BlockStream):
             if self._gain_all is not None:                # the halo's carried gains, then the end gain twice
                 end = self._gain_last.index_select(0, sel)[:, :, None]
                 gain = torch.cat([self._a3(self._gain_all)[:, :, :nh].index_select(1, sel).transpose(0, 1), end, end], dim=2)
-            out, _, _ = render_batch(sig, K, self.S, ang[0], ang[1], self.tbl, normalize="none", gain=gain)
+            out, _, _ = render_batch(sig, K, self.S, ang[0], ang[1], self.tbl, normalize="none", gain=gain,
+                                     tables=None if self._tables is None else self._tables[idx])
             tails.copy_(out[:, halo:halo + L - 1])
             self._peaks.index_copy_(0, sel, torch.maximum(self._peaks.index_select(0, sel), tails.abs().amax(dim=(1, 2))))
         final = self._peaks[idx].cpu().numpy() if return_peaks else None
