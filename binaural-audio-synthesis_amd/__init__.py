@@ -12,7 +12,7 @@ from .stream_batch import StreamBatchRenderer  # noqa: F401
 from .scene import render_scene, SceneStreamRenderer  # noqa: F401
 from .reverb import LateTail, late_tail  # noqa: F401
 from .limiter import limit, StreamLimiter  # noqa: F401
-from .loudness import measure, StreamMeter, normalize_loudness  # noqa: F401
+from .loudness import measure, StreamMeter, normalize_loudness, master  # noqa: F401
 from .rate import convert_rate, StreamRateConverter  # noqa: F401
 from .output import (OutputFilter, filter_output, StreamOutputFilter, headphone_eq, crosstalk_canceller,  # noqa: F401
                      speaker_plant)

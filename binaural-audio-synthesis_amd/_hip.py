@@ -213,6 +213,15 @@ BANK_SIGNATURES = {
                                        _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_int, _c_int, _c_void_p]),
 }
 
+# name -> (restype, argtypes); must list every symbol of include/bas_limit_tp.h (the true-peak limiter, DESIGN.md §3.27: the
+# same library, a header of its own; bas_limit_f32's parameter list)
+LIMIT_TP_SIGNATURES = {
+    "bas_limit_tp_state_floats": (_c_size_t, [_c_int, _c_int]),
+    "bas_limit_tp_f32": (_c_int, [_c_void_p, _c_long, _c_long, _c_long, _c_void_p, _c_long, _c_long, _c_long, _c_int, _c_long,
+                                  _c_long, ctypes.c_double, _c_int, _c_int, _c_void_p, _c_long, _c_void_p, _c_void_p,
+                                  _c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7                                                    # BAS_ABI_VERSION of include/bas.h
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libbas_hip_diag.so")   # -DBAS_DIAG build: reads BAS_FORCE_KERNEL (tests only)
@@ -255,7 +264,8 @@ def _load(path):
             f"or `make -C {os.path.dirname(path)}`.  There is no CPU fallback.")
     import torch                                # noqa: F401  first: PyTorch-ROCm brings its own libamdhip64, and the library
     handle = ctypes.CDLL(path)                  # must bind to THAT runtime (loaded the other way round a second HIP runtime
-    for table in (SIGNATURES, RATE_SIGNATURES, OUTPUT_SIGNATURES, BANK_SIGNATURES):   # comes up beside torch's and sees no device)
+    for table in (SIGNATURES, RATE_SIGNATURES, OUTPUT_SIGNATURES, BANK_SIGNATURES,   # comes up beside torch's and sees no device)
+                  LIMIT_TP_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(handle, name)          # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args

@@ -365,6 +365,35 @@ def normalize_loudness(y, fs, target=-23.0, max_true_peak=-1.0):
     return y32 * g[:, None, None], g_db
 
 
+def master(y, fs, target=-23.0, max_true_peak=-1.0, lookahead_ms=5.0, hold_ms=20.0):
+    """(out, gain_db, Loudness): the signal (as measure() takes it) brought to `target` LUFS integrated with the FULL gain -
+    not stopped where the true peak would meet the ceiling, as normalize_loudness stops it - and then held under
+    `max_true_peak` dBTP by the true-peak limiter (limiter.limit(true_peak=True)) with this look-ahead
+    and hold; the Loudness is measure() of `out`.  Per session for [G, n, 2]; a signal that reads -inf gets gain_db = 0.
+    The limiter only takes level away, so out's integrated loudness is at most the target's (less where it worked hard),
+    and its true peak passes the ceiling by no more than §3.27 quotes."""
+    import torch
+    from . import limiter
+    target, max_true_peak = _check_targets(target, max_true_peak)
+    fs = check_fs(fs)
+    A, Hd = limiter.samples_from_ms(fs, lookahead_ms, hold_ms)
+    ceiling, A, Hd = limiter.check_params(10.0 ** (max_true_peak / 20.0), A, Hd)
+    host = not isinstance(y, torch.Tensor)
+    if host:
+        y = torch.from_numpy(stereo_host(y)).to(_hip.require_gpu())
+    elif not y.is_cuda:
+        raise ValueError("y must be a device tensor (or a host array)")
+    stereo_device(y, "y")
+    L = measure(y, fs).integrated.double()
+    g_db = torch.where(torch.isfinite(L), target - L, torch.zeros_like(L))
+    g = (10.0 ** (g_db / 20.0)).float()
+    out = limiter.limit(y * (g if y.dim() == 2 else g[:, None, None]), ceiling, A, Hd, true_peak=True)
+    if not host:
+        return out, g_db, measure(out, fs)
+    out = out.cpu().numpy()
+    return out, (float(g_db) if y.dim() == 2 else g_db.cpu().numpy()), measure(out, fs)
+
+
 class StreamMeter:
     """The meter behind a stream of blocks, for n_sessions independent stereo streams in one launch.
 
